@@ -6,9 +6,16 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement).  How the numbers are taken:
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times the K steps, writes the
+last step's outputs when --dump-outputs DIR is given and prints the line; `kernels` and everything after it below (except the
+replica checksum of an N > 1 run) is measured only with --full.  How the numbers are taken:
 
   value / ms_per_step   K steps timed CLEAN (no events inside the region), barrier + synchronize on both sides, max over ranks.
+  --dump-outputs DIR    after the timed steps: what the last step computed, as DIR/<name>.npy (float32) -- `losses` (the
+                        [loss, ang, mag] Trainer.step returns), `pred` (the U-Net output of its forward), `params` (the parameter
+                        arena after its Adam update) and `grads` (its gradient arena).  An array of more than DUMP_SAMPLE values
+                        is stored as a fixed, seeded sample of at most DUMP_SAMPLE of them (flattened, ascending index): the files stay
+                        under 64 MB; the inputs are seeded, so two builds run with the same arguments compare file for file.
   kernels               a SECOND pass (3 steps) with one HIP-event pair per conv launch on the launch stream; every label carries
                         the kernel symbol the library launches for it (pg_conv_describe: the name rocprofv3 reports).
   roofline              the kernel with the LARGEST total time per step in that pass (not the fastest one): its algorithmic FLOPs
@@ -22,11 +29,12 @@ Rank 0 prints ONE JSON line (contract in the task statement).  How the numbers a
   other_precisions      (N = 1, fp32 run only) the same step re-timed in the two optional MFMA operand modes ("bf16x3", "bf16").
                         Reported beside the headline, never as `value`.
   dp                    (N > 1) self-diagnosis of the data-parallel path: ranks that really took part in an all-reduce, a checksum
-                        of the parameter arena compared across ranks (a diverged replica FAILS the bench), each bucket's
-                        all-reduce timed alone, the compute-only step and the fraction of communication hidden under backward.
+                        of the parameter arena compared across ranks (a diverged replica FAILS the bench; every N > 1 run), and
+                        with --full each bucket's all-reduce timed alone, the compute-only step and the fraction of communication
+                        hidden under backward.
 
-  other_configs         (N = 1, fp32 headline run only) the other BASELINE configurations measured in the SAME process, so that the
-                        driver's record carries them too -- never as `value`:
+  other_configs         (N = 1, fp32 headline run with --full only) the other BASELINE configurations measured in the SAME process,
+                        never as `value`:
                           fwd            configs[1]: forward only, batch 32 x 1024 x 256, fp32 (+ encoder_convs = D0-D3 together)
                           e2e            configs[4]: 32 stereo clips -> STFT 2048/512 + polar -> U-Net forward on the bf16-resident
                                          kernels -> ISTFT, with its own roofline against the dense bf16 MFMA peak
@@ -55,6 +63,7 @@ PEAK_BF16_MFMA_TFLOPS = 2516.6  # dense bf16: 16 x the fp32 rate (v_mfma_f32_32x
 # figure; the bf16 lines also carry the fraction of this measured, power-limited rate.
 SUSTAINED_BF16_MFMA_TFLOPS_RANDOM = 1778.0
 PEAK_HBM_TBPS = 8.0             # MI355X_MICROARCH.md: HBM3E ~8 TB/s (about 6.3 TB/s is what a streaming kernel reaches)
+DUMP_SAMPLE = 1 << 22          # values per --dump-outputs file at most: 4 arrays x 16 MB stay under 64 MB
 DTYPES = {"fp32": "f32", "bf16": "bf16 operands / f32 accumulate",
           "bf16x3": "f32 operands split hi+lo into 3 bf16 MFMA products / f32 accumulate"}
 
@@ -200,10 +209,22 @@ def quiet_stdout():
 def emit(out):
     line = (json.dumps(out) + "\n").encode()
     sys.stdout.flush()
-    if _REAL_STDOUT is None:
-        os.write(1, line)
-    else:
-        os.write(_REAL_STDOUT, line)
+    fd = 1 if _REAL_STDOUT is None else _REAL_STDOUT
+    while line:                         # os.write may write less than asked to a pipe
+        line = line[os.write(fd, line):]
+
+
+def dump_outputs(torch, path, arrays):
+    """Write each device tensor of ``arrays`` as path/<name>.npy in float32; one of more than DUMP_SAMPLE values as its values at
+    up to DUMP_SAMPLE fixed indices, drawn from a generator seeded with its size (the same in every run and build)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(t.numel()).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def kernel_pass(torch, ops, step_fn, steps, fl, peak, step_ms):
@@ -287,9 +308,9 @@ def roofline_of(by, peak, step_tflops, precision, headline_shape, alg_bytes=None
             "by_kernel": by}
 
 
-def dp_diagnostics(torch, dist, trainer, batch, world, step_ms):
+def dp_diagnostics(torch, dist, trainer, batch, world, step_ms, full):
     """N > 1 only.  When the replicas' parameters differ after the timed steps the line carries dp.error / "invalid" and the
-    process exits with status 3 after printing it."""
+    process exits with status 3 after printing it.  The timings (2) and (3) only with ``full``."""
     from phasegen.unet import BACKWARD_ORDER
     eng = trainer.engine
     flat = eng.arena.flat
@@ -309,6 +330,8 @@ def dp_diagnostics(torch, dist, trainer, batch, world, step_ms):
     if not same:        # the run is INVALID: say so in the line (rank 0 still prints it) and exit non-zero after it
         out["error"] = "data-parallel replicas diverged"
         out["checksums"] = [[float(v) for v in t.cpu()] for t in got]
+        return out
+    if not full:
         return out
     # (2) every bucket's all-reduce alone on an otherwise idle chip (events on the launch stream, which waits for RCCL's)
     red = trainer.reducer
@@ -359,7 +382,7 @@ def run_train(a, torch, dist, world, rank, local):
     from phasegen.trainer import Trainer
     C, L, B = a.channels, a.frames, a.batch
     peak = PEAK_FP32_MFMA_TFLOPS if a.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
-    dev = device_info(torch) if rank == 0 else None
+    dev = device_info(torch, probe=a.full) if rank == 0 else None
     torch.manual_seed(0)
     model = UNetModel(C, 2 * C, gpu_ids=[local], precision=a.precision)
     selftest = a.dp_selftest and world == 1         # one-rank RCCL group: every collective of the N > 1 path is really issued
@@ -386,14 +409,19 @@ def run_train(a, torch, dist, world, rank, local):
         dt = float(t.item())
     loss_val = [float(v) for v in losses.cpu()]
     step_ms = dt / a.steps * 1e3
-    dp = dp_diagnostics(torch, dist, trainer, batch, world, step_ms) if (world > 1 or selftest) else None
+    if a.dump_outputs and rank == 0:
+        arena = model.engine.arena
+        dump_outputs(torch, a.dump_outputs, {"losses": losses, "pred": model.engine.intermediates()["out"],
+                                             "params": arena.flat, "grads": arena.grad})
+    dp = dp_diagnostics(torch, dist, trainer, batch, world, step_ms, a.full) if (world > 1 or selftest) else None
 
-    fl = conv_flops(C, L, B)
-    step_flops = 3 * sum(fl.values()) - fl["D0"]
-    ks, by = kernel_pass(torch, ops, lambda: trainer.step(batch), 3, fl, peak, step_ms)
-    hbm, hbm_mode = kernel_pass.hbm, "the timed step's own launches"
+    if a.full:
+        fl = conv_flops(C, L, B)
+        step_flops = 3 * sum(fl.values()) - fl["D0"]
+        ks, by = kernel_pass(torch, ops, lambda: trainer.step(batch), 3, fl, peak, step_ms)
+        hbm, hbm_mode = kernel_pass.hbm, "the timed step's own launches"
     plain = None
-    if trainer.fuse_adam:
+    if a.full and trainer.fuse_adam:
         # the wgrad launches above carry the Adam update of their weight (24 B of HBM traffic per parameter in the epilogue, not
         # counted in `achieved`'s flops): time the same kernels once more WITHOUT it, so the line shows both
         trainer.fuse_adam = False
@@ -418,15 +446,17 @@ def run_train(a, torch, dist, world, rank, local):
                    "adam": ("fused into the wgrad epilogues" if trainer.fuse_adam else
                             ("per-layer slices on a side stream" if trainer.overlap_adam else "one launch after backward")),
                    "final_loss": loss_val},
-        "roofline": roofline_of(by, peak, step_flops / (dt / a.steps) / 1e12, a.precision, (C, L, B) == (1024, 256, 64),
-                                conv_bytes(C, L, B, trainer.fuse_adam)),
-        "hbm_kernels": {"bound": "hbm", "peak_TBps": PEAK_HBM_TBPS, "from": hbm_mode,
-                        "what": "algorithmic bytes (each operand once: BatchNorm forward 1 read + 1-2 writes, backward 2 reads + 1 write, "
-                                "loss 16 B in + 8 B out per bin-frame, Adam 28 B per parameter) / HIP-event time of the launch on its stream",
-                        "by_kernel": hbm},
-        "kernels": ks,
-        "device": dev,
     }
+    if a.full:
+        out["roofline"] = roofline_of(by, peak, step_flops / (dt / a.steps) / 1e12, a.precision, (C, L, B) == (1024, 256, 64),
+                                      conv_bytes(C, L, B, trainer.fuse_adam))
+        out["hbm_kernels"] = {"bound": "hbm", "peak_TBps": PEAK_HBM_TBPS, "from": hbm_mode,
+                              "what": "algorithmic bytes (each operand once: BatchNorm forward 1 read + 1-2 writes, backward 2 reads + 1 "
+                                      "write, loss 16 B in + 8 B out per bin-frame, Adam 28 B per parameter) / HIP-event time of the "
+                                      "launch on its stream",
+                              "by_kernel": hbm}
+        out["kernels"] = ks
+    out["device"] = dev
     if plain is not None:
         dom = out["roofline"]["kernel"].split(" (")[0]
         if dom in plain:
@@ -444,7 +474,7 @@ def run_train(a, torch, dist, world, rank, local):
     if a.rehearse_on_one_gpu and world > 1:
         out["rehearsal"] = True
         out["rehearsal_note"] = f"{world} ranks share ONE GPU and all-reduce through the host (gloo): code-path check, not a measurement"
-    if world == 1 and a.precision == "fp32" and not a.no_other_precisions:
+    if a.full and world == 1 and a.precision == "fp32" and not a.no_other_precisions:
         other = {}
         for mode in ("bf16x3", "bf16"):
             model.engine.precision = ops.precision_code(mode)
@@ -459,10 +489,10 @@ def run_train(a, torch, dist, world, rank, local):
             other[mode] = {"ms_per_step": d1 * 1e3, "frames_per_s": B * L / d1, "step_tflops": round(step_flops / d1 / 1e12, 2)}
         model.engine.precision = ops.precision_code("fp32")
         out["other_precisions"] = other
-    if world == 1 and a.precision == "fp32" and not a.no_other_configs and (C, L, B) == (1024, 256, 64):
+    if a.full and world == 1 and a.precision == "fp32" and not a.no_other_configs and (C, L, B) == (1024, 256, 64):
         out["other_configs"] = other_configs(torch, dist, model, C, L, B)      # (each leg catches its own failure)
         out["projected_dp_efficiency_8gpu"] = projected_dp_efficiency(out)
-    if world == 1 and not a.no_cpu_baseline and a.precision == "fp32":
+    if a.full and world == 1 and not a.no_cpu_baseline and a.precision == "fp32":
         del trainer, model, batch
         torch.cuda.empty_cache()
         try:
@@ -777,7 +807,7 @@ def run_e2e(a, torch, dist, world, rank, local):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=["train", "fwd", "e2e"], default="train",
                     help="train = the headline (BASELINE configs[2]/[3]); fwd = configs[1]; e2e = configs[4]")
@@ -800,11 +830,20 @@ def main():
                     help="A/B: N = 1 runs the Adam update of every conv weight inside its wgrad kernel's epilogue; this flag falls back to "
                          "per-layer slices of a separate Adam kernel on a side stream (what N > 1 ranks always run)")
     ap.add_argument("--serial-adam", action="store_true", help="A/B: one Adam launch after backward instead of per-layer slices on a side stream")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline: per-kernel passes and rooflines, HBM kernels, the device's MFMA probe, "
+                         "other precisions, other configurations, the CPU baseline and the data-parallel timings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (--config train only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-precisions", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the fwd / e2e / ref_default / dp_equivalent legs of the default line")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the fwd / e2e / ref_default / dp_equivalent legs of the --full line")
     ap.add_argument("--cpu-threads", type=int, default=None)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.config != "train":
+        ap.error("--dump-outputs covers the training step (--config train)")
     a.precision_given = a.precision is not None
     if a.precision is None:
         a.precision = "fp32"

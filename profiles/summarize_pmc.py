@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Condense rocprofv3 CSV output (gpurun_out/..., scratch) into the small, committed files under profiles/.
+"""Condense rocprofv3 CSV output (profiles/collect.sh's raw output directory) into the small, committed files under profiles/.
 
-    python profiles/summarize_pmc.py r03 gpurun_out/prof_r03_train gpurun_out/pmc_r03_train_FETCH_SIZE gpurun_out/pmc_r03_train_WRITE_SIZE ...
+    python profiles/summarize_pmc.py r03 profile_out/prof_r03_train profile_out/pmc_r03_train_FETCH_SIZE profile_out/pmc_r03_train_WRITE_SIZE ...
     (normally through  bash profiles/collect.sh --summarize r03)
 
   <tag>_kernel_stats.csv   verbatim `rocprofv3 --kernel-trace --stats` per-kernel table

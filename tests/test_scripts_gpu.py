@@ -74,7 +74,7 @@ def test_bench_contract_line_and_dp_selftest(tmp_path):
     from inside backward, parameter checksum across ranks, per-bucket timings) on a one-rank group."""
     import json
     out = run([os.path.join(ROOT, "bench.py"), "--channels", "32", "--frames", "64", "--batch", "4", "--steps", "2", "--warmup", "1",
-               "--no-cpu-baseline", "--no-other-precisions", "--dp-selftest"], cwd=str(tmp_path))
+               "--full", "--no-cpu-baseline", "--no-other-precisions", "--dp-selftest"], cwd=str(tmp_path))
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and out.strip() == lines[0], out[:400]     # stdout holds the line and nothing else (RCCL's banner goes to stderr)
     d = json.loads(lines[0])
@@ -92,6 +92,31 @@ def test_bench_contract_line_and_dp_selftest(tmp_path):
     assert set(dp["allreduce_alone_ms"]) == {"U0", "U1", "U2", "U3", "D3", "D2", "D1", "D0"} and dp["step_ms_compute_only"] > 0
 
 
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """Without --full the line holds the headline alone (no per-kernel pass, no other leg), --steps sets the timed steps, and
+    --dump-outputs writes what the last timed step computed: two runs with the same arguments write the same arrays."""
+    import json
+    args = [os.path.join(ROOT, "bench.py"), "--channels", "32", "--frames", "64", "--batch", "4", "--steps", "3", "--warmup", "1"]
+    lines, dumps = [], []
+    for i in range(2):
+        out = run(args + ["--dump-outputs", str(tmp_path / f"out{i}")], cwd=str(tmp_path))
+        assert len(out.splitlines()) == 1, out[:400]
+        lines.append(json.loads(out))
+        dumps.append({f: np.load(tmp_path / f"out{i}" / f) for f in os.listdir(tmp_path / f"out{i}")})
+    d = lines[0]
+    assert d["metric"] == "spectrogram-frames/sec (train fwd+bwd)" and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 4 * 64 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert not {"roofline", "hbm_kernels", "kernels", "other_precisions", "other_configs", "cpu_baseline", "dp"} & set(d)
+    assert "mfma_probe" not in d["device"]
+    assert set(dumps[0]) == {"losses.npy", "pred.npy", "params.npy", "grads.npy"}
+    assert sum(v.nbytes for v in dumps[0].values()) <= 64 << 20
+    assert dumps[0]["pred.npy"].size == 4 * 64 * 64 and np.allclose(dumps[0]["losses.npy"], d["config"]["final_loss"])
+    for name, v in dumps[0].items():
+        assert v.dtype == np.float32 and np.isfinite(v).all() and np.any(v != 0), name
+        np.testing.assert_array_equal(dumps[1][name], v, err_msg=name)       # seeded inputs, bit-reproducible kernels
+
+
 def test_bench_two_ranks_rehearsed_on_one_gpu(tmp_path):
     """`bench.py --gpus 2` exactly as the driver launches it (torch.distributed.run, one process per rank), except that both
     ranks share cuda:0 and all-reduce over gloo (--rehearse-on-one-gpu; RCCL refuses two ranks on one device): the N > 1
@@ -102,7 +127,7 @@ def test_bench_two_ranks_rehearsed_on_one_gpu(tmp_path):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     out = run(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--channels", "32", "--frames", "64",
-               "--batch", "4", "--steps", "2", "--warmup", "1", "--rehearse-on-one-gpu"], cwd=str(tmp_path))
+               "--batch", "4", "--steps", "2", "--warmup", "1", "--full", "--rehearse-on-one-gpu"], cwd=str(tmp_path))
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and out.strip() == lines[0], out[:400]     # ... also with two ranks (gloo's rank chatter, the other rank's prints)
     d = json.loads(lines[0])
