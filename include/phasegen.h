@@ -63,7 +63,11 @@ typedef struct pg_conv_args {
                                      /*   and as ReLU by the up path, model.py:80,82,113)                           */
     void* workspace; int64_t workspace_bytes; /* optional scratch (pg_workspace_bytes_conv()): lets tile counts   */
                                      /*   that quantise badly over the CUs be split evenly (stream-K);      */
-                                     /*   contents are garbage between calls; NULL = always one tile per WG */
+                                     /*   contents are garbage between calls; NULL = always one tile per WG. */
+                                     /*   *_wgrad at fp32 also packs its operands here, behind that region: */
+                                     /*   it needs pg_workspace_bytes_wgrad(a, op) bytes (else              */
+                                     /*   PG_ERR_WORKSPACE); more than pg_workspace_bytes_conv() never      */
+                                     /*   changes how a call splits its work                                 */
     const struct pg_adam_args* adam; /* *_wgrad only, optional (NULL): the optimiser step of THIS weight fused into the   */
                                      /*   wgrad epilogue (train.py:61-62 in one kernel): adam->p / m / v are the weight,   */
                                      /*   exp_avg and exp_avg_sq tensors (layout of w), updated from the gradient value the */
@@ -72,6 +76,10 @@ typedef struct pg_conv_args {
                                      /*   this call on the stream.  Not for data-parallel runs (reduce first).             */
 } pg_conv_args;
 int64_t pg_workspace_bytes_conv(void);
+/* Workspace one wgrad call needs (op: PG_OP_CONV1D_WGRAD / PG_OP_CONVT1D_WGRAD, below): pg_workspace_bytes_conv() plus the fp32
+ * raw-window kernels' packed operands (Q rows with zero halos, P with K contiguous per row; activation applied).  A pure host
+ * function of the geometry, precision and schedule (pointers are not read); a negative value is the call's error code. */
+int64_t pg_workspace_bytes_wgrad(const pg_conv_args* a, int32_t op);
 /* pg_conv_args.precision (BASELINE config 5): PG_PREC_FP32 (0, default) = fp32 operands, v_mfma_f32_32x32x2_f32, the 1e-4
  * parity path; PG_PREC_BF16 = operands rounded to bf16 (RNE, after the fused activation) at fragment load,
  * v_mfma_f32_32x32x16_bf16, fp32 accumulate -- tensors and master weights in HBM stay fp32; PG_PREC_BF16X3 = every fp32

@@ -41,6 +41,12 @@ struct IgemmParams {
     // G (wgrad) only: optional Adam update fused into the epilogue (pg_conv_args.adam): parameter / exp_avg / exp_avg_sq
     // tensors shaped like dW, updated from the gradient value the epilogue stores.  ad_p == NULL: plain wgrad.
     float* ad_p; float* ad_m; float* ad_v; PgAdamScalars ad;
+    // G (wgrad), fp32: both operands packed by the launcher into the caller's workspace (conv_raw_wgrad.hip, pack_g), activation
+    // applied, so that the slab loop gathers every slab with one fixed instruction sequence and no range checks:
+    //   qk: Q rows [b][q][Lq], position t of the row at index p + t, zeros around [0, Lx) (qk_bs = Q * Lq floats per sample);
+    //   pk: P flat-K [m][Kp] (Kp = nslab * 16, zero tail), or per sample [b][m][Kp] (Kp = 16 ceil(LP / 16), zeros from LP on)
+    const float* qk; unsigned qk_bytes; int qk_bs, Lq;
+    const float* pk; unsigned pk_bytes; int Kp;
 };
 
 }  // namespace pgconv
@@ -522,6 +528,9 @@ constexpr int RS2 = 768, RS1 = 384;       // floats reserved per channel window 
 // tiles spanning many short samples (U = 31 columns per sample at the U-Net's bottleneck) still fit their window slots
 constexpr int raw_gap(int tj) { return tj >= 8 ? 16 : tj; }
 constexpr int RTILE_A = RBM * BK;         // weight tile, same swizzled image as above (8 KB)
+// raw-window wgrad (conv_raw_wgrad.hip): floats of Q's row one channel's window slot holds per slab (window 15 s + k, padded so
+// that the fragment reads stay conflict-free); the host sizes the packed rows by it
+constexpr int g_wlp(int kw, int s) { return kw == 32 ? 64 : (kw == 8 ? (s == 1 ? 24 : 40) : 36); }
 
 enum Kind { KIND_F, KIND_T, KIND_G };
 
@@ -532,7 +541,7 @@ namespace pgconv {
 hipError_t launch_im2col(int kind, const IgemmParams& p, int grid, hipStream_t st, int prec);   // conv_im2col.hip
 hipError_t launch_raw_ft(int kind, const IgemmParams& p, int grid, hipStream_t st, int prec);   // conv_raw.hip (F / T, tile 128 x 256)
 hipError_t launch_raw_ft_tall(int kind, const IgemmParams& p, int grid, hipStream_t st, int prec);   // conv_raw_tall.hip (256 x 128)
-hipError_t launch_raw_g(const IgemmParams& p, int grid, hipStream_t st, int prec);              // conv_raw_wgrad.hip
+hipError_t launch_raw_g(const IgemmParams& p, int grid, hipStream_t st, int prec);              // conv_raw_wgrad.hip (fp32: packs first)
 // conv_h3.hip: 4 waves at ONE per SIMD, wave tile 256 x 64, tile 256 x 256
 hipError_t launch_h3(int kind, const IgemmParams& p, int grid, hipStream_t st);
 hipError_t launch_h3_fixup(int kind, const IgemmParams& p, int grid, unsigned split_tiles, bool wide, hipStream_t st);

@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <cmath>
+#include <algorithm>
 #include "conv_common.h"
 
 namespace {
@@ -123,6 +124,7 @@ struct Knobs {
     int force_colsplit;   // 1 = split wherever the geometry allows, whatever the cost model says (bit 18: tests reach the tail launch on small problems)
     int no_colsplit;  // 1 = never split the columns past the last full 256-wide tile off into a tail launch (bit 17: A/B, tests)
     char* desc; int desc_len;   // pg_conv_describe: write the launch plan here INSTEAD of launching
+    long* pack_need;  // pg_workspace_bytes_wgrad: write the packed operands' bytes here INSTEAD of launching
 };
 int decode_knobs(const pg_conv_args* a, Knobs& k) {
     if (a->precision < 0 || a->precision > 2) return pg_fail(PG_ERR_UNSUPPORTED, "conv: precision must be PG_PREC_FP32, PG_PREC_BF16 or PG_PREC_BF16X3");
@@ -142,7 +144,7 @@ int decode_knobs(const pg_conv_args* a, Knobs& k) {
     k.no_colsplit = (sc >> 17) & 1;
     k.force_colsplit = (sc >> 18) & 1;
     if (k.no_raw3 && k.all_raw3) return pg_fail(PG_ERR_SHAPE, "conv: schedule bits 13 and 14 exclude each other");
-    k.desc = nullptr; k.desc_len = 0;
+    k.desc = nullptr; k.desc_len = 0; k.pack_need = nullptr;
     return PG_OK;
 }
 
@@ -215,8 +217,31 @@ bool raw_supported(Kind kind, const IgemmParams& p, const Knobs& kn, int tn = RB
     return sc * (tn - 1) + tj + raw_gap(tj) * (nseg_max - 1) + (kind == KIND_T ? tj : 0) <= (sc == 1 ? RS1 : RS2);
 }
 
+constexpr long WS_STREAMK = (long)MAX_STREAMK_WG * WS_PER_WG;   // pg_workspace_bytes_conv(): the stream-K region of the workspace
+
+// fp32 raw-window wgrad: layout of the packed operands (IgemmParams.qk / .pk, conv_raw_wgrad.hip), which live in the workspace
+// behind its stream-K region.  Q rows reach S * (last gathered frame) + WLP floats (the window slot of the last slab), at least
+// p + Lx; P has Kp = nslab * 16 frames per row (flat K) or 16 ceil(LP / 16) per sample (per-sample slabs).  Returns the bytes, or
+// -1 where an operand would not fit 31-bit buffer offsets.
+long g_pack_layout(IgemmParams& p) {
+    const int cps = (p.LP + 15) / 16;
+    const long gimax = p.g_ps ? 16L * (cps - 1) : (long)p.LP - 1;
+    long lq = (long)p.s * gimax + g_wlp(p.k, p.s);
+    if (lq < (long)p.p + p.Lx) lq = (long)p.p + p.Lx;
+    lq = (lq + 3) / 4 * 4;
+    const long kp = p.g_ps ? 16L * cps : 16L * p.nslab;
+    const long qbytes = (long)p.B * p.Q * lq * 4, pbytes = (p.g_ps ? (long)p.B : 1L) * p.M * kp * 4;
+    if (qbytes >= 0x7ffffff0L || pbytes >= 0x7ffffff0L) return -1;
+    p.Lq = (int)lq; p.qk_bs = (int)((long)p.Q * lq); p.qk_bytes = (unsigned)qbytes;
+    p.Kp = (int)kp; p.pk_bytes = (unsigned)pbytes;
+    return (qbytes + 255) / 256 * 256 + pbytes;
+}
+
 int launch(Kind kind, IgemmParams& p, const Knobs& kn, long rows, long cols, long Ktot, long ws_bytes, hipStream_t st, bool may_split = true) {
     const long Ktot_in = Ktot;
+    const long ws_all = ws_bytes;
+    // the schedule is a function of the stream-K region only: a workspace that also holds packed wgrad operands splits the same way
+    if (ws_bytes > WS_STREAMK) ws_bytes = WS_STREAMK;
     bool raw = raw_supported(kind, p, kn);
     // F / T problems whose columns the tall 256 x 128 tile covers with at least 3 % fewer computed ones take it (and those whose
     // windows only fit the narrower tile: many short samples per tile): small-batch
@@ -272,11 +297,11 @@ int launch(Kind kind, IgemmParams& p, const Knobs& kn, long rows, long cols, lon
                 kb.no_raw3 = 1; kb.all_raw3 = 0;
                 char tail[160] = "";
                 if (kn.desc) { kb.desc = tail; kb.desc_len = (int)sizeof tail; }
-                int rc = launch(kind, p, kn, rows, full, Ktot_in, ws_bytes, st, false);
+                int rc = launch(kind, p, kn, rows, full, Ktot_in, ws_all, st, false);
                 if (rc != PG_OK) return rc;
                 IgemmParams pb = p;
                 pb.n_lo = (int)full;
-                rc = launch(kind, pb, kb, rows, rem, Ktot_in, ws_bytes, st, false);
+                rc = launch(kind, pb, kb, rows, rem, Ktot_in, ws_all, st, false);
                 if (rc == PG_OK && kn.desc) {          // "...|tail=conv_raw_kernel<...>,grid=G"
                     char* bar = strchr(tail, '|');
                     if (bar) { *bar = ','; bar = strchr(bar, '|'); if (bar) *bar = 0; }
@@ -302,6 +327,10 @@ int launch(Kind kind, IgemmParams& p, const Knobs& kn, long rows, long cols, lon
     p.nslab = (int)((Ktot + BK - 1) / BK);
     const long tiles = (long)p.tilesM * p.tilesN;
     if (tiles <= 0 || tiles > 0x0fffffffL || p.nslab <= 0 || cols + bn >= 0x7fffffffL) return pg_fail(PG_ERR_SHAPE, "conv: empty or oversize grid");   // the fixup launches 8 workgroups per tile
+    const bool packed = raw && kind == KIND_G && kn.prec == 0;        // fp32 raw-window wgrad: operands packed into the workspace first
+    const long pack = packed ? g_pack_layout(p) : 0;
+    if (pack < 0) return pg_fail(PG_ERR_SHAPE, "wgrad: packed operand exceeds 2 GiB (31-bit buffer offsets)");
+    if (kn.pack_need) { *kn.pack_need = pack; return PG_OK; }
     const int grid = r3 ? pick_grid(tiles, p.nslab, p, ws_bytes, kn.force_mode, kn.oversub, kn.contended, 1, 2 * WS_PER_WG)
                         : pick_grid(tiles, p.nslab, p, ws_bytes, kn.force_mode, kn.oversub, kn.contended);
     // ranges made of whole tiles (grid == tiles, or a grid that divides the tile count) leave nothing for the fixup
@@ -315,6 +344,12 @@ int launch(Kind kind, IgemmParams& p, const Knobs& kn, long rows, long cols, lon
         snprintf(kn.desc, (size_t)kn.desc_len, "%s|grid=%d|tiles=%ld|slabs=%d|split=%d|whole=%d|fixup=%s", name, grid, tiles, p.nslab, (int)split, p.whole,
                  !split ? "none" : (!r3 && fixup_wide(grid, tiles - p.whole) ? "wide" : "plain"));
         return PG_OK;
+    }
+    if (packed) {
+        if (!p.ws || ws_all < WS_STREAMK + pack)
+            return pg_fail(PG_ERR_WORKSPACE, "wgrad: the fp32 kernels need pg_workspace_bytes_wgrad() bytes of workspace (packed operands)");
+        p.qk = reinterpret_cast<const float*>(reinterpret_cast<char*>(p.ws) + WS_STREAMK);
+        p.pk = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.qk) + ((long)p.qk_bytes + 255) / 256 * 256);
     }
     hipError_t e;
     if (r3) e = pgconv::launch_raw3(kind, p, grid, st);
@@ -475,11 +510,11 @@ static int set_fused_adam(IgemmParams& p, const pg_conv_args* a) {
 }
 
 // nn.Conv1d wgrad: dw[o][c][j] = sum_{b,t} dy[b,o,t] act(x)[b,c,s*t+j-p]  -> G with P = dy (M = Cout), Q = x.
-static int run_conv1d_wgrad(const pg_conv_args* a, void* stream, char* desc, int desc_len) {
+static int run_conv1d_wgrad(const pg_conv_args* a, void* stream, char* desc, int desc_len, long* pack_need = nullptr) {
     if (int e = check_geom(a, false)) return e;
     Knobs kn; if (int e = decode_knobs(a, kn)) return e;
-    kn.desc = desc; kn.desc_len = desc_len;
-    if (!a->dy || !a->x || !a->dw) return pg_fail(PG_ERR_NULL, "conv1d_wgrad: dy, x, dw required");
+    kn.desc = desc; kn.desc_len = desc_len; kn.pack_need = pack_need;
+    if (!pack_need && (!a->dy || !a->x || !a->dw)) return pg_fail(PG_ERR_NULL, "conv1d_wgrad: dy, x, dw required");
     IgemmParams p = {};
     p.pt = a->dy; p.pt_bs = a->dy_bs; p.LP = a->Lout; p.act_p = PG_ACT_NONE;
     p.x = a->x; p.x_bs = a->x_bs; p.act_x = a->x_act; p.y = a->dw;
@@ -491,11 +526,11 @@ static int run_conv1d_wgrad(const pg_conv_args* a, void* stream, char* desc, int
 }
 
 // nn.ConvTranspose1d wgrad: dw[c][o][j] = sum_{b,i} act(x)[b,c,i] dy[b,o,s*i+j-p]  -> G with P = x (M = Cin), Q = dy.
-static int run_convt1d_wgrad(const pg_conv_args* a, void* stream, char* desc, int desc_len) {
+static int run_convt1d_wgrad(const pg_conv_args* a, void* stream, char* desc, int desc_len, long* pack_need = nullptr) {
     if (int e = check_geom(a, true)) return e;
     Knobs kn; if (int e = decode_knobs(a, kn)) return e;
-    kn.desc = desc; kn.desc_len = desc_len;
-    if (!a->dy || !a->x || !a->dw) return pg_fail(PG_ERR_NULL, "convt1d_wgrad: dy, x, dw required");
+    kn.desc = desc; kn.desc_len = desc_len; kn.pack_need = pack_need;
+    if (!pack_need && (!a->dy || !a->x || !a->dw)) return pg_fail(PG_ERR_NULL, "convt1d_wgrad: dy, x, dw required");
     IgemmParams p = {};
     p.pt = a->x; p.pt_bs = a->x_bs; p.LP = a->Lin; p.act_p = a->x_act;
     p.x = a->dy; p.x_bs = a->dy_bs; p.act_x = PG_ACT_NONE; p.y = a->dw;
@@ -581,7 +616,7 @@ static int conv_fwd_h_impl(const pg_convh_args* a, void* stream, bool query, cha
     p.ws = (float*)a->workspace;
     const long tiles = (long)p.tilesM * p.tilesN;
     if (tiles <= 0 || tiles > 0x0fffffffL || p.nslab <= 0) return pg_fail(PG_ERR_SHAPE, "conv_fwd_h: empty or oversize grid");
-    const int grid = pick_grid(tiles, p.nslab, p, a->workspace_bytes, kn.force_mode, kn.oversub, kn.contended, 1, 2 * WS_PER_WG);
+    const int grid = pick_grid(tiles, p.nslab, p, std::min((long)a->workspace_bytes, WS_STREAMK), kn.force_mode, kn.oversub, kn.contended, 1, 2 * WS_PER_WG);
     const bool split = grid != tiles && !(tiles % grid == 0);
     if (desc) {
         snprintf(desc, (size_t)desc_len, "conv_h3_kernel<%d, %d, %s>|grid=%d|tiles=%ld|slabs=%d|split=%d|whole=%d|fixup=%s",
@@ -608,4 +643,14 @@ extern "C" int pg_conv_fwd_h_describe(const pg_convh_args* a, char* buf, int32_t
 
 // Workspace a caller should hand to the conv entry points (pg_conv_args.workspace) so that badly quantised tile counts
 // can be balanced over all CUs (stream-K).  Without it every call falls back to one-tile-per-workgroup scheduling.
-extern "C" int64_t pg_workspace_bytes_conv(void) { return (int64_t)MAX_STREAMK_WG * WS_PER_WG; }
+extern "C" int64_t pg_workspace_bytes_conv(void) { return (int64_t)WS_STREAMK; }
+// Workspace of one wgrad call: the stream-K region plus, behind it, the operands the fp32 raw-window kernels pack (pure host function
+// of the geometry, precision and schedule; pointers are not read).  Negative: the call's error code.
+extern "C" int64_t pg_workspace_bytes_wgrad(const pg_conv_args* a, int32_t op) {
+    long need = 0;
+    int e;
+    if (op == PG_OP_CONV1D_WGRAD) e = run_conv1d_wgrad(a, nullptr, nullptr, 0, &need);
+    else if (op == PG_OP_CONVT1D_WGRAD) e = run_convt1d_wgrad(a, nullptr, nullptr, 0, &need);
+    else return pg_fail(PG_ERR_UNSUPPORTED, "workspace_bytes_wgrad: op must be PG_OP_CONV1D_WGRAD or PG_OP_CONVT1D_WGRAD");
+    return e != PG_OK ? (int64_t)e : (int64_t)(WS_STREAMK + need);
+}

@@ -13,7 +13,7 @@ namespace {
 // ----------------------------------------------------------------------------------------------------------------
 template <int KW, int S> struct GRaw {
     static constexpr int WL = 15 * S + KW;                                   // window floats actually read
-    static constexpr int WLP = (KW == 32) ? 64 : (KW == 8 ? (S == 1 ? 24 : 40) : 36);   // padded; keeps reads conflict-free
+    static constexpr int WLP = g_wlp(KW, S);                                 // padded; keeps reads conflict-free
     static constexpr int NQT = RBN / KW;                                      // whole channels per tile (k = 5: 51, one idle column)
     static constexpr int TNV = NQT * KW;                                      // columns of a tile that exist; also the tile pitch in N
     static constexpr int SUB = NQT * WLP;                                     // floats per sub-window set
@@ -21,11 +21,14 @@ template <int KW, int S> struct GRaw {
                                                                               //   also from lanes past SUB (k = 5: 1836 -> 1856)
     static constexpr int NE = (SUB + NT - 1) / NT;                            // gather pieces per thread and sub-window
     static constexpr int STG = RTILE_A + 2 * SUBS;                            // floats per LDS stage
+    static constexpr int SUBP = (SUB + 255) / 256 * 256;                      // fp32 loop: sub-window slot of whole 16-byte wave instructions
     static_assert(WL <= WLP, "window does not fit its slot");
 };
 
+// bf16 / bf16x3 modes (BF = 1, 2): the slab loop on the caller's tensors, with the per-slab fix-ups (sample ends, windows that
+// leave the row, activations) in the loop.  The fp32 loop (g_raw_f32 below) reads packed operands instead.
 template <int KW, int S, int BF>
-__global__ __launch_bounds__(NT, 2) void conv_g_raw_kernel(const IgemmParams p) {
+__device__ __forceinline__ void g_raw_bf(const IgemmParams& p) {
     using C = GRaw<KW, S>;
     __shared__ __attribute__((aligned(16))) float lds[2 * C::STG];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -257,7 +260,7 @@ __global__ __launch_bounds__(NT, 2) void conv_g_raw_kernel(const IgemmParams p) 
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-// Per-sample slabs (round 3): the variant for SHORT samples.  Above, a slab is 16 consecutive (b, i) of the flattened K axis:
+// Per-sample slabs (round 3): the variant for SHORT samples (the loop below serves the bf16 modes; fp32: g_ps_f32 further down).  Above, a slab is 16 consecutive (b, i) of the flattened K axis:
 // with 30 frames per sample every other slab runs over a sample boundary, and almost every remaining one has its window partly
 // outside the row, so the 2 + 2 wide gathers of the fast path are the exception and 8 + 2 x 8 dword gathers (~2400 issue cycles
 // beside 4096 of MFMA) the rule: 62-69 % of the fp32 pipe at the U-Net's bottleneck.  Here a slab is 16 consecutive frames of ONE
@@ -273,7 +276,7 @@ __global__ __launch_bounds__(NT, 2) void conv_g_raw_kernel(const IgemmParams p) 
 // the wide gathers and re-loaded element-wise by ONE extra dword instruction of wave 0 (tiles with qbase == 0 only).
 // ----------------------------------------------------------------------------------------------------------------
 template <int KW, int S, int BF>
-__global__ __launch_bounds__(NT, 2) void conv_g_ps_kernel(const IgemmParams p) {
+__device__ __forceinline__ void g_ps_bf(const IgemmParams& p) {
     using C = GRaw<KW, S>;
     constexpr int STG = RTILE_A + (C::SUB + 255) / 256 * 256;          // window image rounded up to whole 16-byte wave instructions
     constexpr int NE16 = (C::SUB / 4 + NT - 1) / NT;
@@ -424,8 +427,316 @@ __global__ __launch_bounds__(NT, 2) void conv_g_ps_kernel(const IgemmParams p) {
     }
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// fp32 slab loops on PACKED operands (round 5).  The launcher first copies both operands into the caller's workspace (pack_g
+// below; IgemmParams.qk / .pk) in layouts where every slab is gathered and read by one fixed instruction sequence:
+//   Q rows [b][q][Lq] with zero halos: position t of a row at index p + t, zeros in front and behind as far as any slab's window
+//     reaches -- a window is always whole 16-byte pieces of ONE row: no range check, no neighbouring row's values, no channel-0
+//     special case, no branch on where it lies;
+//   P flat-K [m][(b, i)] (conv_g_raw: the A tile of a slab is the same two 16-byte pieces per thread also where the slab runs over a
+//     sample end) or per sample [b][m][16 ceil(LP / 16)] (conv_g_ps: frames past LP are zeros in memory, not in registers);
+//   the activations (act_x, act_p) applied once there, not on every fragment.
+// What is left per slab: 2 A pieces and the window pieces, their slab advance in the SGPR offset; the fragment reads in use order;
+// 64 MFMAs; one barrier.  The flat-K loop keeps ONE wave-uniform branch, between interior slabs and the slab that runs into the next
+// sample (1 in 8 at 129 frames), whose elements past the sample end read the second sub-window (frame 0 of sample b + 1).  Both
+// sub-windows are gathered on every slab (on interior ones the second is a copy of the first, L2 hits): waves 0-1 carry the first,
+// waves 2-3 the second at k = 32, so every wave issues 3 pieces per slab.  Same k pairs per MFMA and the same MFMA order along K as
+// the loop with in-loop fix-ups, and the packed zeros are the values that loop selected: results are bit-identical.
+// ----------------------------------------------------------------------------------------------------------------
+template <int KW, int S>
+__device__ __forceinline__ void g_raw_f32(const IgemmParams& p) {
+    using C = GRaw<KW, S>;
+    constexpr int NP = 2 * C::SUBP / 4;                 // 16-byte pieces of both sub-window slots (a multiple of 64: wave-uniform sub)
+    constexpr int NE2 = (NP + NT - 1) / NT;
+    constexpr int STG = RTILE_A + 2 * C::SUBP;
+    static_assert(C::WLP % 4 == 0 && 2 * STG * 4 <= 64 * 1024, "16-byte window pieces; LDS budget");
+    __shared__ __attribute__((aligned(16))) float lds[2 * STG];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wv >> 1, wn = wv & 1;
+    const rsrc_t rp = make_rsrc(p.pk, p.pk_bytes), rx = make_rsrc(p.qk, p.qk_bytes);
+    const int qbs4 = p.qk_bs * 4, klast4 = (p.nslab - 1) * BK * 4;
+    const int g = logical_wg(blockIdx.x, gridDim.x, p.whole);
+    const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, gridDim.x, p.whole);
+    int pos = split_lo(sp, g);
+    const int pos_end = split_lo(sp, g + 1);
+    int slot = 0;
+    while (pos < pos_end) {
+        const int tile = pos / p.nslab, sb = pos - tile * p.nslab;
+        const int se = min(p.nslab, sb + (pos_end - pos));
+        const int m0 = (tile / p.tilesN) * RBM, n0 = (tile % p.tilesN) * C::TNV;
+        const int qbase = (tile % p.tilesN) * C::NQT;
+        int pv[2], woff[NE2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int m = m0 + dma16_row(lane, wv, e);
+            pv[e] = m < p.M ? (m * p.Kp + dma16_kc(lane)) * 4 : FAR;
+        }
+#pragma unroll
+        for (int e = 0; e < NE2; ++e) {     // piece pc: sub-window pc / (SUBP / 4), floats [f, f + 4) of its [channel][WLP] image
+            const int pc = tid + NT * e, sub = pc >= C::SUBP / 4 ? 1 : 0, f = 4 * pc - sub * C::SUBP, ql = f / C::WLP, v0 = f - ql * C::WLP;
+            woff[e] = (f < C::SUB && qbase + ql < p.Q) ? ((qbase + ql) * p.Lq + v0) * 4 : FAR;
+        }
+        int bbase[4];                                  // fragment base of this lane's 4 columns
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) {
+            const int c = wn * 128 + jb * 32 + (lane & 31), qc = c / KW;
+            bbase[jb] = qc * C::WLP + (c - qc * KW) + S * 8 * (lane >> 5);
+        }
+        AccR acc;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc.c[i][j][r] = 0.f;
+
+        // wave-uniform (sample, frame) of the slab being GATHERED (one slab ahead of the one being multiplied).  The prefetch behind
+        // the range's last slab may lie past K: its offsets are clamped into the operands (that stage is never multiplied).
+        int gb, gi;
+        { const int k0 = sb * BK; gb = k0 / p.LP; gi = k0 - gb * p.LP; }
+        int kc_cur, kc_next;                           // first slab element that belongs to the next sample (16 = none)
+#define GRF_ISSUE(STAGE_PTR, K0)                                                                          \
+    {   const int sa = min((K0) * 4, klast4);                                                             \
+        _Pragma("unroll") for (int e = 0; e < 2; ++e) dma16s(rp, (STAGE_PTR) + wv * 256 + e * 1024, pv[e], sa); \
+        const int kc = p.LP - gi;                                                                         \
+        const int sw0 = min(gb, p.B - 1) * qbs4 + S * gi * 4;                                             \
+        const int sw1 = (kc < 16 && gb + 1 < p.B) ? (gb + 1) * qbs4 : sw0;                                \
+        _Pragma("unroll") for (int e = 0; e < NE2; ++e) {                                                 \
+            const int pc0 = e * NT + wv * 64;          /* the wave's first piece */                       \
+            if ((e + 1) * NT <= NP || pc0 < NP)                                                           \
+                dma16s(rx, (STAGE_PTR) + RTILE_A + 4 * pc0, woff[e], pc0 >= C::SUBP / 4 ? sw1 : sw0);     \
+        }                                                                                                 \
+        kc_next = kc < 16 ? kc : 16;                                                                      \
+        gi += BK; if (gi >= p.LP) { gi -= p.LP; ++gb; }                                                   \
+    }
+        PG_STAMP_DECL
+        GRF_ISSUE(lds, sb * BK)
+        kc_cur = kc_next;
+        __syncthreads();
+        for (int sl = sb; sl < se; ++sl) {
+            const int cur = (sl - sb) & 1;
+            PG_STAMP(0)
+#if defined(PG_G_ABL) && PG_G_ABL == 1      /* dev ablation (wrong results): no gathers inside the loop */
+            kc_next = 16;
+#else
+            GRF_ISSUE(lds + (cur ^ 1) * STG, (sl + 1) * BK)
+#endif
+            __builtin_amdgcn_sched_barrier(0);
+            PG_STAMP(1)
+            {   // fragments + MFMA for slab sl
+                const float* As = lds + cur * STG;
+                const float* Bw = As + RTILE_A;
+                const int r = lane & 31, h = lane >> 5, sw = (r >> 2) & 3;
+                const float* ap = As + (wm * 64 + r) * BK;
+                f32x4 a[2][2];
+                float b[4][8];
+                if (kc_cur >= 16) {    // read order = use order (the MFMAs below run kk-major): the first MFMA waits for 6 of 20 reads
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) a[i][0] = *reinterpret_cast<const f32x4*>(ap + i * 32 * BK + (((2 * h) ^ sw) << 2));
+#pragma unroll
+                    for (int ip = 0; ip < 4; ++ip) {
+                        if (ip == 2) {
+#pragma unroll
+                            for (int i = 0; i < 2; ++i) a[i][1] = *reinterpret_cast<const f32x4*>(ap + i * 32 * BK + (((2 * h + 1) ^ sw) << 2));
+                        }
+#pragma unroll
+                        for (int jb = 0; jb < 4; ++jb) { b[jb][2 * ip] = Bw[bbase[jb] + S * 2 * ip]; b[jb][2 * ip + 1] = Bw[bbase[jb] + S * (2 * ip + 1)]; }
+                    }
+                } else {               // elements kl >= kc_cur read the second sub-window, which starts at frame 0 of the next sample
+#pragma unroll
+                    for (int c = 0; c < 2; ++c)
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) a[i][c] = *reinterpret_cast<const f32x4*>(ap + i * 32 * BK + (((2 * h + c) ^ sw) << 2));
+                    // (volatile reads: otherwise hipcc sinks the loads of both paths into one tail with per-element selected addresses)
+                    typedef const volatile __attribute__((address_space(3))) float* lds_vptr;
+                    const lds_vptr Bv = (lds_vptr)Bw;
+                    const int shift = C::SUBP - S * kc_cur;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int d = (8 * h + i >= kc_cur) ? shift : 0;
+#pragma unroll
+                        for (int jb = 0; jb < 4; ++jb) b[jb][i] = Bv[bbase[jb] + S * i + d];
+                    }
+                }
+#pragma unroll
+                for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            acc.c[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][kk >> 2][kk & 3], b[j][kk], acc.c[i][j], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            PG_STAMP(2)
+            kc_cur = kc_next;
+            __syncthreads();
+            PG_STAMP(3)
+        }
+        PG_STAMP_FLUSH
+#undef GRF_ISSUE
+        if (sb == 0 && se == p.nslab) epilogue_g<S, 2, 4>(p, acc, m0, n0, lane, wm, wn, n0 + C::TNV);
+        else store_partial(p.ws, g, slot, acc, tid);
+        pos += se - sb;
+        slot = 1;
+    }
+}
+
+// per-sample slabs on packed operands: every slab is the interior case (no branch in the loop but its back edge)
+template <int KW, int S>
+__device__ __forceinline__ void g_ps_f32(const IgemmParams& p) {
+    using C = GRaw<KW, S>;
+    constexpr int STG = RTILE_A + (C::SUB + 255) / 256 * 256;          // window image rounded up to whole 16-byte wave instructions
+    constexpr int NE16 = (C::SUB / 4 + NT - 1) / NT;
+    static_assert(C::WLP % 4 == 0, "16-byte window pieces");
+    __shared__ __attribute__((aligned(16))) float lds[2 * STG];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wv >> 1, wn = wv & 1;
+    const rsrc_t rp = make_rsrc(p.pk, p.pk_bytes), rx = make_rsrc(p.qk, p.qk_bytes);
+    const int pbs4 = p.M * p.Kp * 4, qbs4 = p.qk_bs * 4;
+    const int cps = p.Kp >> 4;                                         // slabs (chunks of 16 frames) per sample
+    const int g = logical_wg(blockIdx.x, gridDim.x, p.whole);
+    const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, gridDim.x, p.whole);
+    int pos = split_lo(sp, g);
+    const int pos_end = split_lo(sp, g + 1);
+    int slot = 0;
+    while (pos < pos_end) {
+        const int tile = pos / p.nslab, sb = pos - tile * p.nslab;
+        const int se = min(p.nslab, sb + (pos_end - pos));
+        const int m0 = (tile / p.tilesN) * RBM, n0 = (tile % p.tilesN) * C::TNV;
+        const int qbase = (tile % p.tilesN) * C::NQT;
+        int pv[2], woff[NE16];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int m = m0 + dma16_row(lane, wv, e);
+            pv[e] = m < p.M ? (m * p.Kp + dma16_kc(lane)) * 4 : FAR;
+        }
+#pragma unroll
+        for (int e = 0; e < NE16; ++e) {
+            const int f = 4 * (tid + NT * e), ql = f / C::WLP, v0 = f - ql * C::WLP;
+            woff[e] = (f < C::SUB && qbase + ql < p.Q) ? ((qbase + ql) * p.Lq + v0) * 4 : FAR;
+        }
+        int bbase[4];
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) {
+            const int c = wn * 128 + jb * 32 + (lane & 31), qc = c / KW;
+            bbase[jb] = qc * C::WLP + (c - qc * KW) + S * 8 * (lane >> 5);
+        }
+        AccR acc;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc.c[i][j][r] = 0.f;
+
+        int gb = sb / cps, gc = sb - gb * cps;          // (sample, chunk) of the slab being GATHERED; clamped as in g_raw_f32
+#define GPF_ISSUE(STAGE_PTR)                                                                              \
+    {   const int gbc = min(gb, p.B - 1), gi = gc << 4;                                                   \
+        _Pragma("unroll") for (int e = 0; e < 2; ++e) dma16s(rp, (STAGE_PTR) + wv * 256 + e * 1024, pv[e], gbc * pbs4 + gi * 4); \
+        const int sw_ = gbc * qbs4 + S * gi * 4;                                                          \
+        _Pragma("unroll") for (int e = 0; e < NE16; ++e)                                                  \
+            if (4 * (e * NT + wv * 64) < C::SUB) dma16s(rx, (STAGE_PTR) + RTILE_A + 4 * (e * NT + wv * 64), woff[e], sw_); \
+        if (++gc == cps) { gc = 0; ++gb; }                                                                \
+    }
+        GPF_ISSUE(lds)
+        __syncthreads();
+        for (int sl = sb; sl < se; ++sl) {
+            const int cur = (sl - sb) & 1;
+            GPF_ISSUE(lds + (cur ^ 1) * STG)
+            __builtin_amdgcn_sched_barrier(0);
+            {
+                const float* As = lds + cur * STG;
+                const float* Bw = As + RTILE_A;
+                const int r = lane & 31, h = lane >> 5, sw = (r >> 2) & 3;
+                const float* ap = As + (wm * 64 + r) * BK;
+                f32x4 a[2][2];
+                float b[4][8];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) a[i][0] = *reinterpret_cast<const f32x4*>(ap + i * 32 * BK + (((2 * h) ^ sw) << 2));
+#pragma unroll
+                for (int ip = 0; ip < 4; ++ip) {
+                    if (ip == 2) {
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) a[i][1] = *reinterpret_cast<const f32x4*>(ap + i * 32 * BK + (((2 * h + 1) ^ sw) << 2));
+                    }
+#pragma unroll
+                    for (int jb = 0; jb < 4; ++jb) { b[jb][2 * ip] = Bw[bbase[jb] + S * 2 * ip]; b[jb][2 * ip + 1] = Bw[bbase[jb] + S * (2 * ip + 1)]; }
+                }
+#pragma unroll
+                for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            acc.c[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][kk >> 2][kk & 3], b[j][kk], acc.c[i][j], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
+        }
+#undef GPF_ISSUE
+        if (sb == 0 && se == p.nslab) epilogue_g<S, 2, 4>(p, acc, m0, n0, lane, wm, wn, n0 + C::TNV);
+        else store_partial(p.ws, g, slot, acc, tid);
+        pos += se - sb;
+        slot = 1;
+    }
+}
+
+template <int KW, int S, int BF>
+__global__ __launch_bounds__(NT, 2) void conv_g_raw_kernel(const IgemmParams p) {
+    if constexpr (BF == 0) g_raw_f32<KW, S>(p);
+    else g_raw_bf<KW, S, BF>(p);
+}
+template <int KW, int S, int BF>
+__global__ __launch_bounds__(NT, 2) void conv_g_ps_kernel(const IgemmParams p) {
+    if constexpr (BF == 0) g_ps_f32<KW, S>(p);
+    else g_ps_bf<KW, S, BF>(p);
+}
+
+// ---- operand packing (HBM-bound, one pass per operand) ----------------------------------------------------------------------
+// rows r = (b, c) of W floats: index j holds act(src[b][c][j - F]) for j - F in [0, L), else 0 (Q with halos; P per sample)
+__global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict__ src, long bs, int C, int L, int F, int W, unsigned n,
+                                                       float slope, float* __restrict__ dst) {
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const unsigned r = i / (unsigned)W, b = r / (unsigned)C, c = r - b * (unsigned)C;
+        const int t = (int)(i - r * (unsigned)W) - F;
+        float v = 0.f;
+        if ((unsigned)t < (unsigned)L) {
+            v = src[(long)b * bs + (long)c * L + t];
+            if (slope != 1.0f) v = act_apply(v, slope);
+        }
+        dst[i] = v;
+    }
+}
+// flat K: dst[m][k], k = b * LP + i: act(src[b][m][i]) for k < B * LP, zeros up to Kp
+__global__ __launch_bounds__(256) void pack_flat_kernel(const float* __restrict__ src, long bs, int B, int LP, int Kp, unsigned n,
+                                                       float slope, float* __restrict__ dst) {
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const unsigned m = i / (unsigned)Kp, k = i - m * (unsigned)Kp, b = k / (unsigned)LP, t = k - b * (unsigned)LP;
+        float v = 0.f;
+        if ((int)b < B) {
+            v = src[(long)b * bs + (long)m * LP + t];
+            if (slope != 1.0f) v = act_apply(v, slope);
+        }
+        dst[i] = v;
+    }
+}
+unsigned pack_grid(unsigned n) { return (n + 255u) / 256u < 2048u ? (n + 255u) / 256u : 2048u; }
+
+hipError_t pack_g(const IgemmParams& p, hipStream_t st) {
+    float* const qk = const_cast<float*>(p.qk);
+    float* const pk = const_cast<float*>(p.pk);
+    const unsigned nq = (unsigned)(p.qk_bytes / 4), np = (unsigned)(p.pk_bytes / 4);
+    hipLaunchKernelGGL(pack_rows_kernel, dim3(pack_grid(nq)), dim3(256), 0, st, p.x, p.x_bs, p.Q, p.Lx, p.p, p.Lq, nq, act_slope(p.act_x), qk);
+    if (p.g_ps) hipLaunchKernelGGL(pack_rows_kernel, dim3(pack_grid(np)), dim3(256), 0, st, p.pt, p.pt_bs, p.M, p.LP, 0, p.Kp, np, act_slope(p.act_p), pk);
+    else hipLaunchKernelGGL(pack_flat_kernel, dim3(pack_grid(np)), dim3(256), 0, st, p.pt, p.pt_bs, p.B, p.LP, p.Kp, np, act_slope(p.act_p), pk);
+    return hipGetLastError();
+}
+
 template <int KW, int S>
 hipError_t launch_g_raw(const IgemmParams& p, int grid, hipStream_t st, int prec) {
+    if (prec == 0) {
+        if (hipError_t e = pack_g(p, st)) return e;
+    }
     if (p.g_ps) {        // per-sample slabs (host: short samples whose padded K costs <= 7 %)
         if (prec == 1) hipLaunchKernelGGL((conv_g_ps_kernel<KW, S, 1>), dim3(grid), dim3(NT), 0, st, p);
         else if (prec == 2) hipLaunchKernelGGL((conv_g_ps_kernel<KW, S, 2>), dim3(grid), dim3(NT), 0, st, p);

@@ -137,6 +137,7 @@ SYMBOLS = {
     "pg_shadow_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "pg_cast_rows_bf16": (C.c_int, [C.POINTER(CastArgs), C.c_void_p]),
     "pg_workspace_bytes_conv": (C.c_int64, []),
+    "pg_workspace_bytes_wgrad": (C.c_int64, [C.POINTER(ConvArgs), C.c_int32]),
     "pg_bn_fwd": (C.c_int, [C.POINTER(BnArgs), C.c_void_p]),
     "pg_bn_bwd": (C.c_int, [C.POINTER(BnArgs), C.c_void_p]),
     "pg_workspace_bytes_loss": (C.c_int64, [C.POINTER(LossArgs)]),

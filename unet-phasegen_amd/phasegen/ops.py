@@ -159,7 +159,8 @@ def _ws_key(device):
 
 
 def conv_workspace(device):
-    """Scratch for the conv kernels' stream-K schedule (pg_workspace_bytes_conv(), 512 MiB), one per (device, STREAM):
+    """Scratch for the conv kernels' stream-K schedule (pg_workspace_bytes_conv(), 512 MiB; a wgrad grows it by its packed operands,
+    pg_workspace_bytes_wgrad()), one per (device, STREAM):
     launches on one stream are ordered and may share it, launches on different streams may overlap and must not.  At most four
     streams per device hold one at a time (least recently used is dropped); ``release_workspaces()`` drops them all."""
     return _conv_ws.get(device, _lib.load().pg_workspace_bytes_conv)
@@ -341,7 +342,14 @@ def conv_wgrad(x, dy, dw, stride, pad, x_act=ACT_NONE, transposed=False, precisi
             raise ValueError("conv_wgrad: fused adam tensors must have dw's shape")
         a.adam = C.addressof(adam)
     lib = _lib.load()
-    _note_plan(a, _lib.OP_CONVT1D_WGRAD if transposed else _lib.OP_CONV1D_WGRAD)
+    op = _lib.OP_CONVT1D_WGRAD if transposed else _lib.OP_CONV1D_WGRAD
+    # the fp32 kernels pack their operands into the workspace behind the stream-K region: grow this stream's buffer to what the call
+    # needs (the largest layer's size sticks after the first step)
+    need = lib.pg_workspace_bytes_wgrad(C.byref(a), op)
+    if need > a.workspace_bytes:
+        ws = _conv_ws.get(x.device, lib.pg_workspace_bytes_conv, at_least=need)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    _note_plan(a, op)
     fn = lib.pg_convt1d_wgrad if transposed else lib.pg_conv1d_wgrad
     _lib.check(fn(C.byref(a), _stream()), "wgrad")
     return dw
