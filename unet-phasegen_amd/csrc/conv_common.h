@@ -31,7 +31,7 @@ struct IgemmParams {
     int nslab;                       // K slabs per tile
     int whole;                       // workgroups that own one whole tile each (hybrid split; 0 = even split)
     int sr;                          // tile order (conv_raw3): 0 / 1 = row-major; R > 1: column-major inside super-rows of R tile rows, so
-    int n_lo;                        // first column of this launch (0 but for the tail launch of a column split, conv_igemm.hip launch())
+    int n_lo;                        // first column of this launch (0 but for the tail launch of a column split, conv_igemm.hip split_columns())
                                      // that the 32 workgroups an XCD runs at a time cover R x 32/R tiles and share activation panels too
     // bf16-resident forward kernels (conv_h3.hip): x and w are bf16; rows of x are x_pitch elements apart (even, zero tail);
     // optional bf16 outputs (B, M, yh_pitch) stored already activated.  All NULL / 0 for the fp32-tensor kernels.
@@ -531,6 +531,9 @@ constexpr int RTILE_A = RBM * BK;         // weight tile, same swizzled image as
 // raw-window wgrad (conv_raw_wgrad.hip): floats of Q's row one channel's window slot holds per slab (window 15 s + k, padded so
 // that the fragment reads stay conflict-free); the host sizes the packed rows by it
 constexpr int g_wlp(int kw, int s) { return kw == 32 ? 64 : (kw == 8 ? (s == 1 ? 24 : 40) : 36); }
+
+// the five (k, stride) pairs of the U-Net's layers (model.py): the geometries the raw-window, conv_raw3 and bf16-resident kernels serve
+inline bool unet_ks(int k, int s) { return (k == 32 && s == 2) || (k == 8 && s == 1) || (k == 8 && s == 2) || (k == 4 && s == 2) || (k == 5 && s == 2); }
 
 enum Kind { KIND_F, KIND_T, KIND_G };
 

@@ -406,9 +406,8 @@ hipError_t launch3(const IgemmParams& p, int grid, hipStream_t st) {
 bool pgconv::h_supported(int kind, const IgemmParams& p) {
     constexpr int tn = 256;
     const bool t = kind == KIND_T;
-    if (kind == KIND_G) return false;
-    if (t) { if (!((p.k == 32 && p.s == 2) || (p.k == 8 && p.s == 1) || (p.k == 8 && p.s == 2) || (p.k == 5 && p.s == 2))) return false; }
-    else if (!((p.k == 32 && p.s == 2) || (p.k == 8 && p.s == 1) || (p.k == 8 && p.s == 2) || (p.k == 4 && p.s == 2))) return false;
+    // the U-Net's pairs less the form no layer runs: k = 4 is only a forward conv (D3), k = 5 only a transposed one (U3)
+    if (kind == KIND_G || !unet_ks(p.k, p.s) || p.k == (t ? 4 : 5)) return false;
     const int kwp = t ? pg_shadow_taps(p.k, p.s) : p.k, tj = kwp < 32 ? kwp : 32, nq = 32 / tj, sc = t ? 1 : p.s;
     if (p.Q % nq || (p.x_pitch & 1) || (p.x_bs & 1) || p.x_pitch <= p.Lx) return false;
     const int lcol = t ? p.U : p.Ly, rsd = h3_rsd(sc);

@@ -436,13 +436,8 @@ hipError_t launch3(const IgemmParams& p, int grid, hipStream_t st) {
 }  // namespace
 
 bool pgconv::raw3_covers(int kind, const IgemmParams& p) {
-    const bool k5 = p.k == 5 && p.s == 2;
-    if (kind == KIND_F) {
-        if (!((p.k == 32 && p.s == 2) || (p.k == 8 && p.s == 1) || (p.k == 8 && p.s == 2) || (p.k == 4 && p.s == 2) || k5)) return false;
-    } else if (kind == KIND_T) {
-        if (!((p.k == 32 && p.s == 2) || (p.k == 8 && p.s == 1) || (p.k == 8 && p.s == 2) || (p.k == 4 && p.s == 2) || k5)) return false;
-    } else return false;
-    const int kv = k5 ? 8 : p.k, kwp = kind == KIND_T ? kv / p.s : kv, tj = kwp < 16 ? kwp : 16;
+    if (kind == KIND_G || !unet_ks(p.k, p.s)) return false;
+    const int kv = p.k == 5 ? 8 : p.k, kwp = kind == KIND_T ? kv / p.s : kv, tj = kwp < 16 ? kwp : 16;
     return ((long)p.Q * kwp) % BK == 0 && p.Q % (16 / tj > 0 ? 16 / tj : 1) == 0;     // whole slabs of whole channels only
 }
 
