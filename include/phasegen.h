@@ -174,6 +174,33 @@ typedef struct pg_bn_args {
 int pg_bn_fwd(const pg_bn_args* a, void* stream);
 int pg_bn_bwd(const pg_bn_args* a, void* stream);
 
+/* BatchNorm forward with PER-CLIP statistics: the reference runs inference one clip at a time and never calls .eval()
+ * (demo.py:33-45, train.py:76-83), so each clip is normalised by its own statistics.  This entry point does that for B clips in
+ * one launch: every row (b, c) of L frames is normalised by ITS mean and biased variance (two-pass, eps inside the sqrt), i.e.
+ * what B calls of pg_bn_fwd with a batch of one compute.  A row's result does not depend on B or on its position in the batch
+ * (bit for bit).  Tensor conventions and the output fields (y / y2 fp32 with their activations, yh / yh2 bf16 (B, C, pitch) with
+ * theirs, row tails untouched; at least one of y, yh) are those of pg_bn_args.  save_mean / save_invstd are optional and (B, C).
+ * running_mean / running_var (C, each optional) end up as after B batch-of-one calls in the order b = 0 .. B-1:
+ * rm = (1 - m) rm + m mean_b, rv = (1 - m) rv + m var_b L / max(L - 1, 1), one step per clip; *num_batches_tracked += B.
+ * They need `workspace`: pg_workspace_bytes_clipnorm() bytes (2 B C floats: the per-row means and variances between the two
+ * launches), else PG_ERR_WORKSPACE; without running buffers the workspace is not touched.  No backward exists: inference only. */
+typedef struct pg_clipnorm_args {
+    int32_t B, C, L; float eps, momentum; int32_t _pad0;
+    const float* x;  int64_t x_bs;       /* raw conv output                                                    */
+    float* y;        int64_t y_bs;       /* normalised + affine output, stored as PG_ACT(y_act); may be NULL if yh is given */
+    float* y2;       int64_t y2_bs;      /* optional second fp32 copy with its own activation                   */
+    int32_t y_act; int32_t y2_act;
+    uint16_t* yh;  int64_t yh_bs;  int32_t yh_pitch;  int32_t yh_act;      /* optional bf16 outputs, as in pg_bn_args */
+    uint16_t* yh2; int64_t yh2_bs; int32_t yh2_pitch; int32_t yh2_act;
+    const float* gamma; const float* beta;    /* (C)                                                            */
+    float* save_mean; float* save_invstd;     /* optional (NULL): (B, C), the statistics of every row           */
+    float* running_mean; float* running_var;  /* optional (NULL): (C), updated in place, one step per clip      */
+    int64_t* num_batches_tracked;             /* optional (NULL): incremented by B on the device                */
+    void* workspace; int64_t workspace_bytes; /* required with running_mean / running_var                       */
+} pg_clipnorm_args;
+int64_t pg_workspace_bytes_clipnorm(const pg_clipnorm_args* a);   /* host function of B and C; negative = error code */
+int pg_clipnorm_fwd(const pg_clipnorm_args* a, void* stream);
+
 /* train.py:45-60: loss = MSE(cos p, cos th) + MSE(sin p, sin th) + mag_weight * MSE(m, logmag), fused with its
  * gradient wrt pred.  pred (B,2C,L) = [phase ; magnitude]; batch (B,2,C,L) = [logmag ; angle].
  * losses[0..2] = {loss, ang, mag}.  Deterministic two-stage reduction through `workspace`. */

@@ -56,6 +56,20 @@ class BnArgs(C.Structure):
                 ("num_batches_tracked", C.c_void_p)]
 
 
+class ClipNormArgs(C.Structure):
+    """pg_clipnorm_args: BatchNorm forward with per-clip statistics (include/phasegen.h)."""
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("L", C.c_int32), ("eps", C.c_float), ("momentum", C.c_float), ("_pad0", C.c_int32),
+                ("x", C.c_void_p), ("x_bs", C.c_int64), ("y", C.c_void_p), ("y_bs", C.c_int64), ("y2", C.c_void_p), ("y2_bs", C.c_int64),
+                ("y_act", C.c_int32), ("y2_act", C.c_int32),
+                ("yh", C.c_void_p), ("yh_bs", C.c_int64), ("yh_pitch", C.c_int32), ("yh_act", C.c_int32),
+                ("yh2", C.c_void_p), ("yh2_bs", C.c_int64), ("yh2_pitch", C.c_int32), ("yh2_act", C.c_int32),
+                ("gamma", C.c_void_p), ("beta", C.c_void_p),
+                ("save_mean", C.c_void_p), ("save_invstd", C.c_void_p),
+                ("running_mean", C.c_void_p), ("running_var", C.c_void_p),
+                ("num_batches_tracked", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class ConvhArgs(C.Structure):
     """pg_convh_args: bf16-resident forward conv / transposed conv (include/phasegen.h)."""
     _fields_ = [("B", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("Lin", C.c_int32), ("Lout", C.c_int32),
@@ -140,6 +154,8 @@ SYMBOLS = {
     "pg_workspace_bytes_wgrad": (C.c_int64, [C.POINTER(ConvArgs), C.c_int32]),
     "pg_bn_fwd": (C.c_int, [C.POINTER(BnArgs), C.c_void_p]),
     "pg_bn_bwd": (C.c_int, [C.POINTER(BnArgs), C.c_void_p]),
+    "pg_workspace_bytes_clipnorm": (C.c_int64, [C.POINTER(ClipNormArgs)]),
+    "pg_clipnorm_fwd": (C.c_int, [C.POINTER(ClipNormArgs), C.c_void_p]),
     "pg_workspace_bytes_loss": (C.c_int64, [C.POINTER(LossArgs)]),
     "pg_loss_fwd_bwd": (C.c_int, [C.POINTER(LossArgs), C.c_void_p]),
     "pg_adam_step": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p]),

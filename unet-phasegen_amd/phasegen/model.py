@@ -110,9 +110,16 @@ class UNetModel(nn.Module):
         self.model = _StateHolder(self.engine.arena)
 
     # nn.parallel.data_parallel (model.py:40-41) is replaced by one process per GPU + RCCL (phasegen.trainer)
-    def forward(self, input):
+    def forward(self, input, per_clip=False):
+        """``per_clip=True`` (under ``torch.no_grad()`` only): every clip of the batch is normalised by its own BatchNorm statistics,
+        i.e. the batch comes out as a loop of batch-of-one forwards would give it (the reference's inference, demo.py:33-45)."""
         if torch.is_tensor(input) and input.is_cuda and input.device != self.engine.device:
             input = input.to(self.engine.device)      # the reference moves its input to the model's GPU (.cuda(gpu_id))
+        if per_clip:
+            if torch.is_grad_enabled():
+                raise RuntimeError("phasegen UNetModel: per_clip=True is inference only (per-clip BatchNorm statistics have no "
+                                   "backward) -- call it under torch.no_grad()")
+            return self.engine.forward(input, inference=True, stats="clip").clone()
         if torch.is_grad_enabled():
             params = [self.model.param(k) for k in detgen.param_order()]
             return _UNetFn.apply(self.engine, input, *params)

@@ -504,6 +504,58 @@ def bn_fwd(x, y, gamma, beta, save_mean, save_invstd, running_mean=None, running
     return y
 
 
+def clipnorm_fwd(x, y, gamma, beta, save_mean=None, save_invstd=None, running_mean=None, running_var=None, eps=1e-5, momentum=0.1,
+                 y_act=ACT_NONE, y2=None, y2_act=ACT_NONE, yh=None, yh_act=ACT_NONE, yh2=None, yh2_act=ACT_NONE, num_batches_tracked=None,
+                 workspace=None):
+    """BatchNorm forward with PER-CLIP statistics (pg_clipnorm_fwd): every row (b, c) of x (B, C, L) is normalised by its own mean
+    and biased variance -- what B batch-of-one ``bn_fwd`` calls compute (the reference's inference, demo.py:33-45), in one launch.
+    Outputs as in ``bn_fwd``; ``save_mean`` / ``save_invstd`` are optional and (B, C).  The running buffers (C) take one momentum
+    step per clip in clip order, ``num_batches_tracked`` grows by B.  ``workspace``: float32 scratch of at least 2 * B * C elements
+    for the running-buffer chain (allocated here when missing; pass a persistent one to capture the call in a graph)."""
+    a = _lib.ClipNormArgs()
+    a.B, a.C, a.L = B, Cc, L = x.shape
+    a.eps, a.momentum = eps, momentum
+    a.y_act, a.y2_act = y_act, y2_act
+    a.x, a.x_bs = _act3(x, "x")
+    for name, t in (("y", y), ("y2", y2)):
+        if t is not None and tuple(t.shape) != (B, Cc, L):
+            raise ValueError(f"clipnorm_fwd: {name}{tuple(t.shape)} should be {(B, Cc, L)}")
+    for name, t in (("yh", yh), ("yh2", yh2)):
+        if t is not None and tuple(t.shape[:2]) != (B, Cc):
+            raise ValueError(f"clipnorm_fwd: {name}{tuple(t.shape)} should be ({B}, {Cc}, pitch)")
+    if y is not None:
+        a.y, a.y_bs = _act3(y, "y")
+    if y2 is not None:
+        a.y2, a.y2_bs = _act3(y2, "y2")
+    if yh is not None:
+        a.yh, a.yh_bs, a.yh_pitch = _h3(yh, L, "yh")
+        a.yh_act = yh_act
+    if yh2 is not None:
+        a.yh2, a.yh2_bs, a.yh2_pitch = _h3(yh2, L, "yh2")
+        a.yh2_act = yh2_act
+    for name, t, n in (("gamma", gamma, Cc), ("beta", beta, Cc), ("save_mean", save_mean, B * Cc), ("save_invstd", save_invstd, B * Cc),
+                       ("running_mean", running_mean, Cc), ("running_var", running_var, Cc)):
+        if t is not None and t.numel() != n:
+            raise ValueError(f"clipnorm_fwd: {name} has {t.numel()} elements, expected {n}")
+    a.gamma, a.beta = _dense(gamma, "gamma"), _dense(beta, "beta")
+    if save_mean is not None:
+        a.save_mean = _dense(save_mean, "save_mean")
+    if save_invstd is not None:
+        a.save_invstd = _dense(save_invstd, "save_invstd")
+    if running_mean is not None:
+        a.running_mean = _dense(running_mean, "running_mean")
+    if running_var is not None:
+        a.running_var = _dense(running_var, "running_var")
+    if num_batches_tracked is not None:
+        a.num_batches_tracked = _dense_as(num_batches_tracked, torch.int64, "num_batches_tracked")
+    if running_mean is not None or running_var is not None:
+        if workspace is None:
+            workspace = torch.empty(2 * B * Cc, device=x.device, dtype=torch.float32)
+        a.workspace, a.workspace_bytes = _dense(workspace, "workspace"), 4 * workspace.numel()
+    _lib.check(_lib.load().pg_clipnorm_fwd(C.byref(a), _stream()), "clipnorm_fwd")
+    return y
+
+
 def bn_bwd(x, dy, dx, gamma, save_mean, save_invstd, dgamma, dbeta):
     a = _lib.BnArgs()
     a.B, a.C, a.L = x.shape

@@ -199,13 +199,24 @@ class UNetEngine:
             ops.conv_fwd(x, self.arena.p(key), y, s, p, transposed=(kind == "t"), y_act=y_act, y2=y2, y2_act=y2_act,
                          precision=self.precision)
 
-    def _bn(self, name, x, y, update_stats, y_act=ACT_NONE, y2=None, y2_act=ACT_NONE):
+    def _clip_ws(self, plan, B):
+        """Scratch of the per-clip BatchNorm's running-buffer chain (2 x B x 2C floats), a plan buffer: graph captures point at it."""
+        if "clip_ws" not in plan:
+            plan["clip_ws"] = torch.empty(2 * B * 2 * self.C, device=self.device, dtype=torch.float32)
+        return plan["clip_ws"]
+
+    def _bn(self, name, x, y, update_stats, y_act=ACT_NONE, y2=None, y2_act=ACT_NONE, clip_ws=None):
         key = BN_OF[name]
         a = self.arena
         sm, si = self.bn_save[name]
         rm = a.buffers[key + ".running_mean"] if update_stats else None
         rv = a.buffers[key + ".running_var"] if update_stats else None
         nb = a.buffers[key + ".num_batches_tracked"] if update_stats else None
+        if clip_ws is not None:                  # per-clip statistics (inference): nothing is saved for a backward
+            with ops.timed("hbm:clipnorm." + name, 4 * x.numel() * (2 + (y2 is not None))):
+                ops.clipnorm_fwd(x, y, a.p(key + ".weight"), a.p(key + ".bias"), None, None, rm, rv, y_act=y_act, y2=y2, y2_act=y2_act,
+                                 num_batches_tracked=nb, workspace=clip_ws)
+            return
         with ops.timed("hbm:bn_fwd." + name, 4 * x.numel() * (2 + (y2 is not None))):        # one read, one or two fp32 writes
             ops.bn_fwd(x, y, a.p(key + ".weight"), a.p(key + ".bias"), sm, si, rm, rv, y_act=y_act, y2=y2, y2_act=y2_act,
                        num_batches_tracked=nb)
@@ -263,32 +274,33 @@ class UNetEngine:
             self.plans[key] = dict(fwd=f, L=(L, L1, L2, L3, L4))
         return self.plans[key]
 
-    def _forward_resident(self, x, update_stats):
+    def _forward_resident(self, x, update_stats, clip=False):
         """Forward with bf16-resident operands: every activation a conv reads lives in HBM as bf16 (written activated by the
         producing conv epilogue / BatchNorm), weights come from bf16 shadows, BatchNorm statistics and outputs stay fp32.
         No tensors are kept for backward: inference only.  With ``self.graphs`` the launch sequence behind the input cast (8 convs
-        with their fixups + 6 BatchNorms) is captured once per (batch, frames, update_stats) into a HIP graph and replayed: every
-        buffer it touches is a plan buffer, the weight shadows included (rebuilt IN PLACE when the parameters change)."""
+        with their fixups + 6 BatchNorms) is captured once per (batch, frames, update_stats, statistics mode) into a HIP graph and
+        replayed: every buffer it touches is a plan buffer, the weight shadows included (rebuilt IN PLACE when the parameters change).
+        ``clip``: the six BatchNorms normalise every clip by its own statistics (ops.clipnorm_fwd), same output wiring."""
         B, C, L = x.shape
         plan = self._plan_h(B, L)
         f = plan["fwd"]
         sh = self._shadows()
         ops.cast_rows_bf16(x, f["x0"])
         if not self.graphs or ops._timer is not None:
-            self._resident_body(plan, sh, update_stats)
+            self._resident_body(plan, sh, update_stats, clip)
         else:
-            # everything a capture freezes is part of the key: shape, the BatchNorm-buffer update, the thread's schedule word and the
-            # engine's precision (ops reads both at launch time; a replay would silently keep the captured ones)
-            key = ("graph", B, L, bool(update_stats), ops.current_schedule(), self.precision)
+            # everything a capture freezes is part of the key: shape, the BatchNorm-buffer update, the thread's schedule word, the
+            # engine's precision (ops reads both at launch time; a replay would silently keep the captured ones) and the statistics mode
+            key = ("graph", B, L, bool(update_stats), ops.current_schedule(), self.precision) + (("clip",) if clip else ())
             g = self.plans.get(key)
             if g is None:                        # first forward at this shape: eager (first-launch costs stay out of the capture)
-                self._resident_body(plan, sh, update_stats)
+                self._resident_body(plan, sh, update_stats, clip)
                 self.plans[key] = "warm"
             else:
                 if g == "warm":                  # second: capture -- nothing executes while capturing -- then replay as this call's forward
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
-                        self._resident_body(plan, sh, update_stats)
+                        self._resident_body(plan, sh, update_stats, clip)
                         # ops' scratch caches are keyed by (device, CURRENT stream) and torch captures on a side stream of its own:
                         # the stream-K workspace the captured launches point at was allocated just now, for the capture stream.  It
                         # is held HERE, next to the graph, so that neither the caches' LRU eviction nor ops.release_workspaces()
@@ -300,12 +312,13 @@ class UNetEngine:
         self.cur = None                      # nothing kept for backward
         return f["out"]
 
-    def _resident_body(self, plan, sh, update_stats):
+    def _resident_body(self, plan, sh, update_stats, clip=False):
         f = plan["fwd"]
         L, L1, L2, L3, L4 = plan["L"]
         C = self.C
         h = 2 * C
         a = self.arena
+        clip_ws = self._clip_ws(plan, f["out"].shape[0]) if clip else None
 
         def conv(name, xh, Lin, **out):
             key, kind, s, p = LAYERS[name]
@@ -318,6 +331,10 @@ class UNetEngine:
             rm = a.buffers[key + ".running_mean"] if update_stats else None
             rv = a.buffers[key + ".running_var"] if update_stats else None
             nb = a.buffers[key + ".num_batches_tracked"] if update_stats else None
+            if clip:
+                ops.clipnorm_fwd(raw, out.pop("y", None), a.p(key + ".weight"), a.p(key + ".bias"), None, None, rm, rv,
+                                 num_batches_tracked=nb, workspace=clip_ws, **out)
+                return
             ops.bn_fwd(raw, out.pop("y", None), a.p(key + ".weight"), a.p(key + ".bias"), sm, si, rm, rv, num_batches_tracked=nb, **out)
 
         conv("D0", f["x0"], L, yh=f["l0"], yh_act=ACT_LEAKY, yh2=f["cat0"][:, :h], yh2_act=ACT_RELU)
@@ -336,10 +353,18 @@ class UNetEngine:
         bn("U0", f["r0"], y=f["out"])
 
     # -- forward -----------------------------------------------------------------------------------------------
-    def forward(self, x, update_stats=True, inference=False):
+    def forward(self, x, update_stats=True, inference=False, stats="batch"):
         """x: (B, C, L) fp32 device tensor -> (B, 2C, L).  BatchNorm is ALWAYS in training mode, as in the
         reference (no .eval() anywhere; demo.py:36 runs batch-of-1 statistics).  ``inference=True`` promises that no
-        backward follows: with precision bf16 the forward then runs on the bf16-resident kernels (csrc/conv_h3.hip)."""
+        backward follows: with precision bf16 the forward then runs on the bf16-resident kernels (csrc/conv_h3.hip).
+        ``stats="clip"`` (inference only: no backward exists for it): every BatchNorm normalises each clip by its OWN statistics,
+        so the B clips come out -- to rounding -- as B batch-of-one forwards give them, the running buffers included (one momentum
+        step per clip, in clip order).  ``stats="batch"`` is the reference's training semantics: statistics over the whole batch."""
+        if stats not in ("batch", "clip"):
+            raise ValueError(f"UNet: stats must be 'batch' or 'clip', got {stats!r}")
+        clip = stats == "clip"
+        if clip and not inference:
+            raise ValueError("UNet: stats='clip' needs inference=True (per-clip statistics have no backward)")
         if x.dim() != 3 or x.shape[1] != self.C:
             raise ValueError(f"UNet: expected input (B, {self.C}, L), got {tuple(x.shape)}")
         if not x.is_cuda or x.dtype != torch.float32:
@@ -350,30 +375,31 @@ class UNetEngine:
             x = x.contiguous()                   # any other layout than (batch-strided) rows of contiguous frames: one copy
         with torch.cuda.device(self.device):     # kernels launch on the CURRENT device's stream: make that the engine's
             if inference and self.resident_ok(x.shape[0], x.shape[2]):
-                return self._forward_resident(x, update_stats)
-            return self._forward(x, update_stats)
+                return self._forward_resident(x, update_stats, clip)
+            return self._forward(x, update_stats, clip)
 
-    def _forward(self, x, update_stats):
+    def _forward(self, x, update_stats, clip=False):
         B, C, L = x.shape           # batch-strided views (e.g. batch[:, 0] of a (B,2,C,L) batch) are read in place
         plan = self.plan(B, L)
         f = plan["fwd"]
         h = 2 * C
+        ws = self._clip_ws(plan, B) if clip else None      # per-clip statistics: every BatchNorm below goes to ops.clipnorm_fwd
         self._conv("D0", x, f["l0"], ACT_LEAKY, f["cat0"][:, :h], ACT_RELU)         # a0 -> leaky(a0), relu(a0)
         self._conv("D1", f["l0"], f["c1"])
-        self._bn("D1", f["c1"], f["l1"], update_stats, ACT_LEAKY, f["cat1"][:, :h], ACT_RELU)   # h1
+        self._bn("D1", f["c1"], f["l1"], update_stats, ACT_LEAKY, f["cat1"][:, :h], ACT_RELU, clip_ws=ws)   # h1
         self._conv("D2", f["l1"], f["c2"])
-        self._bn("D2", f["c2"], f["l2"], update_stats, ACT_LEAKY, f["cat2"][:, :h], ACT_RELU)   # h2
+        self._bn("D2", f["c2"], f["l2"], update_stats, ACT_LEAKY, f["cat2"][:, :h], ACT_RELU, clip_ws=ws)   # h2
         self._conv("D3", f["l2"], f["d3"], ACT_RELU)                                  # relu(d3)
         self._conv("U3", f["d3"], f["r3"])
-        self._bn("U3", f["r3"], f["cat2"][:, h:], update_stats, ACT_RELU)             # relu(u3)
+        self._bn("U3", f["r3"], f["cat2"][:, h:], update_stats, ACT_RELU, clip_ws=ws)             # relu(u3)
         self._conv("U2", f["cat2"], f["r2"])
-        self._bn("U2", f["r2"], f["cat1"][:, h:], update_stats, ACT_RELU)
+        self._bn("U2", f["r2"], f["cat1"][:, h:], update_stats, ACT_RELU, clip_ws=ws)
         self._conv("U1", f["cat1"], f["r1"])
-        self._bn("U1", f["r1"], f["cat0"][:, h:], update_stats, ACT_RELU)
+        self._bn("U1", f["r1"], f["cat0"][:, h:], update_stats, ACT_RELU, clip_ws=ws)
         self._conv("U0", f["cat0"], f["r0"])
-        self._bn("U0", f["r0"], f["out"], update_stats)
+        self._bn("U0", f["r0"], f["out"], update_stats, clip_ws=ws)
         self.fwd_count += 1
-        self.cur = (plan, x)
+        self.cur = None if clip else (plan, x)     # a per-clip forward keeps nothing a backward could use
         return f["out"]
 
     # -- backward ----------------------------------------------------------------------------------------------

@@ -12,7 +12,8 @@ from . import audio
 
 
 @torch.no_grad()
-def validation_metrics(model, val_batch, hop_length=512, n_fft=2048, gl_iters=250, gl_seed=0, group=None, shard=False):
+def validation_metrics(model, val_batch, hop_length=512, n_fft=2048, gl_iters=250, gl_seed=0, group=None, shard=False,
+                       batched=False, clip_batch=64):
     """val_batch: (n, 2, bins, frames) = [logmag; angle] on the device.  Returns {"MSE", "NOPMSE", "LMSE"} floats.
     Nothing leaves the device before the three means: the forwards are batch-of-one (train-mode BatchNorm, train.py:76: the
     statistics of a clip must not see the others), everything else -- the three ISTFTs and the Griffin-Lim comparator -- is
@@ -26,6 +27,9 @@ def validation_metrics(model, val_batch, hop_length=512, n_fft=2048, gl_iters=25
     after the sharded forwards rank 0's buffers are broadcast, which keeps the replicas identical (what Trainer's construction-time
     check asserts once).  The values then depend on W -- rank 0 saw clips 0, W, 2W, ... -- and on nothing else; the model never reads
     them (no .eval() anywhere), they only travel in checkpoints.
+    ``batched=True``: the batch-of-one loop is replaced by forwards with PER-CLIP BatchNorm statistics over chunks of ``clip_batch``
+    clips (``model.forward(..., per_clip=True)``): the same values to rounding, running buffers included, without re-reading the
+    weights for every clip.
     A non-finite Griffin-Lim or ISTFT result raises, as librosa.util.valid_audio does in the reference (utils.py:41,130)."""
     import torch.distributed as dist
     val_batch = val_batch.contiguous()
@@ -38,8 +42,14 @@ def validation_metrics(model, val_batch, hop_length=512, n_fft=2048, gl_iters=25
         vb = val_batch[mine]
         logmag, ang = vb[:, 0].contiguous(), vb[:, 1].contiguous()
         phase = torch.empty_like(logmag)
-        for i in range(len(mine)):
-            phase[i] = model.forward(vb[i:i + 1, 0])[0, :bins]                   # batch of one, train-mode BN (train.py:76)
+        if batched:
+            if clip_batch < 1:
+                raise ValueError("validation_metrics: clip_batch must be at least 1")
+            for i in range(0, len(mine), clip_batch):
+                phase[i:i + clip_batch] = model.forward(vb[i:i + clip_batch, 0], per_clip=True)[:, :bins]   # each clip its own statistics
+        else:
+            for i in range(len(mine)):
+                phase[i] = model.forward(vb[i:i + 1, 0])[0, :bins]               # batch of one, train-mode BN (train.py:76)
         orig = audio.synthesize(logmag, ang, hop_length)
         hyb = audio.synthesize(logmag, phase, hop_length)
         nop = audio.synthesize(logmag, torch.zeros_like(logmag), hop_length)
