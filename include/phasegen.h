@@ -3,7 +3,7 @@
  * The reference (LemonATsu/UNet-PhaseGen) is pure Python and has no FFI of its own; what it binds on
  * this path is torch.nn.Conv1d / ConvTranspose1d / BatchNorm / (Leaky)ReLU / cat (model.py:77-113),
  * MSELoss + Adam (train.py:26-28,45-62), np.abs/np.angle (data.py:39-47) and librosa.stft / istft
- * (preproc_mdb.py:93, utils.py:40).  Each entry point below replaces one of those and cites it.
+ * (preproc_mdb.py:93, utils.py:40) and librosa.resample (preproc_mdb.py:114).  Each entry point below replaces one of those and cites it.
  *
  * Conventions
  *   - plain C: raw DEVICE pointers, sizes, scalars; no torch types.  All tensors fp32.
@@ -281,6 +281,41 @@ typedef struct pg_moments_args { int64_t n; const float* x; double* stats; void*
 int64_t pg_workspace_bytes_moments(void);
 int pg_moments(const pg_moments_args* a, void* stream);
 int pg_standardize(float* x, int64_t n, const double* stats, void* stream);
+
+/* Sample-rate conversion by up / down (target rate / original rate): the rate change of preproc_mdb.py:105-116 (librosa.load at
+ * 44.1 kHz, librosa.resample to 16 kHz).  A band-limited sinc interpolator under a Kaiser window, resampy's published parameters:
+ *   quality                Z (zero crossings)   beta                  roll-off r
+ *   PG_RS_KAISER_BEST      64                   14.769656459379492    0.9475937167399596
+ *   PG_RS_KAISER_FAST      16                   8.555504641634386     0.85
+ *   h(t) = r sinc(r t) I0(beta sqrt(1 - (t/Z)^2)) / I0(beta) for |t| <= Z, else 0          (sinc(x) = sin(pi x) / (pi x))
+ * up / down are reduced by their gcd to U / D; s = min(1, U/D), W = Z / s, H = floor(W), taps = floor(W) + ceil(W) + 1
+ * (160 / 441, best: H = 176, taps = 354).  Output t has n0 = (t D) div U, p = (t D) mod U and
+ *   y[t] = sum_{k < taps} bank[k U + p] x[n0 - H + k]        x[n] = 0 outside [0, n_in); k ascending, one fmaf per tap
+ *   bank[k U + p] = float32(s h(s (p/U + H - k)))            tap-major, phase-minor; evaluated in double
+ *   n_out = ceil(n_in U / D)
+ * Parity with resampy is UNPINNED (as the STFT's with librosa): resampy interpolates linearly in a 512-per-crossing table and
+ * truncates its index step; this is the filter that table samples.  Two known deviations: the last sample t = n_out - 1 is
+ * computed (old librosa zero-pads it when resampy returns floor), and equal rates are filtered like any other ratio (callers
+ * that want librosa's pass-through skip the call).
+ * The filter bank is built by the caller ON THE HOST (pg_resample_bank writes pg_resample_bank_elems() floats to a host buffer)
+ * and handed to pg_resample as a DEVICE copy: the library allocates nothing and keeps nothing.  Limits after reduction: U <= 1024
+ * and taps <= 2048, else PG_ERR_UNSUPPORTED (of the pairs of 8 / 11.025 / 16 / 22.05 / 32 / 44.1 / 48 kHz only 11.025 -> 32 kHz,
+ * 1280 phases, is outside; go through 22.05 kHz).  The argument of h is formed as (p + U (H - k)) /
+ * max(U, D), one division of exact integers, so |t| <= Z is decided exactly at the edge of the support.  A row's
+ * result does not depend on n_signals or its position in the batch (bit for bit); nothing outside [0, n_in) of a row is used. */
+enum { PG_RS_KAISER_BEST = 0, PG_RS_KAISER_FAST = 1 };
+int64_t pg_resample_out_len(int64_t n_in, int32_t up, int32_t down);            /* host; <0 = error code            */
+int32_t pg_resample_taps(int32_t up, int32_t down, int32_t quality);             /* host; <0 = error code            */
+int64_t pg_resample_bank_elems(int32_t up, int32_t down, int32_t quality);       /* host: taps * U; <0 = error code  */
+int pg_resample_bank(float* bank_host, int32_t up, int32_t down, int32_t quality);   /* HOST buffer, double arithmetic */
+typedef struct pg_resample_args {
+    int32_t n_signals, up, down, quality;
+    int64_t n_in, n_out;                 /* n_out == pg_resample_out_len(...) else PG_ERR_SHAPE */
+    const float* x; int64_t x_stride;    /* (n_signals, n_in), rows x_stride >= n_in apart      */
+    float* y;       int64_t y_stride;    /* (n_signals, n_out), rows y_stride >= n_out apart    */
+    const float* bank;                   /* DEVICE copy of pg_resample_bank's output            */
+} pg_resample_args;
+int pg_resample(const pg_resample_args* a, void* stream);
 
 /* small helpers the training step needs on device */
 int pg_fill(float* p, int64_t n, float value, void* stream);

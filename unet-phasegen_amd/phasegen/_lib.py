@@ -21,6 +21,7 @@ SCHED_NO_RAW3 = 0x2000  # fp32 F / T: never the one-wave-per-SIMD kernels (conv_
 SCHED_ALL_RAW3 = 0x4000  # ... those kernels wherever they cover the problem (also the F form of k = 32, which auto leaves on the older ones)
 SCHED_NO_COLSPLIT = 0x20000  # fp32 F / T on conv_raw3: keep the columns past the last full 256-wide tile in the same launch (no tail launch)
 SCHED_COLSPLIT = 0x40000     # ... or always hand them to the tail launch where the geometry allows (tests; the automatic choice prices the tail)
+RS_KAISER_BEST, RS_KAISER_FAST = 0, 1      # pg_resample_args.quality (PG_RS_*)
 # (pg_convh_args.schedule bits 5-6 selected tile families that ABI 0.4 removed; bit 12, the surviving conv_h3 family, is a no-op)
 
 c_float_p = C.c_void_p  # device pointers travel as integers
@@ -133,6 +134,14 @@ class OlaArgs(C.Structure):
                 ("n", C.c_int32), ("_pad0", C.c_int32)]
 
 
+class ResampleArgs(C.Structure):
+    """pg_resample_args: sample-rate conversion by up / down (include/phasegen.h)."""
+    _fields_ = [("n_signals", C.c_int32), ("up", C.c_int32), ("down", C.c_int32), ("quality", C.c_int32),
+                ("n_in", C.c_int64), ("n_out", C.c_int64),
+                ("x", C.c_void_p), ("x_stride", C.c_int64), ("y", C.c_void_p), ("y_stride", C.c_int64),
+                ("bank", C.c_void_p)]
+
+
 # every symbol include/phasegen.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pg_conv1d_fwd": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
@@ -166,6 +175,11 @@ SYMBOLS = {
     "pg_istft": (C.c_int, [C.POINTER(IstftArgs), C.c_void_p]),
     "pg_gl_project": (C.c_int, [C.POINTER(GlArgs), C.c_void_p]),
     "pg_ola_nt": (C.c_int, [C.POINTER(OlaArgs), C.c_void_p]),
+    "pg_resample_out_len": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "pg_resample_taps": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "pg_resample_bank_elems": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "pg_resample_bank": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "pg_resample": (C.c_int, [C.POINTER(ResampleArgs), C.c_void_p]),
     "pg_fill": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "pg_conv_fwd_h_describe": (C.c_int, [C.POINTER(ConvhArgs), C.c_char_p, C.c_int32]),
     "pg_version": (C.c_int, []),

@@ -641,6 +641,72 @@ def stft(y, n_fft, hop, polar=False, out=None, single_frame=None, chunk_start=No
     return out
 
 
+_RES_TYPES = {"kaiser_best": _lib.RS_KAISER_BEST, "kaiser_fast": _lib.RS_KAISER_FAST,
+              _lib.RS_KAISER_BEST: _lib.RS_KAISER_BEST, _lib.RS_KAISER_FAST: _lib.RS_KAISER_FAST}
+_resample_banks = {}     # (U, D, quality, device) -> device copy of pg_resample_bank's output (read-only; at most 226 KB each)
+
+
+def resample_bank_host(up, down, quality=_lib.RS_KAISER_BEST):
+    """pg_resample_bank: the (taps, U) float32 polyphase filter bank of up / down, built on the host in double (no GPU needed)."""
+    import numpy as np
+    lib = _lib.load()
+    n = lib.pg_resample_bank_elems(up, down, quality)
+    if n < 0:
+        _lib.check(int(n), "resample_bank_elems")
+    bank = np.empty(n, np.float32)
+    _lib.check(lib.pg_resample_bank(bank.ctypes.data_as(C.c_void_p), up, down, quality), "resample_bank")
+    return bank.reshape(lib.pg_resample_taps(up, down, quality), -1)
+
+
+def _resample_bank(up, down, quality, device):
+    import math
+    g = math.gcd(up, down)
+    key = (up // g, down // g, quality, torch.device(device))
+    bank = _resample_banks.get(key)
+    if bank is None:
+        bank = _resample_banks[key] = torch.from_numpy(resample_bank_host(up, down, quality)).to(device)
+    return bank
+
+
+def resample(x, orig_sr, target_sr, res_type="kaiser_best", out=None):
+    """librosa.resample(x, orig_sr, target_sr) of preproc_mdb.py:114 on device: x (n,) or (n_signals, n) float32 whose rows are
+    contiguous (the row stride is free) -> (..., ceil(n * target_sr / orig_sr)).  Kaiser-windowed sinc with resampy's published
+    ``kaiser_best`` / ``kaiser_fast`` parameters (include/phasegen.h; parity with resampy's table interpolation is unpinned).
+    The filter bank is built once per (reduced ratio, quality, device).  Equal rates return ``x`` itself, as librosa does."""
+    orig_sr, target_sr = int(orig_sr), int(target_sr)
+    if res_type not in _RES_TYPES:
+        raise ValueError(f"resample: res_type must be 'kaiser_best' or 'kaiser_fast', got {res_type!r}")
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() in (1, 2)):
+        raise ValueError(f"resample: expected a 1-D or 2-D float32 device tensor, got {tuple(x.shape)} {x.dtype} {x.device}")
+    if orig_sr == target_sr and orig_sr > 0:
+        return x
+    _on_current_device(x, "x")
+    lib = _lib.load()
+    x2 = x[None] if x.dim() == 1 else x
+    n_sig, n_in = x2.shape
+    if n_in > 1 and x2.stride(1) != 1:
+        raise ValueError(f"resample: samples must be contiguous (strides {x.stride()})")
+    n_out = lib.pg_resample_out_len(n_in, target_sr, orig_sr)
+    if n_out < 0:
+        _lib.check(int(n_out), "resample_out_len")
+    want = (n_out,) if x.dim() == 1 else (n_sig, n_out)
+    if out is None:
+        out = torch.empty(want, device=x.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == want and (n_out == 1 or out.stride(-1) == 1)):
+        raise ValueError(f"resample: out must be a float32 device tensor of shape {want} with contiguous rows")
+    else:
+        _on_current_device(out, "out")
+    o2 = out[None] if out.dim() == 1 else out
+    quality = _RES_TYPES[res_type]
+    a = _lib.ResampleArgs()
+    a.n_signals, a.up, a.down, a.quality, a.n_in, a.n_out = n_sig, target_sr, orig_sr, quality, n_in, n_out
+    a.x, a.x_stride = x2.data_ptr(), (x2.stride(0) if n_sig > 1 else n_in)
+    a.y, a.y_stride = o2.data_ptr(), (o2.stride(0) if n_sig > 1 else n_out)
+    a.bank = _resample_bank(target_sr, orig_sr, quality, x.device).data_ptr()
+    _lib.check(lib.pg_resample(C.byref(a), _stream()), "resample")
+    return out
+
+
 _moments_ws = _StreamCache()
 _caches.append(_moments_ws)
 

@@ -1,8 +1,14 @@
-"""Feature extraction of preproc_mdb.py on device: chunking + STFT + global normalisation +
-shuffled split, producing the on-disk format data.py consumes: (N, 2, n_fft/2, frames) float32 ``{genre}_audio_{train,
-val}.npy``.  MedleyDB walking, stem mixing and resampling (preproc_mdb.py:15-64,105-116) stay out of scope: the input here
-is already-loaded mono audio at the target rate.
+"""Feature extraction of preproc_mdb.py on device: wav loading + rate change + chunking + STFT +
+global normalisation + shuffled split, producing the on-disk format data.py consumes: (N, 2, n_fft/2, frames) float32
+``{genre}_audio_{train,val}.npy``.  MedleyDB walking and stem mixing (preproc_mdb.py:15-64) stay out of scope; so do
+compressed audio formats: the input is wav files (``load_audio``, ``get_mix_chunks``) or already-loaded arrays / device tensors,
+at the target rate or -- with ``osr`` -- at another one.
 
+  load           preproc_mdb.py:112    the loading half of librosa.load: scipy's wav reader, integer PCM scaled to [-1, 1),
+                 channels averaged to mono
+  rate change    preproc_mdb.py:112-114 librosa.load(sr=osr) + librosa.resample(osr -> rsr): pg_resample, a Kaiser-windowed sinc
+                 with resampy's published kaiser_best / kaiser_fast parameters (parity with resampy's table interpolation is
+                 unpinned, include/phasegen.h), on the device
   chunk starts   preproc_mdb.py:66-82  one aligned chunk every t_slice samples plus n_random uniformly random crops in
                  [0, a_len - t_slice // 1.3) after each -- the random starts come from a numpy Generator you pass, so a
                  run is reproducible (the reference uses the global np.random state)
@@ -37,16 +43,56 @@ def n_chunks(a_len, t_slice, n_random):
     return len(range(0, a_len, t_slice)) * (1 + n_random)
 
 
+def load_audio(path, mono=True):
+    """The loading half of librosa.load (preproc_mdb.py:112) for wav files, through scipy.io.wavfile: int16 / 32768, int32 / 2^31,
+    uint8 (v - 128) / 128, float as is; with ``mono`` the channels are averaged.  -> (float32 array (samples,) -- or
+    (channels, samples) for multi-channel files with mono=False --, the file's own sample rate).  No rate change happens here."""
+    from scipy.io import wavfile
+    sr, d = wavfile.read(path)
+    if d.dtype == np.int16:
+        a = d.astype(np.float32) / np.float32(32768.0)
+    elif d.dtype == np.int32:
+        a = d.astype(np.float32) / np.float32(2147483648.0)
+    elif d.dtype == np.uint8:
+        a = (d.astype(np.float32) - np.float32(128.0)) / np.float32(128.0)
+    elif d.dtype.kind == "f":
+        a = d.astype(np.float32)
+    else:
+        raise ValueError(f"load_audio: unsupported sample type {d.dtype} in {path}")
+    if a.ndim == 2:
+        a = a.mean(axis=1) if mono else np.ascontiguousarray(a.T)
+    return a, int(sr)
+
+
+def _device_of(device):
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def resample(audio, orig_sr, target_sr, res_type="kaiser_best", device=None):
+    """librosa.resample (preproc_mdb.py:114) on the device: host array or device tensor, (samples,) or (channels, samples) ->
+    float32 device tensor at ``target_sr`` (ops.resample; equal rates pass through)."""
+    if torch.is_tensor(audio):
+        a = audio.to(audio.device if device is None and audio.is_cuda else _device_of(device), torch.float32)
+    else:
+        a = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(_device_of(device))
+    return ops.resample(a, orig_sr, target_sr, res_type=res_type)
+
+
 def chunk_audio(audio, t_slice, n_fft, hop_length, n_random, rng, device=None, out=None):
-    """audio: mono float array (or (channels, samples)).  -> (n_chunks, channels, 2, n_fft/2, frames) device tensor (``out``,
-    when given, is that tensor: a slice of the dataset array)."""
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    a = np.asarray(audio, dtype=np.float32)
-    if a.ndim == 1:
-        a = a[None]
-    n_ch, a_len = a.shape
+    """audio: mono float array (or (channels, samples)), on the host or a device tensor (used where it is: no host round
+    trip).  -> (n_chunks, channels, 2, n_fft/2, frames) device tensor (``out``, when given, is that tensor: a slice of the
+    dataset array)."""
+    dev = _device_of(device)
+    if torch.is_tensor(audio):
+        ad = audio.to(dev, torch.float32)
+        ad = (ad[None] if ad.dim() == 1 else ad).contiguous()
+    else:
+        a = np.asarray(audio, dtype=np.float32)
+        if a.ndim == 1:
+            a = a[None]
+        ad = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    n_ch, a_len = ad.shape
     starts = chunk_starts(a_len, t_slice, n_random, rng)
-    ad = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     # signal order (chunk, channel): the layout of the dataset array, so the STFT writes it directly
     st = torch.tensor(np.repeat(np.asarray(starts, np.int64), n_ch), device=dev)
     rows = torch.tensor(np.tile(np.arange(n_ch, dtype=np.int32), len(starts)), device=dev)
@@ -58,14 +104,34 @@ def chunk_audio(audio, t_slice, n_fft, hop_length, n_random, rng, device=None, o
     return out
 
 
+def get_mix_chunks(fn, t_slice, n_fft, hop_length, n_random, rsr, osr=44100, rng=None, device=None):
+    """preproc_mdb.py:105-116: ``fn`` is a wav path or a tuple of paths (the stems / mixes of one track).  Each file is loaded as
+    mono (librosa.load(f, sr=osr): resampled to ``osr`` when its own rate differs), resampled from ``osr`` to ``rsr``, the
+    signals are trimmed to the shortest (chunk_audio, preproc_mdb.py:68-69), stacked and chunked.  -> chunk_audio's tensor."""
+    if not isinstance(fn, tuple):
+        fn = (fn,)
+    dev = _device_of(device)
+    mix = []
+    for f in fn:
+        m, sr = load_audio(f, mono=True)
+        m = resample(m, sr, osr, device=dev)
+        mix.append(resample(m, osr, rsr, device=dev))
+    a_len = min(m.shape[-1] for m in mix)
+    audio = torch.stack([m[:a_len] for m in mix])
+    return chunk_audio(audio, t_slice, n_fft, hop_length, n_random, np.random.default_rng() if rng is None else rng, dev)
+
+
 def build_dataset(tracks, chunk_seconds=4.064, rsr=16000, n_fft=2048, hop_length=512, n_random=0, n_val=40, seed=0,
-                  out_dir=None, genre="Pop", device=None):
-    """tracks: list of mono float arrays at ``rsr``.  Returns (train, val) float32 numpy arrays; also writes
+                  out_dir=None, genre="Pop", device=None, osr=None):
+    """tracks: list of mono float arrays (or device tensors) at ``rsr`` -- or at ``osr`` when that is given: every track is then
+    resampled to ``rsr`` on the device first.  Returns (train, val) float32 numpy arrays; also writes
     ``{out_dir}/{genre}_audio_{train,val}.npy`` when ``out_dir`` is given (preproc_mdb.py:195-196)."""
     rng = np.random.default_rng(seed)
     t_slice = int(chunk_seconds * rsr)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    shaped = [np.asarray(t, np.float32).reshape(-1, np.shape(t)[-1]).shape for t in tracks]     # (channels, samples) per track
+    dev = _device_of(device)
+    if osr is not None and osr != rsr:
+        tracks = [resample(t, osr, rsr, device=dev) for t in tracks]
+    shaped = [(int(np.prod(np.shape(t)[:-1], dtype=np.int64)), np.shape(t)[-1]) for t in tracks]     # (channels, samples) per track
     n_ch = shaped[0][0]
     counts = [n_chunks(a_len, t_slice, n_random) for _, a_len in shaped]
     x = torch.empty(sum(counts), n_ch, 2, n_fft // 2, 1 + t_slice // hop_length, device=dev)    # (N, channels, 2, bins, frames)
