@@ -317,6 +317,38 @@ typedef struct pg_resample_args {
 } pg_resample_args;
 int pg_resample(const pg_resample_args* a, void* stream);
 
+/* Whole tracks from overlapped clips: crossfaded overlap-add of n_clips equal-length clips per track, plus the finite check and the
+ * peak normalisation of utils.py:41-42 taken over the WHOLE result (all tracks jointly: librosa.util.normalize(axis=None)).  The
+ * reference has no counterpart (its demo.py stops at clips of `frames` columns); the arithmetic below is the contract.
+ *   T = clip_len; clip k begins at output sample k step; V = T - step samples are shared with the next clip (0 <= 2 V <= T: at most
+ *   two clips cover a sample); (n_clips-1) step < n_out <= (n_clips-1) step + T (the last clip may be cut short).
+ *   ramp[j] = float32(sin^2(pi (j + 0.5) / (2 V))), 0 <= j < V, evaluated in double on the HOST (pg_stitch_ramp): every entry is
+ *   strictly positive and ramp[j] + ramp[V-1-j] is within 2^-23 of 1.  pg_stitch takes a DEVICE copy, as pg_resample its bank: the
+ *   library allocates nothing and keeps nothing.
+ *   Output sample t of a track: k = min(t div step, n_clips-1), j = t - k step.  If k >= 1 and j < V, with a = ramp[V-1-j],
+ *   b = ramp[j], lo = clip[k-1][j + step], hi = clip[k][j]:   raw = (fl(a lo) + fl(b hi)) / fl(a + b)   -- all fp32, nothing
+ *   contracted, the lower clip's term first.  Otherwise raw = clip[k][j], copied bit for bit (the head of clip 0 and the tail of the
+ *   last clip are never faded).  Hence step == T concatenates the clips and all-ones clips give all ones, bit for bit.
+ *   *n_nonfinite = number of output samples of all tracks that are NaN or +-inf; *peak = max |raw| over the finite samples of all
+ *   tracks; with normalize = 1 and peak > FLT_MIN, out = raw / peak, else out = raw.  The reduction is two-stage through `workspace`
+ *   (per-workgroup partials, then a second launch; no float atomics) and exact in any order: the result does not depend on the grid.
+ *   The workspace (pg_workspace_bytes_stitch() bytes, else PG_ERR_WORKSPACE) is needed only when normalize, peak or n_nonfinite is set.
+ * Samples move 16 bytes per lane when step, T, the three strides and the pointers allow it and one by one otherwise; both paths give
+ * the same bits.  Index arithmetic is 64-bit.  pg_stitch_ramp: overlap == 0 writes nothing (PG_OK), overlap < 0 is PG_ERR_SHAPE. */
+int     pg_stitch_ramp(float* ramp_host, int32_t overlap);   /* HOST buffer of `overlap` floats, double arithmetic */
+typedef struct pg_stitch_args {
+    int32_t n_tracks, n_clips, clip_len, step;   /* T = clip_len; V = T - step is the overlap; 0 <= 2 V <= T, step >= 1 */
+    int64_t n_out;                               /* (n_clips-1)*step < n_out <= (n_clips-1)*step + T                      */
+    const float* clips; int64_t clip_stride, track_stride;   /* clip k of track r: clips + r*track_stride + k*clip_stride, T contiguous samples */
+    float* out; int64_t out_stride;              /* (n_tracks, n_out), rows out_stride >= n_out apart                    */
+    const float* ramp;                           /* DEVICE copy of pg_stitch_ramp(V); may be NULL iff V == 0             */
+    int32_t normalize, _pad0;
+    float* peak; int32_t* n_nonfinite;           /* optional device outputs, one value each                              */
+    void* workspace; int64_t workspace_bytes;
+} pg_stitch_args;                                /* 112 bytes */
+int64_t pg_workspace_bytes_stitch(const pg_stitch_args* a);  /* host; negative = error code */
+int     pg_stitch(const pg_stitch_args* a, void* stream);
+
 /* small helpers the training step needs on device */
 int pg_fill(float* p, int64_t n, float value, void* stream);
 

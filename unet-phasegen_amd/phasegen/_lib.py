@@ -142,6 +142,17 @@ class ResampleArgs(C.Structure):
                 ("bank", C.c_void_p)]
 
 
+class StitchArgs(C.Structure):
+    """pg_stitch_args: crossfaded overlap-add of equal-length clips into tracks (include/phasegen.h)."""
+    _fields_ = [("n_tracks", C.c_int32), ("n_clips", C.c_int32), ("clip_len", C.c_int32), ("step", C.c_int32),
+                ("n_out", C.c_int64),
+                ("clips", C.c_void_p), ("clip_stride", C.c_int64), ("track_stride", C.c_int64),
+                ("out", C.c_void_p), ("out_stride", C.c_int64),
+                ("ramp", C.c_void_p), ("normalize", C.c_int32), ("_pad0", C.c_int32),
+                ("peak", C.c_void_p), ("n_nonfinite", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 # every symbol include/phasegen.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pg_conv1d_fwd": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
@@ -180,6 +191,9 @@ SYMBOLS = {
     "pg_resample_bank_elems": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "pg_resample_bank": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "pg_resample": (C.c_int, [C.POINTER(ResampleArgs), C.c_void_p]),
+    "pg_stitch_ramp": (C.c_int, [C.c_void_p, C.c_int32]),
+    "pg_workspace_bytes_stitch": (C.c_int64, [C.POINTER(StitchArgs)]),
+    "pg_stitch": (C.c_int, [C.POINTER(StitchArgs), C.c_void_p]),
     "pg_fill": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "pg_conv_fwd_h_describe": (C.c_int, [C.POINTER(ConvhArgs), C.c_char_p, C.c_int32]),
     "pg_version": (C.c_int, []),

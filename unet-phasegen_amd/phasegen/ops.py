@@ -167,7 +167,7 @@ def conv_workspace(device):
 
 
 def release_workspaces():
-    """Drop every cached scratch buffer (conv stream-K, loss, ISTFT, overlap-add, moments): they are re-created on demand."""
+    """Drop every cached scratch buffer (conv stream-K, loss, ISTFT, overlap-add, moments, stitch): they are re-created on demand."""
     for c in _caches:
         c.clear()
 
@@ -707,6 +707,84 @@ def resample(x, orig_sr, target_sr, res_type="kaiser_best", out=None):
     return out
 
 
+_stitch_ramps = {}       # (V, device) -> device copy of pg_stitch_ramp's output (read-only)
+_stitch_ws = _StreamCache()
+_caches.append(_stitch_ws)
+
+
+def stitch_ramp_host(overlap):
+    """pg_stitch_ramp: the crossfade ramp float32(sin^2(pi (j + 0.5) / (2 V))), j < V, built on the host in double (no GPU needed)."""
+    import numpy as np
+    ramp = np.empty(max(int(overlap), 0), np.float32)
+    _lib.check(_lib.load().pg_stitch_ramp(ramp.ctypes.data_as(C.c_void_p) if ramp.size else None, int(overlap)), "stitch_ramp")
+    return ramp
+
+
+def _stitch_ramp(V, device):
+    key = (V, torch.device(device))
+    ramp = _stitch_ramps.get(key)
+    if ramp is None:
+        ramp = _stitch_ramps[key] = torch.from_numpy(stitch_ramp_host(V)).to(device)
+    return ramp
+
+
+def stitch(clips, step, n_out, normalize=False, out=None, return_status=False):
+    """Crossfaded overlap-add of equal-length clips into tracks (pg_stitch): clips (n_clips, T) or (n_tracks, n_clips, T) float32
+    on the device, samples contiguous, outer strides free; clip k begins at output sample k * step and shares V = T - step samples
+    (0 <= 2 V <= T) with the next one under a sin^2 ramp; (n_clips - 1) * step < n_out <= (n_clips - 1) * step + T.  -> (n_out,)
+    or (n_tracks, n_out).  ``normalize``: divide by the peak of the finite samples of ALL tracks (utils.py:42 for whole tracks).
+    ``return_status``: also the (peak, n_nonfinite) device tensors (float32 / int32, 0-d)."""
+    if not (torch.is_tensor(clips) and clips.is_cuda and clips.dtype == torch.float32 and clips.dim() in (2, 3)):
+        raise ValueError("stitch: clips must be a 2-D or 3-D float32 device tensor")
+    _on_current_device(clips, "clips")
+    c3 = clips[None] if clips.dim() == 2 else clips
+    n_tracks, n_clips, T = c3.shape
+    step, n_out = int(step), int(n_out)
+    if n_tracks < 1 or n_clips < 1 or T < 1:
+        raise ValueError(f"stitch: empty clips {tuple(clips.shape)}")
+    if not 1 <= step <= T or 2 * (T - step) > T:
+        raise ValueError(f"stitch: step {step} with clips of {T} samples (need 1 <= step <= T and an overlap T - step of at most T / 2)")
+    if not (n_clips - 1) * step < n_out <= (n_clips - 1) * step + T:
+        raise ValueError(f"stitch: n_out {n_out} outside ({(n_clips - 1) * step}, {(n_clips - 1) * step + T}]")
+    if T > 1 and c3.stride(2) != 1:
+        raise ValueError(f"stitch: samples must be contiguous (strides {clips.stride()})")
+    clip_stride = c3.stride(1) if n_clips > 1 else T
+    track_stride = c3.stride(0) if n_tracks > 1 else n_clips * max(clip_stride, T)
+    if clip_stride < T or track_stride < 0:
+        raise ValueError(f"stitch: clips overlap in memory (strides {clips.stride()})")
+    want = (n_out,) if clips.dim() == 2 else (n_tracks, n_out)
+    if out is None:
+        out = torch.empty(want, device=clips.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == want and (n_out == 1 or out.stride(-1) == 1)):
+        raise ValueError(f"stitch: out must be a float32 device tensor of shape {want} with contiguous rows")
+    else:
+        _on_current_device(out, "out")
+    o2 = out[None] if out.dim() == 1 else out
+    out_stride = o2.stride(0) if n_tracks > 1 else n_out
+    if out_stride < n_out:
+        raise ValueError(f"stitch: rows of out overlap (strides {out.stride()})")
+    lib = _lib.load()
+    a = _lib.StitchArgs()
+    a.n_tracks, a.n_clips, a.clip_len, a.step, a.n_out = n_tracks, n_clips, T, step, n_out
+    a.clips, a.clip_stride, a.track_stride = c3.data_ptr(), clip_stride, track_stride
+    a.out, a.out_stride = o2.data_ptr(), out_stride
+    if T > step:
+        a.ramp = _stitch_ramp(T - step, clips.device).data_ptr()
+    a.normalize = int(bool(normalize))
+    status = None
+    if normalize or return_status:
+        need = lib.pg_workspace_bytes_stitch(C.byref(a))
+        if need < 0:
+            _lib.check(int(need), "workspace_bytes_stitch")
+        ws = _stitch_ws.get(clips.device, lambda: need, need)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    if return_status:
+        status = (torch.empty((), device=clips.device, dtype=torch.float32), torch.empty((), device=clips.device, dtype=torch.int32))
+        a.peak, a.n_nonfinite = status[0].data_ptr(), status[1].data_ptr()
+    _lib.check(lib.pg_stitch(C.byref(a), _stream()), "stitch")
+    return (out, status[0], status[1]) if return_status else out
+
+
 _moments_ws = _StreamCache()
 _caches.append(_moments_ws)
 
@@ -722,6 +800,15 @@ def standardize_(x):
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
     _lib.check(lib.pg_moments(C.byref(a), _stream()), "moments")
     _lib.check(lib.pg_standardize(C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(stats.data_ptr()), _stream()), "standardize")
+    return stats
+
+
+def standardize_with_(x, mean, std):
+    """``standardize_`` with statistics the caller supplies -- a training set's (mean, std) applied to new audio: x = (x - mean)
+    / std in place, the same pg_standardize launch (float32 arithmetic on float32(mean), float32(std)).  Returns the two-double
+    device tensor it passed."""
+    stats = torch.tensor([float(mean), float(std)], dtype=torch.float64).to(x.device)
+    _lib.check(_lib.load().pg_standardize(C.c_void_p(_dense(x, "x")), x.numel(), C.c_void_p(stats.data_ptr()), _stream()), "standardize")
     return stats
 
 

@@ -122,10 +122,13 @@ def get_mix_chunks(fn, t_slice, n_fft, hop_length, n_random, rsr, osr=44100, rng
 
 
 def build_dataset(tracks, chunk_seconds=4.064, rsr=16000, n_fft=2048, hop_length=512, n_random=0, n_val=40, seed=0,
-                  out_dir=None, genre="Pop", device=None, osr=None):
+                  out_dir=None, genre="Pop", device=None, osr=None, return_stats=False):
     """tracks: list of mono float arrays (or device tensors) at ``rsr`` -- or at ``osr`` when that is given: every track is then
     resampled to ``rsr`` on the device first.  Returns (train, val) float32 numpy arrays; also writes
-    ``{out_dir}/{genre}_audio_{train,val}.npy`` when ``out_dir`` is given (preproc_mdb.py:195-196)."""
+    ``{out_dir}/{genre}_audio_{train,val}.npy`` when ``out_dir`` is given (preproc_mdb.py:195-196).
+    ``return_stats=True``: returns (train, val, (mean, std)) -- the two Python floats of the normalisation, which the reference
+    computes and throws away and which new audio needs to be normalised like the training set (phasegen.track) -- and also writes
+    them, two float64 values, to ``{out_dir}/{genre}_audio_stats.npy``."""
     rng = np.random.default_rng(seed)
     t_slice = int(chunk_seconds * rsr)
     dev = _device_of(device)
@@ -141,7 +144,7 @@ def build_dataset(tracks, chunk_seconds=4.064, rsr=16000, n_fft=2048, hop_length
         o += c
     if x.shape[1] == 1:
         x = x[:, 0]                                                      # np.squeeze(axis=1), preproc_mdb.py:179-180
-    ops.standardize_(x)                                                  # numpy .std() is the population std
+    stats = ops.standardize_(x)                                          # numpy .std() is the population std
     x = x.cpu().numpy()
     idx = np.linspace(0, len(x) - 1, len(x), dtype=int)
     rng.shuffle(idx)
@@ -150,4 +153,9 @@ def build_dataset(tracks, chunk_seconds=4.064, rsr=16000, n_fft=2048, hop_length
         os.makedirs(out_dir, exist_ok=True)
         np.save(os.path.join(out_dir, f"{genre}_audio_val.npy"), val)
         np.save(os.path.join(out_dir, f"{genre}_audio_train.npy"), train)
+    if return_stats:
+        mean, std = (float(v) for v in stats.cpu().numpy())
+        if out_dir is not None:
+            np.save(os.path.join(out_dir, f"{genre}_audio_stats.npy"), np.array([mean, std], np.float64))
+        return train, val, (mean, std)
     return train, val

@@ -1,0 +1,69 @@
+#!/usr/bin/env python3
+"""Whole-track phase reconstruction from the command line: a wav file of any length and rate goes through a trained U-Net as
+overlapped clips and comes back as one wav at ``--sr`` with the predicted phase (``phasegen.track.reconstruct_track``).  The
+reference's ``demo.py`` stops at dataset clips; flags shared with it keep its names and defaults.
+
+``--stats`` is the ``{genre}_audio_stats.npy`` that ``phasegen.preproc.build_dataset(..., return_stats=True)`` writes beside the
+training set: the (mean, std) the model's inputs were normalised with.  Without it the track's own moments are used.
+WAV files are written with scipy (float32 PCM), as in ``demo.py``.
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def main():
+    parser = argparse.ArgumentParser(description="Reconstruct the phase of a whole track.")
+    parser.add_argument("--weight", required=True, help="a UNetModel.save checkpoint")
+    parser.add_argument("--input", required=True, help="wav in")
+    parser.add_argument("--output", required=True, help="wav out")
+    parser.add_argument("--stats", default=None, help="*_audio_stats.npy of the training set (default: this track's own moments)")
+    parser.add_argument("--channels", default=1024, type=int, help="bins = model width")
+    parser.add_argument("--n_fft", default=None, type=int, help="default: 2 * channels")
+    parser.add_argument("--hop", default=None, type=int, help="default: n_fft / 4")
+    parser.add_argument("--frames", default=128, type=int)
+    parser.add_argument("--overlap_frames", default=32, type=int)
+    parser.add_argument("--sr", default=16000, type=int)
+    parser.add_argument("--precision", choices=["fp32", "bf16x3", "bf16"], default="fp32",
+                        help="MFMA operand mode of the convolutions (pg_conv_args.precision): fp32 = the reference's arithmetic")
+    parser.add_argument("--gpu", default=0, type=int)
+    parser.add_argument("--stereo", action="store_true", help="keep the file's channels instead of their mono average")
+    args = parser.parse_args()
+    n_fft = 2 * args.channels if args.n_fft is None else args.n_fft
+    hop = n_fft // 4 if args.hop is None else args.hop
+    if n_fft != 2 * args.channels:
+        parser.error("--n_fft must be 2 * --channels (the model takes n_fft / 2 bins)")
+
+    import numpy as np
+    import torch
+    from scipy.io import wavfile
+    from cycleGAN import UNetModel
+    from phasegen import preproc, track
+
+    torch.cuda.set_device(args.gpu)
+    model = UNetModel(args.channels, args.channels * 2, gpu_ids=[args.gpu], precision=args.precision).cuda(args.gpu)
+    model.load(args.weight)
+    stats = None
+    if args.stats is not None:
+        mean, std = (float(v) for v in np.load(args.stats))
+        stats = (mean, std)
+    else:
+        print("reconstruct: no --stats given, normalising with this track's own mean and std", file=sys.stderr)
+    audio, file_sr = preproc.load_audio(args.input, mono=not args.stereo)
+
+    start = time.time()
+    out = track.reconstruct_track(model, audio, n_fft=n_fft, hop_length=hop, frames=args.frames, overlap_frames=args.overlap_frames,
+                                  stats=stats, osr=file_sr, sr=args.sr)
+    out = out.cpu().numpy()
+    took = time.time() - start
+    n = out.shape[-1]
+    _, _, n_clips = track.track_plan(n, args.frames, hop, args.overlap_frames)
+    wavfile.write(args.output, args.sr, np.ascontiguousarray(out.T if out.ndim == 2 else out, dtype=np.float32))
+    print("Reconstructed {:.2f} s of audio in {:.3f} s ({} clips).".format(n / args.sr, took, n_clips))
+
+
+if __name__ == "__main__":
+    main()
