@@ -349,6 +349,54 @@ typedef struct pg_stitch_args {
 int64_t pg_workspace_bytes_stitch(const pg_stitch_args* a);  /* host; negative = error code */
 int     pg_stitch(const pg_stitch_args* a, void* stream);
 
+/* How far a reconstruction is from its source, reduced on the device: the sums from which SI-SDR / SNR (waveforms) and spectral
+ * convergence / log-spectral distance (spectrograms) are formed on the host (phasegen/metrics.py).  The reference has no counterpart
+ * (validate.py takes mean absolute waveform errors of three dataset clips on the host); the arithmetic below is the contract.
+ * Common to both calls: `out` is (n_signals, 6) DEVICE doubles, row s for signal s; `gain` is NULL (= 1.0) or n_signals device
+ * doubles; sums are kept in double and reduced in two or three launches through `workspace` (pg_workspace_bytes_*() bytes, else
+ * PG_ERR_WORKSPACE; no floating-point atomics; the library allocates nothing and keeps nothing).  The partition of the work and every
+ * summation tree are functions of the shapes (n; bins, frames) alone -- not of the grid, the CU count, n_signals or the signal's
+ * position -- so row s of a batch has the bits of the same signal run alone.  Elements move 16 bytes per lane where the base
+ * pointers and the strides (and, for spectrograms, frames % 4 == 0) allow and one by one otherwise; both paths give the same bits.
+ * Index arithmetic is 64-bit.
+ *
+ * pg_wave_compare: x (reference) and y (estimate), (n_signals, n) fp32, rows x_stride / y_stride >= n apart; g = gain[s].
+ *   A sample where x or y is NaN or +-inf is counted in slot 5 and taken as 0 in BOTH inputs.  Element arithmetic is in double: the
+ *   products x x, y y, x y of two floats are exact; g y is rounded, x - g y is rounded, its square is rounded.
+ *     out[s] = { sum x^2, sum y^2, sum x y, sum (x - g y)^2, max |x - g y|, number of non-finite samples }
+ *
+ * pg_spec_compare: R (reference) and E (estimate) in the layout pg_stft writes, (n_signals, 2, bins, frames) fp32 = [re; im] planes
+ *   bins * frames apart, signals r_stride / e_stride >= 2 bins frames apart; bins and frames are any positive integers.
+ *   Per cell, in fp32 and uncontracted, with g_f = (float)gain[s]:
+ *     mR = sqrtf(re^2 + im^2) of R, mE0 = sqrtf(re^2 + im^2) of E, mE = g_f mE0, L(m) = 10 log10f(fmaxf(m m, floor_power))
+ *   A cell where any of its four floats is NaN or +-inf is counted in slot 5 and taken as zero in both inputs.  The products mR mR,
+ *   mE0 mE0, mR mE0, (mR - mE)^2 and (L(mR) - L(mE))^2 are formed in fp32 and promoted to double before they are added.
+ *     out[s] = { sum mR^2, sum mE0^2, sum mR mE0, sum (mR - mE)^2,
+ *                sum over frames of sqrt((sum over bins of (L(mR) - L(mE))^2) / bins), number of non-finite cells }
+ *   Slot 4 / frames is the log-spectral distance in dB; a cell that is zero in both inputs adds 0 to it (both levels are the floor's).
+ *   floor_power must be positive and finite (PG_ERR_SHAPE). */
+typedef struct pg_wave_compare_args {
+    int32_t n_signals, _pad0;
+    int64_t n;
+    const float* x; int64_t x_stride;
+    const float* y; int64_t y_stride;
+    const double* gain;                          /* optional (NULL = 1.0): n_signals device doubles */
+    double* out;                                 /* (n_signals, 6) device doubles                   */
+    void* workspace; int64_t workspace_bytes;
+} pg_wave_compare_args;                          /* 80 bytes */
+int64_t pg_workspace_bytes_wave_compare(const pg_wave_compare_args* a);   /* host function of n_signals and n; negative = error code */
+int     pg_wave_compare(const pg_wave_compare_args* a, void* stream);
+typedef struct pg_spec_compare_args {
+    int32_t n_signals, bins, frames; float floor_power;
+    const float* R; int64_t r_stride;
+    const float* E; int64_t e_stride;
+    const double* gain;                          /* optional (NULL = 1.0): n_signals device doubles */
+    double* out;                                 /* (n_signals, 6) device doubles                   */
+    void* workspace; int64_t workspace_bytes;
+} pg_spec_compare_args;                          /* 80 bytes */
+int64_t pg_workspace_bytes_spec_compare(const pg_spec_compare_args* a);   /* host function of n_signals, bins, frames; negative = error code */
+int     pg_spec_compare(const pg_spec_compare_args* a, void* stream);
+
 /* small helpers the training step needs on device */
 int pg_fill(float* p, int64_t n, float value, void* stream);
 

@@ -153,6 +153,22 @@ class StitchArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class WaveCompareArgs(C.Structure):
+    """pg_wave_compare_args: six sums per signal of a reference / estimate pair of waveforms (include/phasegen.h)."""
+    _fields_ = [("n_signals", C.c_int32), ("_pad0", C.c_int32), ("n", C.c_int64),
+                ("x", C.c_void_p), ("x_stride", C.c_int64), ("y", C.c_void_p), ("y_stride", C.c_int64),
+                ("gain", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class SpecCompareArgs(C.Structure):
+    """pg_spec_compare_args: six sums per signal of a reference / estimate pair of spectrograms (include/phasegen.h)."""
+    _fields_ = [("n_signals", C.c_int32), ("bins", C.c_int32), ("frames", C.c_int32), ("floor_power", C.c_float),
+                ("R", C.c_void_p), ("r_stride", C.c_int64), ("E", C.c_void_p), ("e_stride", C.c_int64),
+                ("gain", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 # every symbol include/phasegen.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pg_conv1d_fwd": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
@@ -194,6 +210,10 @@ SYMBOLS = {
     "pg_stitch_ramp": (C.c_int, [C.c_void_p, C.c_int32]),
     "pg_workspace_bytes_stitch": (C.c_int64, [C.POINTER(StitchArgs)]),
     "pg_stitch": (C.c_int, [C.POINTER(StitchArgs), C.c_void_p]),
+    "pg_workspace_bytes_wave_compare": (C.c_int64, [C.POINTER(WaveCompareArgs)]),
+    "pg_wave_compare": (C.c_int, [C.POINTER(WaveCompareArgs), C.c_void_p]),
+    "pg_workspace_bytes_spec_compare": (C.c_int64, [C.POINTER(SpecCompareArgs)]),
+    "pg_spec_compare": (C.c_int, [C.POINTER(SpecCompareArgs), C.c_void_p]),
     "pg_fill": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "pg_conv_fwd_h_describe": (C.c_int, [C.POINTER(ConvhArgs), C.c_char_p, C.c_int32]),
     "pg_version": (C.c_int, []),

@@ -69,14 +69,15 @@ def _synthesis_matrix(bins, device):
     return _synth[key]
 
 
-def griffin_lim_batch(mag, n_fft, hop_length, n_iter, init=None, seed=None):
+def griffin_lim_batch(mag, n_fft, hop_length, n_iter, init=None, seed=None, normalize=True):
     """utils.py:85-134 for a BATCH of clips, device tensors in and out: ``mag`` (n, n_fft/2, frames) magnitudes (DC dropped).
     Every iteration is four launches whatever n is -- STFT (pg_stft) -> keep phase, impose magnitude (pg_gl_project) -> the
     2046-point inverse transform as ONE 1x1 convolution on the fp32-MFMA conv kernel (batch axis = clips) -> overlap-add
     (pg_ola_nt) -- and clip c's result is bit-identical to running it alone (no kernel reduces across clips).
     ``init``: (n, hop * (frames - 1)) start signals; else clip c starts from N(0, 1) drawn with seed ``seed + c`` (or ``seed[c]``
     when a list is given; replaces ``np.random.randn``, utils.py:116).  Returns device tensors (audio (n, length) peak-normalised per clip, new_spec
-    (n, 2, bins, frames) = [re; im] of the last projection, loss (n,))."""
+    (n, 2, bins, frames) = [re; im] of the last projection, loss (n,)).  ``normalize=False`` returns the signals as the last
+    overlap-add left them (``track.evaluate_track`` stitches those: clips of one track share one scale)."""
     dev = _dev()
     if not (torch.is_tensor(mag) and mag.is_cuda and mag.dtype == torch.float32 and mag.dim() == 3):
         raise ValueError("griffin_lim_batch: mag must be a float32 device tensor (n, bins, frames)")
@@ -123,8 +124,11 @@ def griffin_lim_batch(mag, n_fft, hop_length, n_iter, init=None, seed=None):
         if n_iter > 0:
             for c in range(m):          # one 1-D reduction per clip: the summation order does not depend on how many clips run together
                 loss[c0 + c] = torch.sqrt(torch.sum((recon[c] - prev[c]) ** 2) / length)
-        peak = recon.abs().amax(dim=1, keepdim=True)
-        audio[c0:c1] = torch.where(peak > torch.finfo(torch.float32).tiny, recon / peak, recon)
+        if normalize:
+            peak = recon.abs().amax(dim=1, keepdim=True)
+            audio[c0:c1] = torch.where(peak > torch.finfo(torch.float32).tiny, recon / peak, recon)
+        else:
+            audio[c0:c1] = recon
     return audio, new_spec, loss
 
 

@@ -167,7 +167,7 @@ def conv_workspace(device):
 
 
 def release_workspaces():
-    """Drop every cached scratch buffer (conv stream-K, loss, ISTFT, overlap-add, moments, stitch): they are re-created on demand."""
+    """Drop every cached scratch buffer (conv stream-K, loss, ISTFT, overlap-add, moments, stitch, compare): they are re-created on demand."""
     for c in _caches:
         c.clear()
 
@@ -783,6 +783,106 @@ def stitch(clips, step, n_out, normalize=False, out=None, return_status=False):
         a.peak, a.n_nonfinite = status[0].data_ptr(), status[1].data_ptr()
     _lib.check(lib.pg_stitch(C.byref(a), _stream()), "stitch")
     return (out, status[0], status[1]) if return_status else out
+
+
+_compare_ws = _StreamCache()
+_caches.append(_compare_ws)
+
+
+def _compare_gain(gain, n_sig, device, name):
+    """None, a number, or a float64 device tensor of 1 or n_sig entries -> n_sig contiguous device doubles (or None)."""
+    if gain is None:
+        return None
+    if not torch.is_tensor(gain):
+        return torch.full((n_sig,), float(gain), dtype=torch.float64, device=device)
+    if not (gain.is_cuda and gain.dtype == torch.float64 and gain.numel() in (1, n_sig)):
+        raise ValueError(f"{name}: gain must be a number or a float64 device tensor of 1 or {n_sig} entries")
+    _on_current_device(gain, "gain")
+    return gain.reshape(-1).expand(n_sig).contiguous()
+
+
+def _compare_out(out, n_sig, device, name):
+    if out is None:
+        return torch.empty(n_sig, 6, dtype=torch.float64, device=device)
+    if not (out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (n_sig, 6) and out.is_contiguous()):
+        raise ValueError(f"{name}: out must be a contiguous float64 device tensor of shape {(n_sig, 6)}")
+    _on_current_device(out, "out")
+    return out
+
+
+def wave_compare(x, y, gain=None, out=None):
+    """pg_wave_compare: x (reference) and y (estimate), (n,) or (n_signals, n) float32 device tensors of equal shape whose rows are
+    contiguous (the row strides are free) -> (n_signals, 6) float64 device tensor, per row
+    [sum x^2, sum y^2, sum x y, sum (x - g y)^2, max |x - g y|, number of non-finite samples] (such samples count as 0 in both).
+    ``gain``: None (1.0), a number, or a float64 device tensor of one entry or one per row -- nothing is read back to the host."""
+    for name, t in (("x", x), ("y", y)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() in (1, 2)):
+            raise ValueError(f"wave_compare: {name} must be a 1-D or 2-D float32 device tensor")
+        _on_current_device(t, name)
+    if x.shape != y.shape:
+        raise ValueError(f"wave_compare: shapes differ: x{tuple(x.shape)} y{tuple(y.shape)}")
+    x2, y2 = (x[None], y[None]) if x.dim() == 1 else (x, y)
+    n_sig, n = x2.shape
+    if n_sig < 1 or n < 1:
+        raise ValueError(f"wave_compare: empty input {tuple(x.shape)}")
+    if n > 1 and (x2.stride(1) != 1 or y2.stride(1) != 1):
+        raise ValueError("wave_compare: samples must be contiguous")
+    a = _lib.WaveCompareArgs()
+    a.n_signals, a.n = n_sig, n
+    a.x, a.x_stride = x2.data_ptr(), (x2.stride(0) if n_sig > 1 else n)
+    a.y, a.y_stride = y2.data_ptr(), (y2.stride(0) if n_sig > 1 else n)
+    if a.x_stride < n or a.y_stride < n:
+        raise ValueError("wave_compare: rows overlap in memory")
+    g = _compare_gain(gain, n_sig, x.device, "wave_compare")
+    if g is not None:
+        a.gain = g.data_ptr()
+    out = _compare_out(out, n_sig, x.device, "wave_compare")
+    a.out = out.data_ptr()
+    lib = _lib.load()
+    need = lib.pg_workspace_bytes_wave_compare(C.byref(a))
+    if need < 0:
+        _lib.check(int(need), "workspace_bytes_wave_compare")
+    ws = _compare_ws.get(x.device, lambda: need, need)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    _lib.check(lib.pg_wave_compare(C.byref(a), _stream()), "wave_compare")
+    return out
+
+
+def spec_compare(R, E, gain=None, floor=1e-10, out=None):
+    """pg_spec_compare: R (reference) and E (estimate) in ``stft``'s layout, (n_signals, 2, bins, frames) float32 device tensors
+    (each signal dense, the signal stride free) -> (n_signals, 6) float64 device tensor, per signal [sum mR^2, sum mE0^2,
+    sum mR mE0, sum (mR - g mE0)^2, sum over frames of the rms over bins of the level difference in dB, number of non-finite cells]
+    with levels 10 log10(max(m^2, floor)).  ``gain`` as in ``wave_compare``."""
+    for name, t in (("R", R), ("E", E)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == 2):
+            raise ValueError(f"spec_compare: {name} must be a float32 device tensor (n_signals, 2, bins, frames)")
+        _on_current_device(t, name)
+        if t.numel() == 0:
+            raise ValueError(f"spec_compare: empty input {tuple(t.shape)}")
+        if not t[0].is_contiguous():
+            raise ValueError(f"spec_compare: every signal of {name} must be dense (strides {t.stride()})")
+    if R.shape != E.shape:
+        raise ValueError(f"spec_compare: shapes differ: R{tuple(R.shape)} E{tuple(E.shape)}")
+    n_sig, _, bins, frames = R.shape
+    a = _lib.SpecCompareArgs()
+    a.n_signals, a.bins, a.frames, a.floor_power = n_sig, bins, frames, float(floor)
+    a.R, a.r_stride = R.data_ptr(), (R.stride(0) if n_sig > 1 else 2 * bins * frames)
+    a.E, a.e_stride = E.data_ptr(), (E.stride(0) if n_sig > 1 else 2 * bins * frames)
+    if a.r_stride < 2 * bins * frames or a.e_stride < 2 * bins * frames:
+        raise ValueError("spec_compare: signals overlap in memory")
+    g = _compare_gain(gain, n_sig, R.device, "spec_compare")
+    if g is not None:
+        a.gain = g.data_ptr()
+    out = _compare_out(out, n_sig, R.device, "spec_compare")
+    a.out = out.data_ptr()
+    lib = _lib.load()
+    need = lib.pg_workspace_bytes_spec_compare(C.byref(a))
+    if need < 0:
+        _lib.check(int(need), "workspace_bytes_spec_compare")
+    ws = _compare_ws.get(R.device, lambda: need, need)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    _lib.check(lib.pg_spec_compare(C.byref(a), _stream()), "spec_compare")
+    return out
 
 
 _moments_ws = _StreamCache()

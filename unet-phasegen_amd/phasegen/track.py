@@ -14,12 +14,15 @@ device:
                  buffers end as after the reference's one-clip-at-a-time loop
   ISTFT          audio.synthesize, un-normalised clips of T = hop * (frames - 1) samples
   stitch         ops.stitch: sin^2 crossfade over the overlap, finite check and peak normalisation over the whole result
+
+``evaluate_track`` runs the analysis once, synthesises the track from several phase sources (the model's, none at all, the
+analysis' own, Griffin-Lim's) and reports ``metrics.compare_audio`` of each against the input.
 """
 import numpy as np
 import torch
 
 from . import audio as pg_audio
-from . import ops, preproc
+from . import metrics, ops, preproc
 from .unet import frame_plan
 
 
@@ -39,20 +42,16 @@ def track_plan(a_len, frames, hop_length, overlap_frames):
     return T, step, n_clips
 
 
-def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None,
-                      osr=None, sr=16000, res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True):
-    """audio (samples,) or (channels, samples), host array or device tensor, at ``sr`` -- or at ``osr`` when given (resampled to
-    ``sr`` first) -> float32 device tensor of the same shape with the a_len samples per channel of the track at ``sr``, its phase
-    predicted by ``model`` (phase="unet") or kept from the analysis (phase="original", ``model`` may be None: the chunk / stitch
-    round trip).  ``stats`` = (mean, std) of the training set; None: the track's own moments.  ``normalize``: peak-normalise over
-    all channels jointly (utils.py:42 for the whole track).  Raises ValueError("Audio buffer is not finite everywhere") as
-    ``audio.generate_audio`` does."""
-    if phase not in ("unet", "original"):
-        raise ValueError(f"reconstruct_track: phase must be 'unet' or 'original', got {phase!r}")
-    if phase == "unet" and model is None:
-        raise ValueError("reconstruct_track: phase='unet' needs a model")
-    if clip_batch < 1:
-        raise ValueError("reconstruct_track: clip_batch must be positive")
+PHASES = ("unet", "zero", "original", "griffinlim")
+
+
+class _Analysis:
+    """What every phase source shares: the track at ``sr`` (a2: (channels, a_len)), the clip plan and the clips' [log1p|z| ; angle]."""
+    __slots__ = ("a2", "mono", "n_ch", "a_len", "T", "step", "n_clips", "bins", "pol")
+
+
+def _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type):
+    """resample -> chunked STFT -> standardise -> polar, once per track."""
     if osr is not None:
         a = preproc.resample(audio, osr, sr, res_type=res_type)
     elif torch.is_tensor(audio):
@@ -61,11 +60,12 @@ def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, over
         a = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(preproc._device_of(None))
     if a.dim() not in (1, 2):
         raise ValueError(f"reconstruct_track: audio must be (samples,) or (channels, samples), got {tuple(a.shape)}")
-    mono = a.dim() == 1
-    a2 = (a[None] if mono else a).contiguous()
-    n_ch, a_len = a2.shape
-    T, step, n_clips = track_plan(a_len, frames, hop_length, overlap_frames)
-    bins = n_fft // 2
+    an = _Analysis()
+    an.mono = a.dim() == 1
+    an.a2 = a2 = (a[None] if an.mono else a).contiguous()
+    an.n_ch, an.a_len = n_ch, a_len = a2.shape
+    an.T, an.step, an.n_clips = T, step, n_clips = track_plan(a_len, frames, hop_length, overlap_frames)
+    an.bins = n_fft // 2
     dev = a2.device
     with torch.cuda.device(dev), torch.no_grad():
         # signal order (clip, channel), as preproc.chunk_audio
@@ -76,16 +76,97 @@ def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, over
             ops.standardize_(x)
         else:
             ops.standardize_with_(x, stats[0], stats[1])
-        pol = ops.polar(x)
-        logmag = pol[:, 0]
-        if phase == "unet":
-            ph = torch.empty(n_clips * n_ch, bins, frames, device=dev)
-            for i in range(0, n_clips * n_ch, clip_batch):
-                ph[i:i + clip_batch] = model.forward(logmag[i:i + clip_batch], per_clip=True)[:, :bins]
-        else:
-            ph = pol[:, 1]
-        clips = pg_audio.synthesize(logmag, ph, hop_length, normalize=False)                   # (n_clips * n_ch, T)
-        out, _, bad = ops.stitch(clips.view(n_clips, n_ch, T).transpose(0, 1), step, a_len, normalize=normalize, return_status=True)
+        an.pol = ops.polar(x)
+    return an
+
+
+def _clips(an, model, phase, hop_length, clip_batch, gl_iters=250, gl_seed=0):
+    """Un-normalised clip audio (n_clips * n_ch, T) of one phase source."""
+    logmag = an.pol[:, 0]
+    n_sig, bins, frames = logmag.shape
+    if phase == "griffinlim":
+        n_fft = 2 * bins
+        return pg_audio.griffin_lim_batch(torch.exp(logmag) - 1.0, n_fft, hop_length, gl_iters, seed=gl_seed, normalize=False)[0]
+    if phase == "unet":
+        ph = torch.empty(n_sig, bins, frames, device=logmag.device)
+        for i in range(0, n_sig, clip_batch):
+            ph[i:i + clip_batch] = model.forward(logmag[i:i + clip_batch], per_clip=True)[:, :bins]
+    elif phase == "zero":
+        ph = torch.zeros_like(logmag)
+    else:
+        ph = an.pol[:, 1]
+    return pg_audio.synthesize(logmag, ph, hop_length, normalize=False)
+
+
+def _synthesise(an, model, phase, hop_length, clip_batch, normalize, gl_iters=250, gl_seed=0):
+    """One phase source -> the stitched track (channels, a_len); raises when a sample is not finite."""
+    with torch.cuda.device(an.a2.device), torch.no_grad():
+        clips = _clips(an, model, phase, hop_length, clip_batch, gl_iters, gl_seed)            # (n_clips * n_ch, T)
+        out, _, bad = ops.stitch(clips.view(an.n_clips, an.n_ch, an.T).transpose(0, 1), an.step, an.a_len, normalize=normalize, return_status=True)
         if int(bad.item()) != 0:
             raise ValueError("Audio buffer is not finite everywhere")       # librosa.util.valid_audio's ParameterError
-    return out[0] if mono else out
+    return out
+
+
+def peak_normalize(audio):
+    """utils.py:42 for a whole track on the device: audio (samples,) or (channels, samples) divided by its joint peak -- the second
+    launch of pg_stitch over one clip per channel, so ``peak_normalize(reconstruct_track(..., normalize=False))`` has the bits of
+    ``reconstruct_track(..., normalize=True)``."""
+    a2 = audio[None] if audio.dim() == 1 else audio
+    n = a2.shape[1]
+    with torch.cuda.device(a2.device):
+        out = ops.stitch(a2[:, None, :], n, n, normalize=True)
+    return out[0] if audio.dim() == 1 else out
+
+
+def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None,
+                      osr=None, sr=16000, res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True):
+    """audio (samples,) or (channels, samples), host array or device tensor, at ``sr`` -- or at ``osr`` when given (resampled to
+    ``sr`` first) -> float32 device tensor of the same shape with the a_len samples per channel of the track at ``sr``, its phase
+    predicted by ``model`` (phase="unet"), kept from the analysis (phase="original": the chunk / stitch round trip) or all zero
+    (phase="zero", the reference's "no phase" comparator); ``model`` may be None for the last two.  ``stats`` = (mean, std) of the
+    training set; None: the track's own moments.  ``normalize``: peak-normalise over all channels jointly (utils.py:42 for the whole
+    track).  Raises ValueError("Audio buffer is not finite everywhere") as ``audio.generate_audio`` does."""
+    if phase not in ("unet", "original", "zero"):
+        raise ValueError(f"reconstruct_track: phase must be 'unet', 'original' or 'zero', got {phase!r}")
+    if phase == "unet" and model is None:
+        raise ValueError("reconstruct_track: phase='unet' needs a model")
+    if clip_batch < 1:
+        raise ValueError("reconstruct_track: clip_batch must be positive")
+    an = _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type)
+    out = _synthesise(an, model, phase, hop_length, clip_batch, normalize)
+    return out[0] if an.mono else out
+
+
+def evaluate_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
+                   res_type="kaiser_best", clip_batch=64, phases=("unet", "zero", "original"), gl_iters=250, gl_seed=0, floor=1e-10,
+                   return_audio=False):
+    """The quality report of a track: ONE analysis (as ``reconstruct_track``), then for every entry of ``phases`` -- "unet" (the
+    model's phase), "zero" (none), "original" (the analysis' own: what the chunk / stitch round trip alone costs), "griffinlim"
+    (``audio.griffin_lim_batch`` on exp(logmag) - 1 per clip, ``gl_iters`` iterations from noise seeded ``gl_seed`` + clip index) --
+    the un-normalised stitched track and ``metrics.compare_audio(input at sr, track, n_fft, hop_length, floor)``.
+    -> {"n_samples", "sr", "n_clips", "metrics": {phase: dict}} and, with ``return_audio``, "audio": {phase: device tensor shaped
+    like the input}.  The "unet" audio has the bits of ``reconstruct_track(..., normalize=False)``.  ``model`` may be None when
+    "unet" is not asked for."""
+    phases = tuple(phases)
+    for p in phases:
+        if p not in PHASES:
+            raise ValueError(f"evaluate_track: unknown phase {p!r} (expected some of {PHASES})")
+    if len(set(phases)) != len(phases) or not phases:
+        raise ValueError("evaluate_track: phases must be a non-empty list without repetitions")
+    if "unet" in phases and model is None:
+        raise ValueError("evaluate_track: phase 'unet' needs a model")
+    if clip_batch < 1:
+        raise ValueError("evaluate_track: clip_batch must be positive")
+    an = _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type)
+    ref = an.a2[0] if an.mono else an.a2
+    res = {"n_samples": int(an.a_len), "sr": int(sr), "n_clips": int(an.n_clips), "metrics": {}}
+    if return_audio:
+        res["audio"] = {}
+    for p in phases:
+        out = _synthesise(an, model, p, hop_length, clip_batch, False, gl_iters, gl_seed)
+        out = out[0] if an.mono else out
+        res["metrics"][p] = metrics.compare_audio(ref, out, n_fft, hop_length, floor)
+        if return_audio:
+            res["audio"][p] = out
+    return res

@@ -6,8 +6,15 @@ reference's ``demo.py`` stops at dataset clips; flags shared with it keep its na
 ``--stats`` is the ``{genre}_audio_stats.npy`` that ``phasegen.preproc.build_dataset(..., return_stats=True)`` writes beside the
 training set: the (mean, std) the model's inputs were normalised with.  Without it the track's own moments are used.
 WAV files are written with scipy (float32 PCM), as in ``demo.py``.
+
+``--report PATH`` also measures the result (``phasegen.track.evaluate_track``): SI-SDR, gain-matched SNR, spectral convergence and
+log-spectral distance of the track against the input at ``--sr``, for the model's phase and for the comparators of
+``--report_phases`` (``zero``: no phase at all, ``original``: the analysis' own phase, i.e. what chunking and stitching alone cost,
+``griffinlim``: ``--gl_iters`` Griffin-Lim iterations from noise), written as JSON.  The model still runs once and the wav is the
+same file, byte for byte.
 """
 import argparse
+import json
 import os
 import sys
 import time
@@ -31,6 +38,10 @@ def main():
                         help="MFMA operand mode of the convolutions (pg_conv_args.precision): fp32 = the reference's arithmetic")
     parser.add_argument("--gpu", default=0, type=int)
     parser.add_argument("--stereo", action="store_true", help="keep the file's channels instead of their mono average")
+    parser.add_argument("--report", default=None, metavar="PATH", help="write a JSON quality report of the result against the input")
+    parser.add_argument("--report_phases", default="unet,zero,original",
+                        help="comma list of phase sources to report: unet, zero, original, griffinlim ('unet' is always included)")
+    parser.add_argument("--gl_iters", default=250, type=int, help="Griffin-Lim iterations of the 'griffinlim' report phase")
     args = parser.parse_args()
     n_fft = 2 * args.channels if args.n_fft is None else args.n_fft
     hop = n_fft // 4 if args.hop is None else args.hop
@@ -54,15 +65,34 @@ def main():
         print("reconstruct: no --stats given, normalising with this track's own mean and std", file=sys.stderr)
     audio, file_sr = preproc.load_audio(args.input, mono=not args.stereo)
 
+    phases = [p.strip() for p in args.report_phases.split(",") if p.strip()]
+    if args.report is not None:
+        if "unet" not in phases:
+            phases.insert(0, "unet")
+        for p in phases:
+            if p not in track.PHASES:
+                parser.error(f"--report_phases: unknown phase {p!r} (expected some of {', '.join(track.PHASES)})")
+
     start = time.time()
-    out = track.reconstruct_track(model, audio, n_fft=n_fft, hop_length=hop, frames=args.frames, overlap_frames=args.overlap_frames,
-                                  stats=stats, osr=file_sr, sr=args.sr)
+    kw = dict(n_fft=n_fft, hop_length=hop, frames=args.frames, overlap_frames=args.overlap_frames, stats=stats, osr=file_sr, sr=args.sr)
+    report = None
+    if args.report is None:
+        out = track.reconstruct_track(model, audio, **kw)
+    else:
+        report = track.evaluate_track(model, audio, phases=phases, gl_iters=args.gl_iters, return_audio=True, **kw)
+        out = track.peak_normalize(report.pop("audio")["unet"])
     out = out.cpu().numpy()
     took = time.time() - start
     n = out.shape[-1]
     _, _, n_clips = track.track_plan(n, args.frames, hop, args.overlap_frames)
     wavfile.write(args.output, args.sr, np.ascontiguousarray(out.T if out.ndim == 2 else out, dtype=np.float32))
     print("Reconstructed {:.2f} s of audio in {:.3f} s ({} clips).".format(n / args.sr, took, n_clips))
+    if report is not None:
+        report.update(input=os.path.abspath(args.input), seconds=n / args.sr, flags=vars(args))
+        with open(args.report, "w") as f:
+            json.dump(report, f, indent=1)
+        print("Report: " + "; ".join("{} SI-SDR {:.2f} dB, spectral convergence {:.4f}, LSD {:.2f} dB".format(
+            p, m["si_sdr_db"], m["spectral_convergence"], m["lsd_db"]) for p, m in ((p, report["metrics"].get(p)) for p in ("unet", "zero")) if m))
 
 
 if __name__ == "__main__":
