@@ -240,6 +240,10 @@ typedef struct pg_stft_args {
     const int64_t* chunk_start; const int32_t* chunk_row; int64_t src_len; int64_t src_stride;
 } pg_stft_args;
 int pg_stft(const pg_stft_args* a, void* stream);
+/* The launch plan of a pg_stft call WITHOUT launching it (measurement aid, as pg_conv_describe: the same checks as the call, buf of at
+ * least 128 bytes, pointers non-NULL but not read): one entry per launch in launch order, joined by '|', each
+ * "kernel<template args>,grid=X[xY],block=T,lds=B" with the kernel named as rocprofv3 reports it and B the dynamic LDS bytes. */
+int pg_stft_describe(const pg_stft_args* a, char* buf, int32_t buflen);
 /* The integer framing map alone (bit-exact contract): idx[t, k] = sample index of tap k of frame t. */
 int pg_stft_frame_index(int32_t n_samples, int32_t n_fft, int32_t hop, int32_t n_frames, int32_t* idx, void* stream);
 
@@ -260,6 +264,7 @@ typedef struct pg_istft_args {
 } pg_istft_args;
 int64_t pg_workspace_bytes_istft(const pg_istft_args* a);
 int pg_istft(const pg_istft_args* a, void* stream);
+int pg_istft_describe(const pg_istft_args* a, char* buf, int32_t buflen);   /* launch plan without launching, as pg_stft_describe */
 
 /* Griffin-Lim building blocks (utils.py:112-134).  pg_gl_project: S (2,bins,frames) = [re; im] of the current estimate's
  * STFT and the target magnitudes mag (bins,frames) -> new_spec = mag * exp(j angle(S)) written as (2,bins,frames) to

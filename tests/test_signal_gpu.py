@@ -78,7 +78,9 @@ def test_polar_vs_reference_golden_exact_edges(golden_dir):
     assert np.allclose(mag_only[:, 0], np.expm1(g["output"][:, 0].astype(np.float64)), rtol=1e-5, atol=1e-6)
 
 
-@pytest.mark.parametrize("bins,frames,hop,nsig", [(1024, 128, 512, 2), (512, 256, 256, 2), (16, 24, 8, 3), (32, 9, 16, 1)])
+@pytest.mark.parametrize("bins,frames,hop,nsig", [(1024, 128, 512, 2), (512, 256, 256, 2), (16, 24, 8, 3), (32, 9, 16, 1),
+                                                  (512, 7, 256, 2),      # fused overlap-add, one ragged group: no seam launch, two peak slots per signal
+                                                  (1024, 9, 512, 1)])    # ... two groups, the second of one frame
 def test_istft_vs_oracle(bins, frames, hop, nsig):
     from phasegen import ops
     re = detgen.normal(31, (nsig, bins, frames))

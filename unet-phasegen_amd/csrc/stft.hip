@@ -42,6 +42,27 @@ __device__ __host__ __forceinline__ int reflect_index(int pos, int n) {
 
 __device__ __forceinline__ float hann(int k, int n) { return 0.5f - 0.5f * cospif(2.0f * (float)k / (float)n); }
 
+// Maximum of mx over a workgroup of WAVES waves, returned to every thread (a maximum is exact in any order): shuffle butterfly, one
+// LDS slot per wave, fold.  red[] is free again after the caller's next barrier.
+template <int WAVES> __device__ __forceinline__ float block_max(float mx, float* red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    lds_barrier();
+    mx = red[0];
+#pragma unroll
+    for (int i = 1; i < WAVES; ++i) mx = fmaxf(mx, red[i]);
+    return mx;
+}
+
+// the frames lo .. hi that cover padded position ip of the overlap-add: lo = ceil((ip - N + 1) / hop) and hi = ip / hop, clamped
+struct FrameRange { int lo, hi; };
+__device__ __forceinline__ FrameRange frame_range(int ip, int N, int hop, int n_frames) {
+    int t_hi = ip / hop; if (t_hi > n_frames - 1) t_hi = n_frames - 1;
+    int t_lo = (ip - N + hop) / hop; if (ip - N + 1 <= 0) t_lo = 0;
+    return { t_lo, t_hi };
+}
+
 // In-LDS Stockham radix-2 FFT of length N (power of two).  buf0 holds the input; returns the buffer holding the
 // natural-order output.  tw[i] = exp(-2 pi i / N * i), i < N/2; sign = +1 forward, -1 inverse (conjugate twiddles).
 __device__ float2* fft_lds(float2* buf0, float2* buf1, const float2* tw, int N, float sign) {
@@ -462,11 +483,7 @@ __global__ __launch_bounds__(256) void istft_peak_normalize_kernel(float* audio,
     const int sig = blockIdx.y;
     float mx = 0.f;
     for (int i = threadIdx.x; i < nparts; i += 256) mx = fmaxf(mx, partial[(long)sig * nparts + i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    const float pk = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const float pk = block_max<4>(mx, red);
     if (!(pk > 1.17549435e-38f)) return;
     float* row = audio + (long)sig * len;
     if ((len & 3) == 0 && (((uintptr_t)audio) & 15) == 0) {
@@ -821,6 +838,28 @@ __device__ __forceinline__ void istft_build_w(const pg_istft_args& a, float2 (*r
     }
 }
 
+// this wave's frame: inverse transform of the spectrum in its region `reg`, window, n_fft reals to dst (global memory, or `reg` itself)
+template <int P>
+__device__ __forceinline__ void istft_wave_frame(float2* reg, const float2* T1, const float2* T2, int lane, float cb, float sb, float2* dst) {
+    using W = WaveFft<P>;
+    const float inv = 1.0f / (float)W::M;
+    float2 v[P];
+#pragma unroll
+    for (int r = 0; r < P; ++r) v[r] = reg[lane + 64 * r];
+    wave_order();
+    if (!(PG_W_ABL & 2)) wave_fft<-1>(v, reg, T1, T2, lane);
+    int lo = lane;
+    asm volatile("" : "+v"(lo));                              // (opaque: keeps the store addresses out of the loop-invariant registers)
+    float cbo = cb, sbo = sb;
+    asm volatile("" : "+v"(cbo), "+v"(sbo));                  // (opaque: or the window values are hoisted out of the loop)
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        float w0, w1;
+        hann_pair<P>(cbo, sbo, W::rot_out(r), w0, w1);
+        dst[W::out(lo, r)] = make_float2(v[r].x * (inv * w0), v[r].y * (inv * w1));
+    }
+}
+
 // ISTFT frames, n_fft = 128 P: the workgroup builds the spectra together, then every wave inverts its own frame and stores it
 // windowed, 8 B per lane.  (A prefetch of the next group's rows during the transforms needs 32 more registers than two workgroups per
 // CU leave: measured 151 us at one workgroup per CU with it against 125 us without.)
@@ -836,7 +875,6 @@ __global__ __launch_bounds__(WT, 4) void istft_frames_w_kernel(const pg_istft_ar
     wave_fft_tables<P>(T1, T2);
     float cb, sb, sc, ss, sc2 = 0.f, ss2 = 0.f;               // (cos, sin)(2 pi lane / M): base of the window angles of this lane's outputs
     sincospif(2.0f * (float)lane / (float)M, &sb, &cb);
-    const float inv = 1.0f / (float)M;
     sincospif((float)(1 + (int)(threadIdx.x >> 1)) / (float)M, &ss, &sc);          // exp(+2 pi i k / n_fft) of this thread's bin pairs
     if (M > 512) sincospif((float)(257 + (int)(threadIdx.x >> 1)) / (float)M, &ss2, &sc2);
     const bool vec4 = (a.n_frames & 3) == 0 && ((a.a_bs | a.b_bs) & 3) == 0 && ((((uintptr_t)a.a) | ((uintptr_t)a.b)) & 15) == 0;
@@ -846,24 +884,8 @@ __global__ __launch_bounds__(WT, 4) void istft_frames_w_kernel(const pg_istft_ar
         const int nfr = min(NW, a.n_frames - t0);
         istft_build_w<P>(a, regs, sig, t0, nfr, vec4, sc, ss, sc2, ss2);
         lds_barrier();
-        if (wave < nfr) {
-            float2 v[P];
-#pragma unroll
-            for (int r = 0; r < P; ++r) v[r] = regs[wave][lane + 64 * r];
-            wave_order();
-            if (!(PG_W_ABL & 2)) wave_fft<-1>(v, regs[wave], T1, T2, lane);
-            int lo = lane;
-            asm volatile("" : "+v"(lo));                      // (opaque: keeps the store addresses out of the loop-invariant registers)
-            float2* dst = (float2*)(frames + ((long)sig * a.n_frames + t0 + wave) * N);
-            float cbo = cb, sbo = sb;
-            asm volatile("" : "+v"(cbo), "+v"(sbo));          // (opaque: or the window values are hoisted out of the loop)
-#pragma unroll
-            for (int r = 0; r < P; ++r) {
-                float w0, w1;
-                hann_pair<P>(cbo, sbo, W::rot_out(r), w0, w1);
-                dst[W::out(lo, r)] = make_float2(v[r].x * (inv * w0), v[r].y * (inv * w1));
-            }
-        }
+        if (wave < nfr)
+            istft_wave_frame<P>(regs[wave], T1, T2, lane, cb, sb, (float2*)(frames + ((long)sig * a.n_frames + t0 + wave) * N));
         lds_barrier();
     }
 }
@@ -894,30 +916,37 @@ __device__ __forceinline__ WssCtx wss_ctx(int first_pos, int N, int hop) {
     }
     return c;
 }
+// The squared-window sum of four consecutive samples follows the frames covering them by ROTATING (cos, sin) of the window angle
+// instead of re-evaluating the window: wss_start at the taps n0 .. n0 + 3 the first frame sees, wss_step per frame.
+struct WssRot { float c[4], s[4]; };
+__device__ __forceinline__ WssRot wss_start(int n0, int N, float cd, float sd) {
+    WssRot r;
+    sincospif(2.0f * (float)n0 / (float)N, &r.s[0], &r.c[0]);
+#pragma unroll
+    for (int j = 1; j < 4; ++j) { r.c[j] = r.c[j - 1] * cd - r.s[j - 1] * sd; r.s[j] = r.s[j - 1] * cd + r.c[j - 1] * sd; }
+    return r;
+}
+__device__ __forceinline__ void wss_step(WssRot& r, float (&wss)[4], float ch, float sh) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float w = 0.5f - 0.5f * r.c[j];
+        wss[j] += w * w;
+        const float cn = r.c[j] * ch + r.s[j] * sh;                         // the next frame sees this sample hop taps earlier
+        r.s[j] = r.s[j] * ch - r.c[j] * sh;
+        r.c[j] = cn;
+    }
+}
 // four consecutive output samples at padded position ip (multiple of 4): divide the overlap-added sums by librosa's
 // window_sumsquare over the frames that exist there (utils.py:40, librosa.istft); returns max |y|
 __device__ __forceinline__ float ola_finalize(float4& acc, int ip, int N, int hop, int n_frames, const WssCtx& c) {
-    int t_hi = ip / hop; if (t_hi > n_frames - 1) t_hi = n_frames - 1;
-    int t_lo = (ip - N + hop) / hop; if (ip - N + 1 <= 0) t_lo = 0;
+    const FrameRange fr = frame_range(ip, N, hop, n_frames);
     float wss[4];
-    if (t_hi - t_lo + 1 == N / hop) {                                       // interior: the thread's constants
+    if (fr.hi - fr.lo + 1 == N / hop) {                                     // interior: the thread's constants
         wss[0] = c.iw[0]; wss[1] = c.iw[1]; wss[2] = c.iw[2]; wss[3] = c.iw[3];
     } else {                                                                // ends of the signal: by rotation
-        float cs[4], sn[4];
         wss[0] = wss[1] = wss[2] = wss[3] = 0.f;
-        sincospif(2.0f * (float)(ip - t_lo * hop) / (float)N, &sn[0], &cs[0]);
-#pragma unroll
-        for (int j = 1; j < 4; ++j) { cs[j] = cs[j - 1] * c.cd - sn[j - 1] * c.sd; sn[j] = sn[j - 1] * c.cd + cs[j - 1] * c.sd; }
-        for (int t = t_lo; t <= t_hi; ++t) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float w = 0.5f - 0.5f * cs[j];
-                wss[j] += w * w;
-                const float cn = cs[j] * c.ch + sn[j] * c.sh;               // the next frame sees this sample hop taps earlier
-                sn[j] = sn[j] * c.ch - cs[j] * c.sh;
-                cs[j] = cn;
-            }
-        }
+        WssRot rot = wss_start(ip - fr.lo * hop, N, c.cd, c.sd);
+        for (int t = fr.lo; t <= fr.hi; ++t) wss_step(rot, wss, c.ch, c.sh);
     }
     acc.x = wss[0] > 1.17549435e-38f ? acc.x / wss[0] : acc.x;
     acc.y = wss[1] > 1.17549435e-38f ? acc.y / wss[1] : acc.y;
@@ -927,6 +956,12 @@ __device__ __forceinline__ float ola_finalize(float4& acc, int ip, int N, int ho
 }
 
 // partial[] layout of this path, per signal: [groups] peaks of the main kernel's finalised samples, then [groups] peaks of the seams
+// (ow_parts: what the launch plan reserves per signal and tells the normaliser to fold)
+__host__ __device__ constexpr int ow_parts(int groups) { return 2 * groups; }
+__device__ __forceinline__ float* ow_peak(float* partial, int sig, int groups, bool seam, int grp) {
+    return partial + (long)sig * ow_parts(groups) + (seam ? groups : 0) + grp;
+}
+
 template <int P>
 __global__ __launch_bounds__(WT, 4) void istft_ola_w_kernel(const pg_istft_args a, float* tails, float* partial) {
     using W = WaveFft<P>;
@@ -941,7 +976,6 @@ __global__ __launch_bounds__(WT, 4) void istft_ola_w_kernel(const pg_istft_args 
     wave_fft_tables<P>(T1, T2);
     float cb, sb, sc, ss, sc2 = 0.f, ss2 = 0.f;
     sincospif(2.0f * (float)lane / (float)M, &sb, &cb);
-    const float inv = 1.0f / (float)M;
     sincospif((float)(1 + (int)(threadIdx.x >> 1)) / (float)M, &ss, &sc);
     if (M > 512) sincospif((float)(257 + (int)(threadIdx.x >> 1)) / (float)M, &ss2, &sc2);
     const bool vec4 = (a.n_frames & 3) == 0 && ((a.a_bs | a.b_bs) & 3) == 0 && ((((uintptr_t)a.a) | ((uintptr_t)a.b)) & 15) == 0;
@@ -952,23 +986,7 @@ __global__ __launch_bounds__(WT, 4) void istft_ola_w_kernel(const pg_istft_args 
         const int nfr = min(NW, a.n_frames - t0);
         istft_build_w<P>(a, regs, sig, t0, nfr, vec4, sc, ss, sc2, ss2);
         lds_barrier();
-        if (wave < nfr) {                                     // this wave's frame: inverse transform, window, back to its region as n_fft reals
-            float2 v[P];
-#pragma unroll
-            for (int r = 0; r < P; ++r) v[r] = regs[wave][lane + 64 * r];
-            wave_order();
-            wave_fft<-1>(v, regs[wave], T1, T2, lane);
-            int lo = lane;
-            asm volatile("" : "+v"(lo));
-            float cbo = cb, sbo = sb;
-            asm volatile("" : "+v"(cbo), "+v"(sbo));
-#pragma unroll
-            for (int r = 0; r < P; ++r) {
-                float w0, w1;
-                hann_pair<P>(cbo, sbo, W::rot_out(r), w0, w1);
-                regs[wave][W::out(lo, r)] = make_float2(v[r].x * (inv * w0), v[r].y * (inv * w1));
-            }
-        }
+        if (wave < nfr) istft_wave_frame<P>(regs[wave], T1, T2, lane, cb, sb, regs[wave]);    // back to its region as n_fft reals
         lds_barrier();
         // overlap-add over the group's frames: position pr (relative to t0 hop) gets frame f's sample pr - f hop
         const bool first = grp == 0, last = grp == groups - 1;
@@ -992,14 +1010,10 @@ __global__ __launch_bounds__(WT, 4) void istft_ola_w_kernel(const pg_istft_args 
             mx = fmaxf(mx, ola_finalize(acc, ip, N, hop, a.n_frames, wc));
             *(float4*)(out + i0) = acc;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        if (lane == 0) red[wave] = mx;
-        lds_barrier();                                        // (also: the regions are the next group's work space)
+        mx = block_max<NW>(mx, red);                          // (its barrier also: the regions are the next group's work space)
         if (threadIdx.x == 0) {
-            for (int i = 1; i < NW; ++i) mx = fmaxf(mx, red[i]);
-            partial[(long)sig * 2 * groups + grp] = mx;
-            if (first) partial[(long)sig * 2 * groups + groups] = 0.f;       // group 0 has no seam in front of it
+            *ow_peak(partial, sig, groups, false, grp) = mx;
+            if (first) *ow_peak(partial, sig, groups, true, 0) = 0.f;        // group 0 has no seam in front of it
         }
     }
 }
@@ -1024,11 +1038,8 @@ __global__ __launch_bounds__(256) void istft_seam_kernel(const pg_istft_args a, 
         mx = fmaxf(mx, ola_finalize(acc, ip, N, hop, a.n_frames, wc));
         *(float4*)(out + i0) = acc;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[(long)sig * 2 * groups + groups + grp] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    mx = block_max<4>(mx, red);
+    if (threadIdx.x == 0) *ow_peak(partial, sig, groups, true, grp) = mx;
 }
 
 __global__ void frame_index_kernel(int n_samples, int n_fft, int hop, int n_frames, int* idx) {
@@ -1086,26 +1097,16 @@ __global__ __launch_bounds__(256) void istft_ola4_kernel(const pg_istft_args a, 
         const bool vec = (a.hop & 3) == 0 && N <= 16 * a.hop && i0 + OLA_SPT <= len && (((uintptr_t)a.audio) & 15) == 0;
         if (vec) {                                   // ip, hop, N/2 are multiples of 4: the 4 samples share their frame range
             const int ip = i0 + (N >> 1);
-            int t_hi = ip / a.hop; if (t_hi > a.n_frames - 1) t_hi = a.n_frames - 1;
-            int t_lo = (ip - N + a.hop) / a.hop; if (ip - N + 1 <= 0) t_lo = 0;
-            float sd, cd, sh, ch, c[OLA_SPT], sn[OLA_SPT];
+            const FrameRange fr = frame_range(ip, N, a.hop, a.n_frames);
+            float sd, cd, sh, ch;
             sincospif(2.0f / (float)N, &sd, &cd);
             sincospif(2.0f * (float)a.hop / (float)N, &sh, &ch);
-            sincospif(2.0f * (float)(ip - t_lo * a.hop) / (float)N, &sn[0], &c[0]);
-#pragma unroll
-            for (int j = 1; j < OLA_SPT; ++j) { c[j] = c[j - 1] * cd - sn[j - 1] * sd; sn[j] = sn[j - 1] * cd + c[j - 1] * sd; }
+            WssRot rot = wss_start(ip - fr.lo * a.hop, N, cd, sd);
             float acc[OLA_SPT] = {0.f, 0.f, 0.f, 0.f}, wss[OLA_SPT] = {0.f, 0.f, 0.f, 0.f};
-            for (int t = t_lo; t <= t_hi; ++t) {
+            for (int t = fr.lo; t <= fr.hi; ++t) {
                 const float4 v = *(const float4*)(fs + (long)t * N + (ip - t * a.hop));
                 acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w;
-#pragma unroll
-                for (int j = 0; j < OLA_SPT; ++j) {
-                    const float w = 0.5f - 0.5f * c[j];
-                    wss[j] += w * w;
-                    const float cn = c[j] * ch + sn[j] * sh;             // the next frame sees this sample hop taps earlier
-                    sn[j] = sn[j] * ch - c[j] * sh;
-                    c[j] = cn;
-                }
+                wss_step(rot, wss, ch, sh);
             }
             float y[OLA_SPT];
 #pragma unroll
@@ -1117,10 +1118,9 @@ __global__ __launch_bounds__(256) void istft_ola4_kernel(const pg_istft_args a, 
         } else {
             for (int j = 0; j < OLA_SPT && i0 + j < len; ++j) {
                 const int ip = i0 + j + (N >> 1);
-                int t_hi = ip / a.hop; if (t_hi > a.n_frames - 1) t_hi = a.n_frames - 1;
-                int t_lo = (ip - N + a.hop) / a.hop; if (ip - N + 1 <= 0) t_lo = 0;          // ceil((ip-N+1)/hop), clamped
+                const FrameRange fr = frame_range(ip, N, a.hop, a.n_frames);
                 float sum = 0.f, wss = 0.f;
-                for (int t = t_lo; t <= t_hi; ++t) {
+                for (int t = fr.lo; t <= fr.hi; ++t) {
                     const int n = ip - t * a.hop;
                     const float w = hann(n, N);
                     sum += fs[(long)t * N + n];
@@ -1132,11 +1132,8 @@ __global__ __launch_bounds__(256) void istft_ola4_kernel(const pg_istft_args a, 
             }
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[(long)sig * gridDim.x + blockIdx.x] = fmaxf(fmaxf(scratch[0], scratch[1]), fmaxf(scratch[2], scratch[3]));
+    mx = block_max<4>(mx, scratch);
+    if (threadIdx.x == 0) partial[(long)sig * gridDim.x + blockIdx.x] = mx;
 }
 
 // Griffin-Lim projection onto the target magnitudes: keep the phase of S, impose mag (utils.py:122-124)
@@ -1171,10 +1168,9 @@ __global__ __launch_bounds__(256) void ola_nt_kernel(pg_ola_args a, unsigned* pe
     float mx = 0.f;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < len; i += gridDim.x * blockDim.x) {
         const int ip = i + (N >> 1);
-        int t_hi = ip / a.hop; if (t_hi > a.frames - 1) t_hi = a.frames - 1;
-        int t_lo = (ip - N + a.hop) / a.hop; if (ip - N + 1 <= 0) t_lo = 0;
+        const FrameRange fr = frame_range(ip, N, a.hop, a.frames);
         float s = 0.f, wss = 0.f;
-        for (int t = t_lo; t <= t_hi; ++t) {
+        for (int t = fr.lo; t <= fr.hi; ++t) {
             const int n = ip - t * a.hop;
             const float w = hann(n, N);
             s += a.fr[(long)n * a.frames + t];
@@ -1184,14 +1180,8 @@ __global__ __launch_bounds__(256) void ola_nt_kernel(pg_ola_args a, unsigned* pe
         a.audio[i] = yv;
         mx = fmaxf(mx, fabsf(yv));
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < (int)(blockDim.x >> 6); ++i) mx = fmaxf(mx, scratch[i]);
-        atomicMax(peak, __float_as_uint(mx));
-    }
+    mx = block_max<4>(mx, scratch);                           // (launched with 256 threads)
+    if (threadIdx.x == 0) atomicMax(peak, __float_as_uint(mx));
 }
 
 bool pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
@@ -1204,51 +1194,171 @@ int batched_grid(int total) { const int g = 8 * ((total + 7) / 8), cap = (2 * pg
 // the attribute belongs to (function, CURRENT device): set on every call (a host-side table write), so a process that drives
 // several devices is served too and nothing is cached between calls
 hipError_t batched_lds_ready() {
-    const int lds = (int)batched_lds(BATCHED_MAX_NFFT);
-    hipError_t e = hipFuncSetAttribute((const void*)stft_frames_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)stft_frames_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)istft_frames4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    const int w16 = (int)wave_lds<16>();                     // (the 512-point kernels' 41.5 KB are below the default limit)
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)stft_w_kernel<false, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, w16);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)stft_w_kernel<true, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, w16);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)istft_frames_w_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, w16);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)istft_ola_w_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, w16);
-
+    const int lds = (int)batched_lds(BATCHED_MAX_NFFT), w16 = (int)wave_lds<16>();   // (the 512-point kernels' 41.5 KB are below the default limit)
+    const struct { const void* fn; int lds; } big[] = {
+        {(const void*)stft_frames_kernel<false>, lds}, {(const void*)stft_frames_kernel<true>, lds}, {(const void*)istft_frames4_kernel, lds},
+        {(const void*)stft_w_kernel<false, 16>, w16}, {(const void*)stft_w_kernel<true, 16>, w16},
+        {(const void*)istft_frames_w_kernel<16>, w16}, {(const void*)istft_ola_w_kernel<16>, w16}};
+    hipError_t e = hipSuccess;
+    for (const auto& k : big)
+        if (e == hipSuccess) e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
     return e;
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------------------------------------------
+// Launch plans.  plan_stft / plan_istft are pure functions of the argument struct (sizes, flags, pointer ALIGNMENT: nothing is
+// dereferenced) and of pg_cu_count(); pg_stft / pg_istft execute a plan, pg_*_describe format it, pg_workspace_bytes_istft sizes it.
+// Which inputs need which kernel (tests/test_signal_families.py pins the map):
+//   stft_kernel / istft_frames_kernel   radix-2, one frame per workgroup: n_fft = 4096, and single_frame (the tests' reference schedule)
+//   stft_frames_kernel / istft_frames4  radix-4, four frames per workgroup: n_fft 32 .. 512
+//   stft_w_kernel / istft_frames_w      one wave per frame: n_fft = 1024 (P = 8) and 2048 (P = 16)
+//   istft_ola_w_kernel + istft_seam     overlap-add inside the transform: n_fft 1024 / 2048 at hop = n_fft / 4 into 16 B-aligned audio
+//   istft_ola4_kernel                   overlap-add of a frame workspace: behind every other inverse transform
+enum Kern { STFT_R2, STFT_FRAMES, STFT_W, ISTFT_R2, ISTFT_FRAMES4, ISTFT_FRAMES_W, ISTFT_OLA_W, ISTFT_SEAM, ISTFT_OLA4, ISTFT_NORM };
+struct Launch { Kern k; bool chunked; int P; unsigned gx, gy, block; size_t lds; };    // chunked, P: template arguments; gy = 0: a 1-D grid
+struct StftPlan { Launch l[1]; int n; };
+struct IstftPlan {
+    Launch l[3]; int n;
+    // workspace: [256 B reserved][peak partials: part_per per signal, region padded to 256 B][frames of the three-kernel path / tails of the fused one]
+    int64_t head_bytes, part_off, part_bytes, data_off, data_bytes;
+    int part_per, len;
+};
 
-extern "C" int pg_stft(const pg_stft_args* a, void* stream) {
+// one wave per frame, NW frames per workgroup (78.3 KB of LDS at n_fft 2048: 2 workgroups per CU; 41.5 KB at 1024: 3)
+Launch wave_launch(Kern k, bool chunked, int n_fft, int n_signals, int n_frames) {
+    const int totw = n_signals * ((n_frames + NW - 1) / NW);
+    if (n_fft == 2048) return {k, chunked, 16, (unsigned)wave_grid(totw), 0, WT, wave_lds<16>()};
+    return {k, chunked, 8, (unsigned)wave_grid(totw, 3), 0, WT, wave_lds<8>()};
+}
+size_t radix2_lds(int n_fft) { return (size_t)(2 * n_fft + n_fft / 2) * sizeof(float2); }
+
+int plan_stft(const pg_stft_args* a, StftPlan& pl) {
     if (!a || !a->y || !a->out) return pg_fail(PG_ERR_NULL, "stft: y, out required");
     if (!pow2(a->n_fft) || a->n_fft < 32 || a->n_fft > 4096) return pg_fail(PG_ERR_UNSUPPORTED, "stft: n_fft must be a power of two in [32, 4096]");
     if (a->n_signals <= 0 || a->hop <= 0 || a->n_samples <= a->n_fft / 2) return pg_fail(PG_ERR_SHAPE, "stft: bad sizes (reflect padding needs n_samples > n_fft/2)");
     if (a->n_frames != 1 + a->n_samples / a->hop) return pg_fail(PG_ERR_SHAPE, "stft: n_frames must equal 1 + n_samples / hop");
     if (a->chunk_start && (a->src_len <= 0 || a->src_stride < a->src_len)) return pg_fail(PG_ERR_SHAPE, "stft: chunked source needs 0 < src_len <= src_stride");
     if (!a->chunk_start && a->chunk_row) return pg_fail(PG_ERR_NULL, "stft: chunk_row without chunk_start");
-    hipError_t e = batched_lds_ready();
-    if (e != hipSuccess) return pg_fail((int)e, hipGetErrorString(e));
-    if (a->n_fft <= BATCHED_MAX_NFFT && !a->single_frame) {
-        const int total = a->n_signals * ((a->n_frames + SF - 1) / SF);
-        if (a->n_fft == 2048 || a->n_fft == 1024) {        // one wave per frame (wave_fft), NW frames per workgroup
-            const int totw = a->n_signals * ((a->n_frames + NW - 1) / NW);
-            hipStream_t st = (hipStream_t)stream;
-            if (a->n_fft == 2048) {
-                if (a->chunk_start) hipLaunchKernelGGL((stft_w_kernel<true, 16>), dim3((unsigned)wave_grid(totw)), dim3(WT), wave_lds<16>(), st, *a);
-                else hipLaunchKernelGGL((stft_w_kernel<false, 16>), dim3((unsigned)wave_grid(totw)), dim3(WT), wave_lds<16>(), st, *a);
-            } else {
-                if (a->chunk_start) hipLaunchKernelGGL((stft_w_kernel<true, 8>), dim3((unsigned)wave_grid(totw, 3)), dim3(WT), wave_lds<8>(), st, *a);
-                else hipLaunchKernelGGL((stft_w_kernel<false, 8>), dim3((unsigned)wave_grid(totw, 3)), dim3(WT), wave_lds<8>(), st, *a);
-            }
-        }
-        else if (a->chunk_start) hipLaunchKernelGGL(stft_frames_kernel<true>, dim3((unsigned)batched_grid(total)), dim3(BT), batched_lds(a->n_fft), (hipStream_t)stream, *a);
-        else hipLaunchKernelGGL(stft_frames_kernel<false>, dim3((unsigned)batched_grid(total)), dim3(BT), batched_lds(a->n_fft), (hipStream_t)stream, *a);
+    const bool chunked = a->chunk_start != nullptr;
+    pl.n = 1;
+    if (a->n_fft > BATCHED_MAX_NFFT || a->single_frame)
+        pl.l[0] = {STFT_R2, false, 0, (unsigned)(a->n_signals * a->n_frames), 0, FFT_THREADS, radix2_lds(a->n_fft)};
+    else if (a->n_fft == 2048 || a->n_fft == 1024) pl.l[0] = wave_launch(STFT_W, chunked, a->n_fft, a->n_signals, a->n_frames);
+    else pl.l[0] = {STFT_FRAMES, chunked, 0, (unsigned)batched_grid(a->n_signals * ((a->n_frames + SF - 1) / SF)), 0, BT, batched_lds(a->n_fft)};
+    return PG_OK;
+}
+
+int ola_blocks(const pg_istft_args& a) { return (a.hop * (a.n_frames - 1) + 256 * OLA_SPT - 1) / (256 * OLA_SPT); }
+
+// The launches of a call, and the workspace layout.  The workspace query does not see the audio pointer's alignment, hence not the
+// path, so BOTH regions are the maximum over the two candidates' needs -- at every size, fusable or not: callers cache buffers by
+// that value, which has only ever depended on the sizes -- and the layout is the same whichever path runs.
+IstftPlan plan_istft(const pg_istft_args& a) {
+    const int N = 2 * a.bins, groups = (a.n_frames + NW - 1) / NW;
+    const bool wave = (N == 2048 || N == 1024) && !a.single_frame;
+    // n_fft = 2048 at hop 512 (the reference's defaults, preproc_mdb.py:202-204) or 1024 at 256, 16 B-aligned audio: overlap-add inside
+    // the transform kernel, seams fixed by a second one
+    const bool fused = wave && a.hop * OW_COVER == N && (((uintptr_t)a.audio) & 15) == 0;
+    const struct { int64_t per, data; } need[2] = {       // peak partials per signal, bytes behind them: three-kernel path, fused path
+        {ola_blocks(a), (int64_t)a.n_signals * a.n_frames * 2 * a.bins * (int64_t)sizeof(float)},
+        {ow_parts(groups), (int64_t)a.n_signals * groups * OW_HB * (N / OW_COVER) * (int64_t)sizeof(float)}};
+    IstftPlan pl = {};
+    pl.part_per = (int)need[fused].per;
+    pl.len = a.hop * (a.n_frames - 1);
+    pl.head_bytes = pl.part_off = 256;
+    pl.part_bytes = ((int64_t)a.n_signals * (need[0].per > need[1].per ? need[0].per : need[1].per) * (int64_t)sizeof(float) + 255) / 256 * 256;
+    pl.data_off = pl.part_off + pl.part_bytes;
+    pl.data_bytes = need[0].data > need[1].data ? need[0].data : need[1].data;
+    if (fused) {
+        pl.l[pl.n++] = wave_launch(ISTFT_OLA_W, false, N, a.n_signals, a.n_frames);
+        if (groups > 1) pl.l[pl.n++] = {ISTFT_SEAM, false, 0, (unsigned)(groups - 1), (unsigned)a.n_signals, 256, 0};
     } else {
-        const size_t lds = (size_t)(2 * a->n_fft + a->n_fft / 2) * sizeof(float2);
-        hipLaunchKernelGGL(stft_kernel, dim3((unsigned)(a->n_signals * a->n_frames)), dim3(FFT_THREADS), lds, (hipStream_t)stream, *a);
+        if (wave) pl.l[pl.n++] = wave_launch(ISTFT_FRAMES_W, false, N, a.n_signals, a.n_frames);
+        else if (N <= BATCHED_MAX_NFFT && !a.single_frame)
+            pl.l[pl.n++] = {ISTFT_FRAMES4, false, 0, (unsigned)batched_grid(a.n_signals * ((a.n_frames + SF - 1) / SF)), 0, BT, batched_lds(N)};
+        else pl.l[pl.n++] = {ISTFT_R2, false, 0, (unsigned)(a.n_signals * a.n_frames), 0, FFT_THREADS, radix2_lds(N)};
+        pl.l[pl.n++] = {ISTFT_OLA4, false, 0, (unsigned)ola_blocks(a), (unsigned)a.n_signals, 256, 0};
     }
-    e = hipGetLastError();
-    return e == hipSuccess ? PG_OK : pg_fail((int)e, hipGetErrorString(e));
+    if (a.normalize) {       // the peak over the per-workgroup peaks and the division by it are ONE launch (round 3: two)
+        int bx = (pl.len / 4 + 255) / 256; if (bx > 256) bx = 256; if (bx < 1) bx = 1;
+        pl.l[pl.n++] = {ISTFT_NORM, false, 0, (unsigned)bx, (unsigned)a.n_signals, 256, 0};
+    }
+    return pl;
+}
+
+int plan_istft(const pg_istft_args* a, IstftPlan& pl) {
+    if (!a || !a->a || !a->b || !a->audio || !a->workspace) return pg_fail(PG_ERR_NULL, "istft: a, b, audio, workspace required");
+    const int N = 2 * a->bins;
+    if (!pow2(N) || N < 32 || N > 4096) return pg_fail(PG_ERR_UNSUPPORTED, "istft: 2*bins must be a power of two in [32, 4096]");
+    if (a->n_signals <= 0 || a->n_signals > 64 || a->n_frames < 2 || a->hop <= 0 || a->hop > N) return pg_fail(PG_ERR_SHAPE, "istft: bad sizes (1..64 signals per call)");
+    pl = plan_istft(*a);
+    if (a->workspace_bytes < pl.data_off + pl.data_bytes) return pg_fail(PG_ERR_WORKSPACE, "istft: workspace too small");
+    return PG_OK;
+}
+
+// Launches l of a plan, or with `name` only spells the kernel as a profiler reports it: one switch, so that a described plan names
+// what runs.  s: the STFT call; i, pl: the ISTFT call and its plan.
+#define PG_UNPACK(...) __VA_ARGS__
+#define PG_RUN(args, ...) do { if (name) snprintf(name, 64, "%s", #__VA_ARGS__); \
+                               else hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(l.block), l.lds, st, PG_UNPACK args); } while (0)
+void run(const Launch& l, const pg_stft_args* s, const pg_istft_args* i, const IstftPlan* pl, hipStream_t st, char* name = nullptr) {
+    const dim3 grid(l.gx, l.gy ? l.gy : 1);
+    float* partial = pl ? (float*)((char*)i->workspace + pl->part_off) : nullptr;
+    float* data = pl ? (float*)((char*)i->workspace + pl->data_off) : nullptr;          // frames, or tails
+    switch (l.k) {
+    case STFT_R2: PG_RUN((*s), stft_kernel); break;
+    case STFT_FRAMES: if (l.chunked) PG_RUN((*s), stft_frames_kernel<true>); else PG_RUN((*s), stft_frames_kernel<false>); break;
+    case STFT_W:
+        if (l.P == 16) { if (l.chunked) PG_RUN((*s), stft_w_kernel<true, 16>); else PG_RUN((*s), stft_w_kernel<false, 16>); }
+        else { if (l.chunked) PG_RUN((*s), stft_w_kernel<true, 8>); else PG_RUN((*s), stft_w_kernel<false, 8>); }
+        break;
+    case ISTFT_R2: PG_RUN((*i, data), istft_frames_kernel); break;
+    case ISTFT_FRAMES4: PG_RUN((*i, data), istft_frames4_kernel); break;
+    case ISTFT_FRAMES_W: if (l.P == 16) PG_RUN((*i, data), istft_frames_w_kernel<16>); else PG_RUN((*i, data), istft_frames_w_kernel<8>); break;
+    case ISTFT_OLA_W: if (l.P == 16) PG_RUN((*i, data, partial), istft_ola_w_kernel<16>); else PG_RUN((*i, data, partial), istft_ola_w_kernel<8>); break;
+    case ISTFT_SEAM: PG_RUN((*i, (const float*)data, partial), istft_seam_kernel); break;
+    case ISTFT_OLA4: PG_RUN((*i, (const float*)data, partial), istft_ola4_kernel); break;
+    case ISTFT_NORM: PG_RUN((i->audio, pl->len, (const float*)partial, pl->part_per), istft_peak_normalize_kernel); break;
+    }
+}
+#undef PG_RUN
+#undef PG_UNPACK
+
+// "kernel<template args>,grid=X[xY],block=T,lds=B" per launch, in launch order, joined by '|'
+void describe(const Launch* l, int n, const pg_stft_args* s, const pg_istft_args* i, const IstftPlan* pl, char* buf, int buflen) {
+    int at = 0;
+    for (int k = 0; k < n && at < buflen - 1; ++k) {
+        char name[64], gy[16] = "";
+        run(l[k], s, i, pl, nullptr, name);
+        if (l[k].gy) snprintf(gy, sizeof(gy), "x%u", l[k].gy);
+        at += snprintf(buf + at, (size_t)(buflen - at), "%s%s,grid=%u%s,block=%u,lds=%zu", k ? "|" : "", name, l[k].gx, gy, l[k].block, l[k].lds);
+    }
+}
+
+int launched() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? PG_OK : pg_fail((int)e, hipGetErrorString(e)); }
+
+int execute(const Launch* l, int n, const pg_stft_args* s, const pg_istft_args* i, const IstftPlan* pl, void* stream) {
+    const hipError_t e = batched_lds_ready();
+    if (e != hipSuccess) return pg_fail((int)e, hipGetErrorString(e));
+    for (int k = 0; k < n; ++k) run(l[k], s, i, pl, (hipStream_t)stream);
+    return launched();
+}
+
+}  // namespace
+
+extern "C" int pg_stft(const pg_stft_args* a, void* stream) {
+    StftPlan pl;
+    if (int e = plan_stft(a, pl)) return e;
+    return execute(pl.l, pl.n, a, nullptr, nullptr, stream);
+}
+
+// launch plan of a pg_stft call without launching it (as pg_conv_describe; pointers must be non-NULL, they are not read)
+extern "C" int pg_stft_describe(const pg_stft_args* a, char* buf, int32_t buflen) {
+    if (!buf || buflen < 128) return pg_fail(PG_ERR_NULL, "stft_describe: buf of >= 128 bytes required");
+    StftPlan pl;
+    if (int e = plan_stft(a, pl)) return e;
+    describe(pl.l, pl.n, a, nullptr, nullptr, buf, buflen);
+    return PG_OK;
 }
 
 extern "C" int pg_stft_frame_index(int32_t n_samples, int32_t n_fft, int32_t hop, int32_t n_frames, int32_t* idx, void* stream) {
@@ -1256,63 +1366,28 @@ extern "C" int pg_stft_frame_index(int32_t n_samples, int32_t n_fft, int32_t hop
     if (n_samples <= 0 || n_fft <= 0 || hop <= 0 || n_frames <= 0) return pg_fail(PG_ERR_SHAPE, "stft_frame_index: bad sizes");
     long blocks = ((long)n_frames * n_fft + 255) / 256; if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(frame_index_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_samples, n_fft, hop, n_frames, idx);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PG_OK : pg_fail((int)e, hipGetErrorString(e));
-}
-
-static int ola_blocks(const pg_istft_args* a) { return (a->hop * (a->n_frames - 1) + 256 * OLA_SPT - 1) / (256 * OLA_SPT); }
-static int64_t ola_partial_bytes(const pg_istft_args* a) {      // per-workgroup peaks: the overlap-add kernel's blocks, or (n_fft = 2048 at
-    const int64_t per = ola_blocks(a) > 2 * ((a->n_frames + 7) / 8) ? ola_blocks(a) : 2 * ((a->n_frames + 7) / 8);   // hop 512) 2 x groups
-    const int64_t b = (int64_t)a->n_signals * per * (int64_t)sizeof(float);
-    return (b + 255) / 256 * 256;
+    return launched();
 }
 
 extern "C" int64_t pg_workspace_bytes_istft(const pg_istft_args* a) {
     if (!a) return 0;
-    // [256 B reserved][per-workgroup peaks of the overlap-add, padded to 256 B][frames]
-    return 256 + ola_partial_bytes(a) + (int64_t)a->n_signals * a->n_frames * 2 * a->bins * (int64_t)sizeof(float);
+    const IstftPlan pl = plan_istft(*a);
+    return pl.data_off + pl.data_bytes;
 }
 
 extern "C" int pg_istft(const pg_istft_args* a, void* stream) {
-    if (!a || !a->a || !a->b || !a->audio || !a->workspace) return pg_fail(PG_ERR_NULL, "istft: a, b, audio, workspace required");
-    const int N = 2 * a->bins;
-    if (!pow2(N) || N < 32 || N > 4096) return pg_fail(PG_ERR_UNSUPPORTED, "istft: 2*bins must be a power of two in [32, 4096]");
-    if (a->n_signals <= 0 || a->n_signals > 64 || a->n_frames < 2 || a->hop <= 0 || a->hop > N) return pg_fail(PG_ERR_SHAPE, "istft: bad sizes (1..64 signals per call)");
-    if (a->workspace_bytes < pg_workspace_bytes_istft(a)) return pg_fail(PG_ERR_WORKSPACE, "istft: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float* partial = (float*)((char*)a->workspace + 256);
-    float* frames = (float*)((char*)a->workspace + 256 + ola_partial_bytes(a));
-    hipError_t e;
-    if ((e = batched_lds_ready()) != hipSuccess) return pg_fail((int)e, hipGetErrorString(e));
-    const int len = a->hop * (a->n_frames - 1);
-    int bx = (len / 4 + 255) / 256; if (bx > 256) bx = 256; if (bx < 1) bx = 1;
-    // n_fft = 2048 at hop 512 (the reference's defaults, preproc_mdb.py:202-204) or 1024 at 256, 16 B-aligned audio: overlap-add inside the transform
-    // kernel, seams fixed by a second one; the workspace holds [256 B][2 x groups peaks per signal][tails]
-    if ((N == 2048 || N == 1024) && a->hop * OW_COVER == N && !a->single_frame && (((uintptr_t)a->audio) & 15) == 0) {
-        const int groups = (a->n_frames + NW - 1) / NW;
-        float* tails = (float*)((char*)a->workspace + 256 + ola_partial_bytes(a));
-        if (N == 2048) hipLaunchKernelGGL(istft_ola_w_kernel<16>, dim3((unsigned)wave_grid(a->n_signals * groups)), dim3(WT), wave_lds<16>(), st, *a, tails, partial);
-        else hipLaunchKernelGGL(istft_ola_w_kernel<8>, dim3((unsigned)wave_grid(a->n_signals * groups, 3)), dim3(WT), wave_lds<8>(), st, *a, tails, partial);
-        if (groups > 1) hipLaunchKernelGGL(istft_seam_kernel, dim3(groups - 1, a->n_signals), dim3(256), 0, st, *a, (const float*)tails, partial);
-        if (a->normalize) hipLaunchKernelGGL(istft_peak_normalize_kernel, dim3(bx, a->n_signals), dim3(256), 0, st, a->audio, len, (const float*)partial, 2 * groups);
-        e = hipGetLastError();
-        return e == hipSuccess ? PG_OK : pg_fail((int)e, hipGetErrorString(e));
-    }
-    if (N <= BATCHED_MAX_NFFT && !a->single_frame) {
-        const int total = a->n_signals * ((a->n_frames + SF - 1) / SF);
-        if (N == 2048) hipLaunchKernelGGL(istft_frames_w_kernel<16>, dim3((unsigned)wave_grid(a->n_signals * ((a->n_frames + NW - 1) / NW))), dim3(WT), wave_lds<16>(), st, *a, frames);
-        else if (N == 1024) hipLaunchKernelGGL(istft_frames_w_kernel<8>, dim3((unsigned)wave_grid(a->n_signals * ((a->n_frames + NW - 1) / NW), 3)), dim3(WT), wave_lds<8>(), st, *a, frames);
-        else hipLaunchKernelGGL(istft_frames4_kernel, dim3((unsigned)batched_grid(total)), dim3(BT), batched_lds(N), st, *a, frames);
-    } else {
-        const size_t lds = (size_t)(2 * N + N / 2) * sizeof(float2);
-        hipLaunchKernelGGL(istft_frames_kernel, dim3((unsigned)(a->n_signals * a->n_frames)), dim3(FFT_THREADS), lds, st, *a, frames);
-    }
-    const int nblk = ola_blocks(a);
-    hipLaunchKernelGGL(istft_ola4_kernel, dim3(nblk, a->n_signals), dim3(256), 0, st, *a, (const float*)frames, partial);
-    // the peak over the overlap-add's per-workgroup peaks and the division by it are ONE launch (round 3: two)
-    if (a->normalize) hipLaunchKernelGGL(istft_peak_normalize_kernel, dim3(bx, a->n_signals), dim3(256), 0, st, a->audio, len, (const float*)partial, nblk);
-    e = hipGetLastError();
-    return e == hipSuccess ? PG_OK : pg_fail((int)e, hipGetErrorString(e));
+    IstftPlan pl;
+    if (int e = plan_istft(a, pl)) return e;
+    return execute(pl.l, pl.n, nullptr, a, &pl, stream);
+}
+
+// launch plan of a pg_istft call without launching it (as pg_stft_describe)
+extern "C" int pg_istft_describe(const pg_istft_args* a, char* buf, int32_t buflen) {
+    if (!buf || buflen < 128) return pg_fail(PG_ERR_NULL, "istft_describe: buf of >= 128 bytes required");
+    IstftPlan pl;
+    if (int e = plan_istft(a, pl)) return e;
+    describe(pl.l, pl.n, nullptr, a, &pl, buf, buflen);
+    return PG_OK;
 }
 
 extern "C" int pg_gl_project(const pg_gl_args* a, void* stream) {
@@ -1321,8 +1396,7 @@ extern "C" int pg_gl_project(const pg_gl_args* a, void* stream) {
     const unsigned n = a->n ? (unsigned)a->n : 1u;          // n = 0: one clip (the v0.2 layout of the struct)
     long blocks = ((long)a->bins * a->frames + 255) / 256; if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(gl_project_kernel, dim3((unsigned)blocks, n), dim3(256), 0, (hipStream_t)stream, *a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PG_OK : pg_fail((int)e, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int pg_ola_nt(const pg_ola_args* a, void* stream) {
@@ -1339,6 +1413,5 @@ extern "C" int pg_ola_nt(const pg_ola_args* a, void* stream) {
     int bx = (len + 255) / 256; if (bx > 1024) bx = 1024;
     hipLaunchKernelGGL(ola_nt_kernel, dim3(bx, n), dim3(256), 0, st, *a, peak);
     if (a->normalize) hipLaunchKernelGGL(istft_peak_normalize_kernel, dim3(bx > 256 ? 256 : bx, n), dim3(256), 0, st, a->audio, len, (const float*)peak, 1);
-    e = hipGetLastError();
-    return e == hipSuccess ? PG_OK : pg_fail((int)e, hipGetErrorString(e));
+    return launched();
 }

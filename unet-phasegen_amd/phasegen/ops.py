@@ -609,12 +609,8 @@ def fill(t, value):
     return t
 
 
-def stft(y, n_fft, hop, polar=False, out=None, single_frame=None, chunk_start=None, chunk_row=None, chunk_len=None):
-    """(n_signals, n_samples) -> (n_signals, 2, n_fft/2, 1 + n_samples // hop); preproc_mdb.py:84-97 (+ data.py:39-47).
-
-    Chunked source (preproc_mdb.py:66-97): with ``chunk_start`` (int64 device tensor) signal s is the ``chunk_len`` samples of
-    row ``chunk_row[s]`` (int32 device tensor; default row 0) of y (rows, samples) that begin at chunk_start[s]; samples past
-    the end of the row read as zero -- no gathered or zero-padded copy of the audio is made."""
+def _stft_args(y, n_fft, hop, polar=False, out=None, single_frame=None, chunk_start=None, chunk_row=None, chunk_len=None):
+    """The pg_stft_args of one ops.stft call and the tensor it fills."""
     if y.dim() == 1:
         y = y[None]
     a = _lib.StftArgs()
@@ -637,8 +633,29 @@ def stft(y, n_fft, hop, polar=False, out=None, single_frame=None, chunk_start=No
     a.n_signals, a.n_samples, a.n_fft, a.hop, a.n_frames, a.polar = n_sig, n_samp, n_fft, hop, nf, int(polar)
     a.single_frame = _tls.stft_single if single_frame is None else int(bool(single_frame))
     a.y, a.out = _dense(y, "y"), _dense(out, "out")
+    return a, out
+
+
+def stft(y, n_fft, hop, polar=False, out=None, single_frame=None, chunk_start=None, chunk_row=None, chunk_len=None):
+    """(n_signals, n_samples) -> (n_signals, 2, n_fft/2, 1 + n_samples // hop); preproc_mdb.py:84-97 (+ data.py:39-47).
+
+    Chunked source (preproc_mdb.py:66-97): with ``chunk_start`` (int64 device tensor) signal s is the ``chunk_len`` samples of
+    row ``chunk_row[s]`` (int32 device tensor; default row 0) of y (rows, samples) that begin at chunk_start[s]; samples past
+    the end of the row read as zero -- no gathered or zero-padded copy of the audio is made."""
+    a, out = _stft_args(y, n_fft, hop, polar, out, single_frame, chunk_start, chunk_row, chunk_len)
     _lib.check(_lib.load().pg_stft(C.byref(a), _stream()), "stft")
     return out
+
+
+def _describe(fn, a, what):
+    buf = C.create_string_buffer(256)
+    _lib.check(fn(C.byref(a), buf, 256), what)
+    return buf.value.decode()
+
+
+def stft_describe(*args, **kw):
+    """pg_stft_describe for the arguments of ``stft``: 'kernel<...>,grid=G,block=T,lds=B' of the launch the call would make."""
+    return _describe(_lib.load().pg_stft_describe, _stft_args(*args, **kw)[0], "stft_describe")
 
 
 _RES_TYPES = {"kaiser_best": _lib.RS_KAISER_BEST, "kaiser_fast": _lib.RS_KAISER_FAST,
@@ -935,12 +952,10 @@ _istft_ws = _StreamCache()
 _caches.append(_istft_ws)
 
 
-def istft(a_t, b_t, hop, mode=0, normalize=True, single_frame=None):
-    """(n, bins, frames) x2 -> (n, hop*(frames-1)).  mode 0: (logmag, phase) per demo.py:39; mode 1: (re, im).
-    utils.py:34-42: zero DC row, librosa.istft, peak normalisation."""
+def _istft_calls(a_t, b_t, audio, hop, mode, normalize, single_frame):
+    """The pg_istft_args of ops.istft's calls, one per 64 signals, each with its workspace attached (yielded one at a time: the
+    workspace is the stream's cached buffer)."""
     n, bins, nf = a_t.shape
-    audio = torch.empty(n, hop * (nf - 1), device=a_t.device, dtype=torch.float32)
-    lib = _lib.load()
     for s0 in range(0, n, 64):
         s1 = min(n, s0 + 64)
         a = _lib.IstftArgs()
@@ -949,11 +964,28 @@ def istft(a_t, b_t, hop, mode=0, normalize=True, single_frame=None):
         a.a, a.a_bs = _act3(a_t[s0:s1], "a")
         a.b, a.b_bs = _act3(b_t[s0:s1], "b")
         a.audio = audio[s0:s1].data_ptr()
-        need = lib.pg_workspace_bytes_istft(C.byref(a))
+        need = _lib.load().pg_workspace_bytes_istft(C.byref(a))
         ws = _istft_ws.get(a_t.device, lambda: need, need)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        _lib.check(lib.pg_istft(C.byref(a), _stream()), "istft")
+        yield a
+
+
+def istft(a_t, b_t, hop, mode=0, normalize=True, single_frame=None):
+    """(n, bins, frames) x2 -> (n, hop*(frames-1)).  mode 0: (logmag, phase) per demo.py:39; mode 1: (re, im).
+    utils.py:34-42: zero DC row, librosa.istft, peak normalisation."""
+    n, bins, nf = a_t.shape
+    audio = torch.empty(n, hop * (nf - 1), device=a_t.device, dtype=torch.float32)
+    for a in _istft_calls(a_t, b_t, audio, hop, mode, normalize, single_frame):
+        _lib.check(_lib.load().pg_istft(C.byref(a), _stream()), "istft")
     return audio
+
+
+def istft_describe(a_t, b_t, hop, mode=0, normalize=True, single_frame=None):
+    """pg_istft_describe for the arguments of ``istft``: one string per call (64 signals each), its launches joined by '|'."""
+    n, bins, nf = a_t.shape
+    audio = torch.empty(n, hop * (nf - 1), device=a_t.device, dtype=torch.float32)
+    return [_describe(_lib.load().pg_istft_describe, a, "istft_describe")
+            for a in _istft_calls(a_t, b_t, audio, hop, mode, normalize, single_frame)]
 
 
 def gl_project(S, mag, x, spec_out=None):
