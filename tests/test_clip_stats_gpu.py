@@ -105,6 +105,27 @@ def test_kernel_writes_concat_half_with_second_activated_output():
         assert torch.equal(cat[:, C:], y)                # where the output lives does not change a bit of it
 
 
+@pytest.mark.parametrize("shape", [(3, 24, 61), (3, 24, 128)], ids=["scalar-units", "16-byte-units"])
+def test_kernel_writes_all_four_outputs_at_once(shape):
+    """y, y2, yh and yh2 of ONE call, each with another activation: every output against float64, the bf16 copies the bit-exact
+    rounding of the activated fp32 values of the same call (y is stored unactivated, so they can be recomputed from it)."""
+    from phasegen import ops
+    B, C, L = shape
+    x, gamma, beta = inputs(B, C, L, seed=5)
+    y, y2 = torch.full((B, C, L), float("nan"), device="cuda"), torch.full((B, C, L), float("nan"), device="cuda")
+    yh, yh2 = ops.h_alloc(B, C, L, "cuda").fill_(-7.0), ops.h_alloc(B, C, L, "cuda").fill_(-7.0)
+    ops.clipnorm_fwd(x, y, gamma, beta, y_act=ops.ACT_NONE, y2=y2, y2_act=ops.ACT_RELU, yh=yh, yh_act=ops.ACT_LEAKY, yh2=yh2, yh2_act=ops.ACT_RELU)
+    want, _, _ = expected64(x, gamma, beta)
+    e = (rel(y, want), rel(y2, act64(want, ops.ACT_RELU)), rel(yh[:, :, :L], act64(want, ops.ACT_LEAKY)), rel(yh2[:, :, :L], act64(want, ops.ACT_RELU)))
+    print(f"\nclipnorm four outputs {shape}: y {e[0]:.2e} y2 {e[1]:.2e} (bound {TOL:g}); yh {e[2]:.2e} yh2 {e[3]:.2e} (+ one bf16 rounding, 2^-8)")
+    assert max(e[:2]) < TOL and max(e[2:]) < TOL + 2.0 ** -8
+    yc, y2c = y.cpu(), y2.cpu()
+    assert torch.equal(y2c, F.relu(yc))
+    assert torch.equal(yh[:, :, :L].cpu().view(torch.int16), F.leaky_relu(yc, 0.2).to(torch.bfloat16).view(torch.int16))
+    assert torch.equal(yh2[:, :, :L].cpu().view(torch.int16), y2c.to(torch.bfloat16).view(torch.int16))
+    assert yh.shape[2] > L and bool((yh[:, :, L:] == -7.0).all()) and bool((yh2[:, :, L:] == -7.0).all())
+
+
 @pytest.mark.parametrize("shape", SHAPES)
 def test_batch_invariance_is_bitwise(shape):
     B, C, L = shape

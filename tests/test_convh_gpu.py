@@ -140,21 +140,30 @@ def test_activation_without_the_zero_head_is_refused():
     torch.cuda.synchronize()
 
 
-def test_bn_fwd_bf16_outputs():
+# (L, bf16 row pitch; None = ops.h_alloc's): scalar units; 8-byte loads with scalar stores; 16-byte loads with 8-byte bf16 stores;
+# the same L forced back to scalar stores by a pitch that is no multiple of 4 (BatchNorm's unit width sets the order of the channel
+# sums, so that case's fp32 result is NOT bit-identical to the 16-byte one -- it never was --: every case is checked by value)
+@pytest.mark.parametrize("L,pitch", [(61, None), (62, None), (64, None), (64, 66)], ids=["L61", "L62", "L64", "L64-pitch66"])
+def test_bn_fwd_bf16_outputs(L, pitch):
     from phasegen import ops
-    B, Cc, L = 5, 24, 61
+    B, Cc = 5, 24
     x = rnd(21, B, Cc, L)
     gamma, beta = rnd(22, Cc) + 1.5, rnd(23, Cc)
     y = torch.empty(B, Cc, L, device="cuda")
-    yh, yh2 = ops.h_alloc(B, Cc, L, "cuda"), ops.h_alloc(B, Cc, L, "cuda")
+
+    def bf16_rows():                                        # sentinel-filled: the row tails [L, pitch) must come back untouched
+        t = ops.h_alloc(B, Cc, L, "cuda") if pitch is None else torch.zeros(B, Cc, pitch, device="cuda", dtype=torch.bfloat16)
+        return t.fill_(-7.0)
+    yh, yh2 = bf16_rows(), bf16_rows()
     sm, si = torch.empty(Cc, device="cuda"), torch.empty(Cc, device="cuda")
     ops.bn_fwd(x.cuda(), y, gamma.cuda(), beta.cuda(), sm, si, yh=yh, yh_act=ops.ACT_LEAKY, yh2=yh2, yh2_act=ops.ACT_RELU)
     want = F.batch_norm(x, None, None, gamma, beta, True, 0.1, 1e-5)
     assert relerr(y, want) < 1e-5
-    assert torch.equal(yh[:, :, :L].cpu(), F.leaky_relu(y.cpu(), 0.2).to(torch.bfloat16)) and float(yh[:, :, L:].abs().max()) == 0.0
+    assert torch.equal(yh[:, :, :L].cpu(), F.leaky_relu(y.cpu(), 0.2).to(torch.bfloat16))
     assert torch.equal(yh2[:, :, :L].cpu(), F.relu(y.cpu()).to(torch.bfloat16))
+    assert yh.shape[2] > L and bool((yh[:, :, L:] == -7.0).all()) and bool((yh2[:, :, L:] == -7.0).all())
     ops.bn_fwd(x.cuda(), None, gamma.cuda(), beta.cuda(), sm, si, yh=yh2)                # bf16 output only
-    assert torch.equal(yh2[:, :, :L].cpu(), y.cpu().to(torch.bfloat16))
+    assert torch.equal(yh2[:, :, :L].cpu(), y.cpu().to(torch.bfloat16)) and bool((yh2[:, :, L:] == -7.0).all())
 
 
 @pytest.mark.parametrize("C,L,B", [(16, 64, 3), (32, 128, 2), (1024, 256, 4)], ids=["C16", "C32", "C1024-L256-B4"])

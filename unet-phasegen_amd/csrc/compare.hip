@@ -41,8 +41,6 @@ constexpr int SC_FRAMES = 256;             // frames per workgroup of pg_spec_co
 constexpr int SC_WBINS = 16;               // bins per wave
 constexpr int SC_BINS = 4 * SC_WBINS;      // bins per workgroup
 
-typedef float cf4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ bool cmp_finite(float v) { return fabsf(v) <= FLT_MAX; }      // (false for NaN and inf)
 
 // Block-wide fold of six values; with MAX4 slot 4 is a maximum, else a sum.  Thread 0's copy is the result (every thread gets it).
@@ -89,7 +87,7 @@ __global__ __launch_bounds__(CMP_THREADS) void wave_compare_kernel(const WcKerne
         if (t < a.n) {
             float xv[4], yv[4];
             if (VEC == 4 && t + 4 <= a.n) {
-                const cf4 X = *(const cf4*)(xp + t), Y = *(const cf4*)(yp + t);
+                const f32x4 X = *(const f32x4*)(xp + t), Y = *(const f32x4*)(yp + t);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { xv[j] = X[j]; yv[j] = Y[j]; }
             } else {
@@ -179,8 +177,8 @@ __global__ __launch_bounds__(CMP_THREADS) void spec_compare_kernel(const ScKerne
             const long o = (long)b * a.frames + f;
             float rr[4], ri[4], er[4], ei[4];
             if (VEC == 4 && nf >= 4) {
-                const cf4 A = *(const cf4*)(Rp + o), B = *(const cf4*)(Rp + a.plane + o);
-                const cf4 C = *(const cf4*)(Ep + o), D = *(const cf4*)(Ep + a.plane + o);
+                const f32x4 A = *(const f32x4*)(Rp + o), B = *(const f32x4*)(Rp + a.plane + o);
+                const f32x4 C = *(const f32x4*)(Ep + o), D = *(const f32x4*)(Ep + a.plane + o);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { rr[j] = A[j]; ri[j] = B[j]; er[j] = C[j]; ei[j] = D[j]; }
             } else {

@@ -62,15 +62,9 @@ constexpr int STAGE = TILE_A + TILE_B;    // one LDS stage; two stages = 48 KB
 constexpr int AE = BM / 16;               // dword gather pieces per thread and slab for the A tile (B tile: 8)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Activations are applied branch-free on the MFMA fragments as max(v, slope*v) -- exact for 0 <= slope <= 1:
-// slope 1 = identity, 0.2 = LeakyReLU(0.2) (model.py:80), 0 = ReLU (model.py:82).  A runtime switch per element would
+// Activations are applied on the MFMA fragments (pg_act_slope / pg_act_apply, pg_common.h).  A runtime switch per element would
 // make hipcc branch around every gathered value; callers test `slope != 1` once per slab (wave-uniform).
-__host__ __device__ __forceinline__ float act_slope(int act) {
-    return act == PG_ACT_LEAKY02 ? 0.2f : (act == PG_ACT_RELU ? 0.0f : 1.0f);
-}
-__device__ __forceinline__ float act_apply(float v, float slope) { return fmaxf(v, slope * v); }
 
 // Operand gathers go through buffer descriptors: a lane whose element is padding / out of the tile / past K gets
 // the offset OOB and the hardware returns 0.0 -- no exec-masked branch around the load, no 64-bit address math.
@@ -243,7 +237,7 @@ __device__ __forceinline__ void mma_slab(const float* __restrict__ As, const flo
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int v = 0; v < 4; ++v) a[i][c][v] = act_apply(a[i][c][v], slopeA);
+                for (int v = 0; v < 4; ++v) a[i][c][v] = pg_act_apply(a[i][c][v], slopeA);
     }
     if (slopeB != 1.0f) {
 #pragma unroll
@@ -251,7 +245,7 @@ __device__ __forceinline__ void mma_slab(const float* __restrict__ As, const flo
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int v = 0; v < 4; ++v) b[i][c][v] = act_apply(b[i][c][v], slopeB);
+                for (int v = 0; v < 4; ++v) b[i][c][v] = pg_act_apply(b[i][c][v], slopeB);
     }
     if (BF) {
         float af[WMB][8], bf[2][8];
@@ -276,7 +270,7 @@ struct Epi {
     __device__ __forceinline__ Epi(const IgemmParams& p, unsigned ybytes)
         : radd(make_rsrc(p.add, p.add ? ybytes_of(p.add_bs, p, ybytes) : 0u)),
           rref(make_rsrc(p.ref, (p.ref && p.mask_mode) ? ybytes_of(p.ref_bs, p, ybytes) : 0u)),
-          slope((p.ref && p.mask_mode) ? act_slope(p.mask_mode) : 1.0f), fused(p.add || (p.ref && p.mask_mode)) {}
+          slope((p.ref && p.mask_mode) ? pg_act_slope(p.mask_mode) : 1.0f), fused(p.add || (p.ref && p.mask_mode)) {}
     static __device__ __forceinline__ unsigned ybytes_of(long bs, const IgemmParams& p, unsigned ybytes) {
         return (unsigned)(((long)(p.B - 1) * bs) * 4) + ybytes;
     }
@@ -342,12 +336,10 @@ __device__ __forceinline__ void store_partial(float* ws, int g, int slot, const 
             }
 }
 
-// fp32 -> bf16, round to nearest even (a plain cast: hipcc emits v_cvt_pk_bf16_f32, NaN stays NaN)
-__device__ __forceinline__ unsigned short bf16_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
 // bf16 copies of a forward result (B, M, pitch), stored activated: what the bf16-resident kernels of the next layer read
 __device__ __forceinline__ void store_h(const IgemmParams& p, int b, int m, int t, float v) {
-    if (p.yh) p.yh[(long)b * p.yh_bs + (long)m * p.yh_pitch + t] = bf16_bits(act_apply(v, p.yh_slope));
-    if (p.yh2) p.yh2[(long)b * p.yh2_bs + (long)m * p.yh2_pitch + t] = bf16_bits(act_apply(v, p.yh2_slope));
+    if (p.yh) p.yh[(long)b * p.yh_bs + (long)m * p.yh_pitch + t] = pg_bf16_bits(pg_act_apply(v, p.yh_slope));
+    if (p.yh2) p.yh2[(long)b * p.yh2_bs + (long)m * p.yh2_pitch + t] = pg_bf16_bits(pg_act_apply(v, p.yh2_slope));
 }
 
 // ---- epilogues (shared by the GEMM kernels and the fixup kernels) -------------------------------------------------
@@ -372,8 +364,8 @@ __device__ __forceinline__ void epilogue_f(const IgemmParams& p, const AccT<MB, 
                     const int off = m * p.Ly + t;
                     float v = acc.c[i][j][r];
                     if (ep.fused) v = ep(v, b * (int)p.add_bs + off, b * (int)p.ref_bs + off);
-                    if (p.y) yb[off] = act_apply(v, p.y_slope);
-                    if (p.y2) p.y2[(long)b * p.y2_bs + off] = act_apply(v, p.y2_slope);
+                    if (p.y) yb[off] = pg_act_apply(v, p.y_slope);
+                    if (p.y2) p.y2[(long)b * p.y2_bs + off] = pg_act_apply(v, p.y2_slope);
                     store_h(p, b, m, t, v);
                 }
             }
@@ -401,8 +393,8 @@ __device__ __forceinline__ void epilogue_t(const IgemmParams& p, const AccT<MB, 
                     const int off = o * p.Ly + tau;
                     float v = acc.c[i][j][r];
                     if (ep.fused) v = ep(v, b * (int)p.add_bs + off, b * (int)p.ref_bs + off);
-                    if (p.y) yb[off] = act_apply(v, p.y_slope);
-                    if (p.y2) p.y2[(long)b * p.y2_bs + off] = act_apply(v, p.y2_slope);
+                    if (p.y) yb[off] = pg_act_apply(v, p.y_slope);
+                    if (p.y2) p.y2[(long)b * p.y2_bs + off] = pg_act_apply(v, p.y2_slope);
                     store_h(p, b, o, tau, v);
                 }
             }
@@ -432,8 +424,8 @@ __device__ __forceinline__ void epilogue_t_pm(const IgemmParams& p, const AccT<M
                     const int off = o * p.Ly + tau;
                     float v = acc.c[i][j][r];
                     if (ep.fused) v = ep(v, b * (int)p.add_bs + off, b * (int)p.ref_bs + off);
-                    yb[off] = act_apply(v, p.y_slope);
-                    if (p.y2) p.y2[(long)b * p.y2_bs + off] = act_apply(v, p.y2_slope);
+                    yb[off] = pg_act_apply(v, p.y_slope);
+                    if (p.y2) p.y2[(long)b * p.y2_bs + off] = pg_act_apply(v, p.y2_slope);
                 }
             }
         }

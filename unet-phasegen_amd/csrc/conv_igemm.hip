@@ -421,8 +421,8 @@ int plan_conv(int op, const pg_conv_args* a, bool ptrs, ConvPlan& pl) {
         p.add = a->dx_add; p.add_bs = a->dx_add_bs; p.ref = a->dx_ref; p.ref_bs = a->dx_ref_bs;
         p.mask_mode = a->dx_ref ? a->dx_mask : 0;
     } else {                        // forward: y (and y2) stored through their activations
-        p.w = a->w; p.Ly = lo; p.y = a->y; p.y_bs = a->y_bs; p.y_slope = act_slope(a->y_act);
-        p.y2 = a->y2; p.y2_bs = a->y2_bs; p.y2_slope = act_slope(a->y2_act);
+        p.w = a->w; p.Ly = lo; p.y = a->y; p.y_bs = a->y_bs; p.y_slope = pg_act_slope(a->y_act);
+        p.y2 = a->y2; p.y2_bs = a->y2_bs; p.y2_slope = pg_act_slope(a->y2_act);
     }
     if (ptrs && (!p.x || !p.y || !(o.kind == KIND_G ? p.pt : p.w))) return pg_fail(PG_ERR_NULL, o.null_msg);
     long rows = p.M, cols = (long)p.B * p.Ly, K = (long)p.Q * p.k;
@@ -473,8 +473,8 @@ int h3_params(const pg_convh_args* a, bool ptrs, IgemmParams& p, Knobs& kn) {
     p.x = reinterpret_cast<const float*>(a->x); p.x_bs = a->x_bs; p.x_pitch = a->x_pitch;
     p.w = reinterpret_cast<const float*>(a->w);
     p.y = a->y; p.y_bs = a->y_bs; p.y_slope = 1.0f; p.y2_slope = 1.0f;
-    p.yh = a->yh; p.yh_bs = a->yh_bs; p.yh_pitch = a->yh_pitch; p.yh_slope = act_slope(a->yh_act);
-    p.yh2 = a->yh2; p.yh2_bs = a->yh2_bs; p.yh2_pitch = a->yh2_pitch; p.yh2_slope = act_slope(a->yh2_act);
+    p.yh = a->yh; p.yh_bs = a->yh_bs; p.yh_pitch = a->yh_pitch; p.yh_slope = pg_act_slope(a->yh_act);
+    p.yh2 = a->yh2; p.yh2_bs = a->yh2_bs; p.yh2_pitch = a->yh2_pitch; p.yh2_slope = pg_act_slope(a->yh2_act);
     p.B = a->B; p.Q = a->Cin; p.M = a->Cout; p.Lx = a->Lin; p.Ly = a->Lout; p.k = a->k; p.s = a->stride; p.p = a->pad;
     p.ws = (float*)a->workspace;
     const long xe = ((long)(p.B - 1) * p.x_bs + (long)p.Q * p.x_pitch) * 2;

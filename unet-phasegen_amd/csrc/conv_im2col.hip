@@ -61,7 +61,7 @@ template <int KW, int S, int BF>
 __global__ __launch_bounds__(NT, 2) void conv_f_kernel(const IgemmParams p) {
     const int Ktot = p.Q * (KW ? KW : p.k), Ntot = p.B * p.Ly;
     const rsrc_t rw = make_rsrc(p.w, p.w_bytes), rx = make_rsrc(p.x, p.x_bytes);
-    const float slopeA = 1.0f, slopeB = act_slope(p.act_x);
+    const float slopeA = 1.0f, slopeB = pg_act_slope(p.act_x);
 #define F_SETUP                                                                                       \
     int aoff[AE], xoff[8], jlo[8];     /* per-row constants (BYTE offsets) of this thread's A rows / 8 B rows */ \
     _Pragma("unroll") for (int e = 0; e < AE; ++e) {                                                  \
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(NT, (KW == 0 ? 1 : 2)) void conv_t_kernel(const Ige
     const int KJ = (kw_ + s_ - 1) / s_;
     const int Ktot = p.Q * KJ, Ntot = p.B * p.U, Mrows = p.M * s_;
     const rsrc_t rw = make_rsrc(p.w, p.w_bytes), rx = make_rsrc(p.x, p.x_bytes);
-    const float slopeA = 1.0f, slopeB = act_slope(p.act_x);
+    const float slopeA = 1.0f, slopeB = pg_act_slope(p.act_x);
     const int wq = p.M * kw_;                 // weight stride between input channels q
     /* every (q, jj) names a real tap when s divides k; otherwise (k5 s2) phase 1 has one tap fewer */ \
 #define T_SETUP                                                                                       \
@@ -148,7 +148,7 @@ template <int KW, int S, int BF>
 __global__ __launch_bounds__(NT, 2) void conv_g_kernel(const IgemmParams p) {
     const int Ntot = p.Q * (KW ? KW : p.k);
     const rsrc_t rp = make_rsrc(p.pt, p.pt_bytes), rx = make_rsrc(p.x, p.x_bytes);
-    const float slopeA = act_slope(p.act_p), slopeB = act_slope(p.act_x);
+    const float slopeA = pg_act_slope(p.act_p), slopeB = pg_act_slope(p.act_x);
     const int pbs = (int)p.pt_bs, xbs = (int)p.x_bs;
 #define G_SETUP                                                                                       \
     int aoff[AE], xoff[8], jp[8];                                                                     \

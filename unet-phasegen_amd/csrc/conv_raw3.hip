@@ -210,7 +210,7 @@ __global__ __launch_bounds__(NT3, 1) void conv_raw3_kernel(const IgemmParams p) 
     const int Lcol = TKIND ? p.U : p.Ly;              // columns (output positions) per sample
     const int Ktot = p.Q * KWP, Mrows = TKIND ? p.M * S : p.M;
     const rsrc_t rw = make_rsrc(p.w, p.w_bytes), rx = make_rsrc(p.x, p.x_bytes);
-    const float slopeB = act_slope(p.act_x);
+    const float slopeB = pg_act_slope(p.act_x);
     const int wq = p.M * KW;                          // T: weight stride between input channels
     const int pm_f = ((lane & 7) ^ (((wv & 1) << 2) | (lane >> 4))) << 2;      // conv_raw_impl.h: the logical chunk this lane carries
     const int pm_ql = pm_f / (2 * TJ), pm_within = pm_f - pm_ql * 2 * TJ;

@@ -89,7 +89,7 @@ __device__ __forceinline__ void raw_load_frags(const float* __restrict__ As, con
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int v = 0; v < 4; ++v) f.a[i][c][v] = act_apply(f.a[i][c][v], slopeA);
+                for (int v = 0; v < 4; ++v) f.a[i][c][v] = pg_act_apply(f.a[i][c][v], slopeA);
     }
     if (K5 && ZERO_VIRTUAL) {       // bf16 modes (one MFMA takes all 16 k): the virtual taps' weights -- the next row's -- become 0
 #pragma unroll
@@ -102,7 +102,7 @@ __device__ __forceinline__ void raw_load_frags(const float* __restrict__ As, con
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb)
 #pragma unroll
-            for (int i = 0; i < 8; ++i) f.b[jb][i] = act_apply(f.b[jb][i], slopeB);
+            for (int i = 0; i < 8; ++i) f.b[jb][i] = pg_act_apply(f.b[jb][i], slopeB);
     }
 }
 
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(NT, 2) void conv_raw_kernel(const IgemmParams p) {
     const int Lcol = TKIND ? p.U : p.Ly;              // columns (output positions) per sample
     const int Ktot = p.Q * KWP, Mrows = TKIND ? p.M * S : p.M;
     const rsrc_t rw = make_rsrc(p.w, p.w_bytes), rx = make_rsrc(p.x, p.x_bytes);
-    const float slopeA = 1.0f, slopeB = act_slope(p.act_x);
+    const float slopeA = 1.0f, slopeB = pg_act_slope(p.act_x);
     const int wq = p.M * KW;                          // T: weight stride between input channels
     // phase-major image: the LOGICAL 16-byte chunk this lane carries into LDS (physical chunk lane & 7 of a row, XOR the row's
     // swizzle -- which depends on the wave and lane only, not on the gather instruction) = floats [f, f + 4) of the row's 32:

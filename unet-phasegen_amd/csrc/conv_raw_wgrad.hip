@@ -35,7 +35,7 @@ __device__ __forceinline__ void g_raw_bf(const IgemmParams& p) {
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wv >> 1, wn = wv & 1;
     const int kt = dma_kt(lane, wv);
     const rsrc_t rp = make_rsrc(p.pt, p.pt_bytes), rx = make_rsrc(p.x, p.x_bytes);
-    const float slopeA = act_slope(p.act_p), slopeB = act_slope(p.act_x);
+    const float slopeA = pg_act_slope(p.act_p), slopeB = pg_act_slope(p.act_x);
     const int pbs4 = (int)p.pt_bs * 4, xbs4 = (int)p.x_bs * 4;
     const int g = logical_wg(blockIdx.x, gridDim.x, p.whole);
     const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, gridDim.x, p.whole);
@@ -218,13 +218,13 @@ __device__ __forceinline__ void g_raw_bf(const IgemmParams& p) {
 #pragma unroll
                         for (int c = 0; c < 2; ++c)
 #pragma unroll
-                            for (int v = 0; v < 4; ++v) a[i][c][v] = act_apply(a[i][c][v], slopeA);
+                            for (int v = 0; v < 4; ++v) a[i][c][v] = pg_act_apply(a[i][c][v], slopeA);
                 }
                 if (slopeB != 1.0f) {
 #pragma unroll
                     for (int jb = 0; jb < 4; ++jb)
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) b[jb][i] = act_apply(b[jb][i], slopeB);
+                        for (int i = 0; i < 8; ++i) b[jb][i] = pg_act_apply(b[jb][i], slopeB);
                 }
                 if (BF) mfma_low_2x4<BF>(a, b, acc);
                 else {
@@ -285,7 +285,7 @@ __device__ __forceinline__ void g_ps_bf(const IgemmParams& p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wv >> 1, wn = wv & 1;
     const rsrc_t rp = make_rsrc(p.pt, p.pt_bytes), rx = make_rsrc(p.x, p.x_bytes);
-    const float slopeA = act_slope(p.act_p), slopeB = act_slope(p.act_x);
+    const float slopeA = pg_act_slope(p.act_p), slopeB = pg_act_slope(p.act_x);
     const int pbs4 = (int)p.pt_bs * 4, xbs4 = (int)p.x_bs * 4;
     const int cps = (p.LP + 15) >> 4;                                  // slabs (chunks of 16 frames) per sample
     const int g = logical_wg(blockIdx.x, gridDim.x, p.whole);
@@ -395,13 +395,13 @@ __device__ __forceinline__ void g_ps_bf(const IgemmParams& p) {
 #pragma unroll
                         for (int c = 0; c < 2; ++c)
 #pragma unroll
-                            for (int v = 0; v < 4; ++v) a[i][c][v] = act_apply(a[i][c][v], slopeA);
+                            for (int v = 0; v < 4; ++v) a[i][c][v] = pg_act_apply(a[i][c][v], slopeA);
                 }
                 if (slopeB != 1.0f) {
 #pragma unroll
                     for (int jb = 0; jb < 4; ++jb)
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) b[jb][i] = act_apply(b[jb][i], slopeB);
+                        for (int i = 0; i < 8; ++i) b[jb][i] = pg_act_apply(b[jb][i], slopeB);
                 }
                 if (BF) mfma_low_2x4<BF>(a, b, acc);
                 else {
@@ -702,7 +702,7 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict_
         float v = 0.f;
         if ((unsigned)t < (unsigned)L) {
             v = src[(long)b * bs + (long)c * L + t];
-            if (slope != 1.0f) v = act_apply(v, slope);
+            if (slope != 1.0f) v = pg_act_apply(v, slope);
         }
         dst[i] = v;
     }
@@ -715,7 +715,7 @@ __global__ __launch_bounds__(256) void pack_flat_kernel(const float* __restrict_
         float v = 0.f;
         if ((int)b < B) {
             v = src[(long)b * bs + (long)m * LP + t];
-            if (slope != 1.0f) v = act_apply(v, slope);
+            if (slope != 1.0f) v = pg_act_apply(v, slope);
         }
         dst[i] = v;
     }
@@ -726,9 +726,9 @@ hipError_t pack_g(const IgemmParams& p, hipStream_t st) {
     float* const qk = const_cast<float*>(p.qk);
     float* const pk = const_cast<float*>(p.pk);
     const unsigned nq = (unsigned)(p.qk_bytes / 4), np = (unsigned)(p.pk_bytes / 4);
-    hipLaunchKernelGGL(pack_rows_kernel, dim3(pack_grid(nq)), dim3(256), 0, st, p.x, p.x_bs, p.Q, p.Lx, p.p, p.Lq, nq, act_slope(p.act_x), qk);
-    if (p.g_ps) hipLaunchKernelGGL(pack_rows_kernel, dim3(pack_grid(np)), dim3(256), 0, st, p.pt, p.pt_bs, p.M, p.LP, 0, p.Kp, np, act_slope(p.act_p), pk);
-    else hipLaunchKernelGGL(pack_flat_kernel, dim3(pack_grid(np)), dim3(256), 0, st, p.pt, p.pt_bs, p.B, p.LP, p.Kp, np, act_slope(p.act_p), pk);
+    hipLaunchKernelGGL(pack_rows_kernel, dim3(pack_grid(nq)), dim3(256), 0, st, p.x, p.x_bs, p.Q, p.Lx, p.p, p.Lq, nq, pg_act_slope(p.act_x), qk);
+    if (p.g_ps) hipLaunchKernelGGL(pack_rows_kernel, dim3(pack_grid(np)), dim3(256), 0, st, p.pt, p.pt_bs, p.M, p.LP, 0, p.Kp, np, pg_act_slope(p.act_p), pk);
+    else hipLaunchKernelGGL(pack_flat_kernel, dim3(pack_grid(np)), dim3(256), 0, st, p.pt, p.pt_bs, p.B, p.LP, p.Kp, np, pg_act_slope(p.act_p), pk);
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // pg_common.h -- internal helpers shared by the libphasegen translation units (not part of the ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "phasegen.h"
 
 // Records `msg` as the calling thread's last error and returns `code` (see pg_last_error_string()).
 int pg_fail(int code, const char* msg);
@@ -9,12 +10,31 @@ int pg_cu_count();
 // taps per output phase in a transposed conv's bf16 weight shadow (pointwise.hip)
 int pg_shadow_taps(int k, int stride);
 
-// Wave(64)-level and block-level sum reductions (wavefront shuffles, then 4..16 partials through LDS).
-__device__ __forceinline__ float pg_wave_sum(float v) {
+// Returns PG_OK, or records the pending launch error under `what`.
+inline int pg_launch_ok(const char* what) {
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? PG_OK : pg_fail((int)e, what);
+}
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+
+// Activations are applied branch-free as max(v, slope*v) -- exact for 0 <= slope <= 1:
+// slope 1 = identity, 0.2 = LeakyReLU(0.2) (model.py:80), 0 = ReLU (model.py:82).
+__host__ __device__ __forceinline__ float pg_act_slope(int act) { return act == PG_ACT_LEAKY02 ? 0.2f : (act == PG_ACT_RELU ? 0.0f : 1.0f); }
+__device__ __forceinline__ float pg_act_apply(float v, float slope) { return fmaxf(v, slope * v); }
+// fp32 -> bf16, round to nearest even (a plain cast: hipcc emits v_cvt_pk_bf16_f32, NaN stays NaN)
+__device__ __forceinline__ unsigned short pg_bf16_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
+
+// Sum over groups of G consecutive lanes of a wave (a butterfly, offsets G/2 ... 1: every lane of a group gets its sum), over the
+// wave, and over the block (wave sums, then 4..16 partials through LDS).  T = float or double.
+template <int G, typename T>
+__device__ __forceinline__ T pg_group_sum(T v) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+__device__ __forceinline__ float pg_wave_sum(float v) { return pg_group_sum<64>(v); }
 // All threads get the block-wide sum.  `scratch` = at least 16 floats of LDS; safe to reuse after return.
 __device__ __forceinline__ float pg_block_sum(float v, float* scratch) {
     v = pg_wave_sum(v);

@@ -36,8 +36,6 @@ namespace {
 constexpr int ST_THREADS = 256;
 constexpr int ST_MAX_BLOCKS = 2048;        // 256 CUs x 8 workgroups: the most partials a call leaves in the workspace
 
-typedef float stf4 __attribute__((ext_vector_type(4)));
-
 struct StPartial { float peak; int32_t bad; };
 
 struct StKernelArgs {
@@ -98,14 +96,14 @@ __global__ __launch_bounds__(ST_THREADS) void stitch_kernel(const StKernelArgs a
             if (k > a.n_clips - 1) k = a.n_clips - 1;
             const long j = t - k * a.step;
             const float* hp = tr + k * a.clip_stride + j;
-            stf4 v = *(const stf4*)hp;
+            f32x4 v = *(const f32x4*)hp;
             if (k >= 1 && j < a.V) {
-                const stf4 lo = *(const stf4*)(hp + (a.step - a.clip_stride));
-                const stf4 b = *(const stf4*)(a.ramp + j), ar = *(const stf4*)(a.ramp + (a.V - 4 - j));
+                const f32x4 lo = *(const f32x4*)(hp + (a.step - a.clip_stride));
+                const f32x4 b = *(const f32x4*)(a.ramp + j), ar = *(const f32x4*)(a.ramp + (a.V - 4 - j));
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] = st_blend(ar[3 - i], b[i], lo[i], v[i]);
             }
-            *(stf4*)op = v;
+            *(f32x4*)op = v;
 #pragma unroll
             for (int i = 0; i < 4; ++i) st_note(v[i], peak, bad);
         } else {
@@ -141,10 +139,10 @@ __global__ __launch_bounds__(ST_THREADS) void stitch_finish_kernel(const StKerne
         const long r = u / a.units_per_track, t = (u - r * a.units_per_track) * VEC;
         float* op = a.out + r * a.out_stride + t;
         if (VEC == 4 && t + 4 <= a.n_out) {
-            stf4 v = *(const stf4*)op;
+            f32x4 v = *(const f32x4*)op;
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = v[i] / peak;
-            *(stf4*)op = v;
+            *(f32x4*)op = v;
         } else {
             const long n = VEC == 1 ? 1 : a.n_out - t;
             for (long i = 0; i < n; ++i) op[i] = op[i] / peak;

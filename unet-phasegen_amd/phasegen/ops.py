@@ -50,11 +50,15 @@ def set_timer(t):
     _timer = t
 
 
+def _describe(fn, a, what, *op):
+    buf = C.create_string_buffer(256)
+    _lib.check(fn(C.byref(a), *op, buf, 256), what)
+    return buf.value.decode()
+
+
 def conv_describe(a, op):
     """pg_conv_describe: 'kernel<...>|grid=G|tiles=T|slabs=S|split=0/1|whole=W|fixup=none/plain/wide' for a filled ConvArgs (nothing is launched)."""
-    buf = C.create_string_buffer(256)
-    _lib.check(_lib.load().pg_conv_describe(C.byref(a), op, buf, 256), "conv_describe")
-    return buf.value.decode()
+    return _describe(_lib.load().pg_conv_describe, a, "conv_describe", op)
 
 
 def _note_plan(a, op):
@@ -152,10 +156,13 @@ _conv_ws = _StreamCache()
 _caches = [_conv_ws]
 
 
-def _ws_key(device):
-    """Workspaces are owned by one stream at a time: key the caches by (device, current stream)."""
-    device = torch.device(device)
-    return (device, torch.cuda.current_stream(device).cuda_stream)
+def _workspace(cache, device, need, what):
+    """(ptr, nbytes) of this stream's buffer in ``cache``, at least ``need`` bytes -- the answer of a pg_workspace_bytes_* query,
+    where a negative value is an error code (raised as ``what``)."""
+    if need < 0:
+        _lib.check(int(need), what)
+    ws = cache.get(device, lambda: need, need)
+    return ws.data_ptr(), ws.numel()
 
 
 def conv_workspace(device):
@@ -257,19 +264,17 @@ def _conv_args(transposed, B, Cin, Cout, Lin, k, s, p, device=None, precision=No
     return a
 
 
-def _geom(transposed, w, k=None):
-    if transposed:
-        Cin, Cout, kk = w.shape
-    else:
-        Cout, Cin, kk = w.shape
-    return Cin, Cout, kk
+def _geom(transposed, w_shape):
+    """(Cin, Cout, k) from a weight's shape: Conv1d weights are (Cout, Cin, k), ConvTranspose1d weights (Cin, Cout, k)."""
+    a, b, k = w_shape
+    return (a, b, k) if transposed else (b, a, k)
 
 
 def conv_fwd(x, w, y, stride, pad, x_act=ACT_NONE, transposed=False, y_act=ACT_NONE, y2=None, y2_act=ACT_NONE,
              precision=None, schedule=None):
     """y = y_act(conv(x_act(x), w)) (nn.Conv1d, model.py:77) or conv_transpose (model.py:88) -- writes into ``y``;
     optionally a second copy ``y2 = y2_act(conv(...))`` (pre-activated tensors for the consumers)."""
-    Cin, Cout, k = _geom(transposed, w)
+    Cin, Cout, k = _geom(transposed, w.shape)
     B, _, Lin = x.shape
     a = _conv_args(transposed, B, Cin, Cout, Lin, k, stride, pad, x.device, precision, schedule)
     if tuple(x.shape) != (B, Cin, Lin) or tuple(y.shape) != (B, Cout, a.Lout):
@@ -291,7 +296,7 @@ def conv_fwd(x, w, y, stride, pad, x_act=ACT_NONE, transposed=False, y_act=ACT_N
 
 def conv_dgrad(dy, w, dx, stride, pad, transposed=False, add=None, ref=None, mask=ACT_NONE, precision=None, schedule=None):
     """dx = dgrad(dy, w) [+ add] [* act'(ref)] -- grad wrt the tensor the forward op read."""
-    Cin, Cout, k = _geom(transposed, w)
+    Cin, Cout, k = _geom(transposed, w.shape)
     B, _, Lin = dx.shape
     a = _conv_args(transposed, B, Cin, Cout, Lin, k, stride, pad, dx.device, precision, schedule)
     if tuple(dy.shape) != (B, Cout, a.Lout) or tuple(dx.shape) != (B, Cin, Lin):
@@ -328,7 +333,7 @@ def conv_wgrad(x, dy, dw, stride, pad, x_act=ACT_NONE, transposed=False, precisi
     """dw = wgrad(act(x), dy), overwriting ``dw`` (same layout as the weight).  ``adam`` (from ``adam_args``): the Adam update
     of this weight runs in the kernel's epilogue from the gradient it stores -- bit-identical to ``adam_step`` afterwards; the
     caller must have enqueued every reader of the old weight (the layer's dgrad) before this call."""
-    Cin, Cout, k = _geom(transposed, dw)
+    Cin, Cout, k = _geom(transposed, dw.shape)
     B, _, Lin = x.shape
     a = _conv_args(transposed, B, Cin, Cout, Lin, k, stride, pad, x.device, precision, schedule)
     if tuple(x.shape) != (B, Cin, Lin) or tuple(dy.shape) != (B, Cout, a.Lout):
@@ -387,23 +392,26 @@ def _h3(t, L, name):
     return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else t.shape[1] * pitch), pitch
 
 
-def conv_fwd_h_supported(B, w_shape, Lin, stride, pad, transposed):
-    """True if the bf16-resident kernels cover this layer at this batch / frame count (pg_conv_fwd_h_supported; host only)."""
-    if transposed:
-        Cin, Cout, k = w_shape
-    else:
-        Cout, Cin, k = w_shape
+def _convh_args(B, w_shape, Lin, stride, pad, transposed):
+    """A ConvhArgs with the layer's geometry filled in (``w_shape`` = shape of the fp32 master weight)."""
+    Cin, Cout, k = _geom(transposed, w_shape)
     a = _lib.ConvhArgs()
     a.B, a.Cin, a.Cout, a.Lin, a.k, a.stride, a.pad, a.transposed = B, Cin, Cout, Lin, k, stride, pad, int(transposed)
     a.Lout = convt_out_len(Lin, k, stride, pad) if transposed else conv_out_len(Lin, k, stride, pad)
+    return a
+
+
+def conv_fwd_h_supported(B, w_shape, Lin, stride, pad, transposed):
+    """True if the bf16-resident kernels cover this layer at this batch / frame count (pg_conv_fwd_h_supported; host only)."""
+    a = _convh_args(B, w_shape, Lin, stride, pad, transposed)
     a.x_pitch = h_pitch(Lin)
-    a.x_bs = Cin * a.x_pitch
+    a.x_bs = a.Cin * a.x_pitch
     return bool(_lib.load().pg_conv_fwd_h_supported(C.byref(a)))
 
 
 def shadow_weights(w, transposed, stride, out=None):
     """bf16 shadow of a conv weight in the bf16-resident kernels' GEMM layout (pg_shadow_weights)."""
-    Cin, Cout, k = _geom(transposed, w)
+    Cin, Cout, k = _geom(transposed, w.shape)
     n = _lib.load().pg_shadow_elems(Cin, Cout, k, stride, int(transposed))
     if out is None or out.numel() != n:
         out = torch.empty(n, device=w.device, dtype=torch.bfloat16)
@@ -427,14 +435,9 @@ def conv_fwd_h(xh, Lin, wh, w_shape, stride, pad, transposed=False, y=None, yh=N
                schedule=None):
     """bf16-resident forward conv (pg_conv_fwd_h): xh bf16 (B, Cin, pitch) holding Lin frames, wh the layer's bf16 shadow
     (``w_shape`` = shape of the fp32 master weight).  Outputs: fp32 y (B, Cout, Lout) and / or bf16 yh / yh2 (stored activated)."""
-    if transposed:
-        Cin, Cout, k = w_shape
-    else:
-        Cout, Cin, k = w_shape
     B = xh.shape[0]
-    a = _lib.ConvhArgs()
-    a.B, a.Cin, a.Cout, a.Lin, a.k, a.stride, a.pad, a.transposed = B, Cin, Cout, Lin, k, stride, pad, int(transposed)
-    a.Lout = convt_out_len(Lin, k, stride, pad) if transposed else conv_out_len(Lin, k, stride, pad)
+    a = _convh_args(B, w_shape, Lin, stride, pad, transposed)
+    Cin, Cout, k = a.Cin, a.Cout, a.k
     a.schedule = _tls.schedule if schedule is None else schedule
     if xh.shape[1] != Cin:
         raise ValueError(f"conv_fwd_h: x has {xh.shape[1]} channels, weight expects {Cin}")
@@ -470,9 +473,21 @@ def conv_fwd_h(xh, Lin, wh, w_shape, stride, pad, transposed=False, y=None, yh=N
 
 def conv_fwd_h_describe(a):
     """pg_conv_fwd_h_describe: 'conv_h3_kernel<...>|grid=G|tiles=T|slabs=S|split=0/1|whole=W|fixup=none/plain/wide' for a filled ConvhArgs."""
-    buf = C.create_string_buffer(256)
-    _lib.check(_lib.load().pg_conv_fwd_h_describe(C.byref(a), buf, 256), "conv_fwd_h_describe")
-    return buf.value.decode()
+    return _describe(_lib.load().pg_conv_fwd_h_describe, a, "conv_fwd_h_describe")
+
+
+def _norm_outputs(a, L, y, y_act, y2, y2_act, yh, yh_act, yh2, yh2_act):
+    """Bind the outputs of a normalisation forward into a BnArgs / ClipNormArgs (same field names): fp32 y / y2 (B, C, L) and bf16
+    yh / yh2 (B, C, pitch), each optional and stored with its own activation."""
+    a.y_act, a.y2_act = y_act, y2_act
+    if y is not None:                       # (a tensor that is not given costs no call: these wrappers are on the launch-bound path)
+        a.y, a.y_bs = _act3(y, "y")
+    if y2 is not None:
+        a.y2, a.y2_bs = _act3(y2, "y2")
+    if yh is not None:
+        a.yh, a.yh_bs, a.yh_pitch, a.yh_act = *_h3(yh, L, "yh"), yh_act
+    if yh2 is not None:
+        a.yh2, a.yh2_bs, a.yh2_pitch, a.yh2_act = *_h3(yh2, L, "yh2"), yh2_act
 
 
 def bn_fwd(x, y, gamma, beta, save_mean, save_invstd, running_mean=None, running_var=None, eps=1e-5, momentum=0.1,
@@ -480,20 +495,10 @@ def bn_fwd(x, y, gamma, beta, save_mean, save_invstd, running_mean=None, running
     """Train-mode BatchNorm forward (model.py:81,83).  ``num_batches_tracked``: the layer's int64 counter (0-d device tensor),
     incremented by the kernel itself -- no extra launch."""
     a = _lib.BnArgs()
-    a.y_act, a.y2_act = y_act, y2_act
-    if y2 is not None:
-        a.y2, a.y2_bs = _act3(y2, "y2")
     a.B, a.C, a.L = x.shape
     a.eps, a.momentum = eps, momentum
     a.x, a.x_bs = _act3(x, "x")
-    if yh is not None:
-        a.yh, a.yh_bs, a.yh_pitch = _h3(yh, x.shape[2], "yh")
-        a.yh_act = yh_act
-    if yh2 is not None:
-        a.yh2, a.yh2_bs, a.yh2_pitch = _h3(yh2, x.shape[2], "yh2")
-        a.yh2_act = yh2_act
-    if y is not None:
-        a.y, a.y_bs = _act3(y, "y")
+    _norm_outputs(a, x.shape[2], y, y_act, y2, y2_act, yh, yh_act, yh2, yh2_act)
     a.gamma, a.beta = _dense(gamma, "gamma"), _dense(beta, "beta")
     a.save_mean, a.save_invstd = _dense(save_mean, "save_mean"), _dense(save_invstd, "save_invstd")
     if running_mean is not None:
@@ -515,7 +520,6 @@ def clipnorm_fwd(x, y, gamma, beta, save_mean=None, save_invstd=None, running_me
     a = _lib.ClipNormArgs()
     a.B, a.C, a.L = B, Cc, L = x.shape
     a.eps, a.momentum = eps, momentum
-    a.y_act, a.y2_act = y_act, y2_act
     a.x, a.x_bs = _act3(x, "x")
     for name, t in (("y", y), ("y2", y2)):
         if t is not None and tuple(t.shape) != (B, Cc, L):
@@ -523,16 +527,7 @@ def clipnorm_fwd(x, y, gamma, beta, save_mean=None, save_invstd=None, running_me
     for name, t in (("yh", yh), ("yh2", yh2)):
         if t is not None and tuple(t.shape[:2]) != (B, Cc):
             raise ValueError(f"clipnorm_fwd: {name}{tuple(t.shape)} should be ({B}, {Cc}, pitch)")
-    if y is not None:
-        a.y, a.y_bs = _act3(y, "y")
-    if y2 is not None:
-        a.y2, a.y2_bs = _act3(y2, "y2")
-    if yh is not None:
-        a.yh, a.yh_bs, a.yh_pitch = _h3(yh, L, "yh")
-        a.yh_act = yh_act
-    if yh2 is not None:
-        a.yh2, a.yh2_bs, a.yh2_pitch = _h3(yh2, L, "yh2")
-        a.yh2_act = yh2_act
+    _norm_outputs(a, L, y, y_act, y2, y2_act, yh, yh_act, yh2, yh2_act)
     for name, t, n in (("gamma", gamma, Cc), ("beta", beta, Cc), ("save_mean", save_mean, B * Cc), ("save_invstd", save_invstd, B * Cc),
                        ("running_mean", running_mean, Cc), ("running_var", running_var, Cc)):
         if t is not None and t.numel() != n:
@@ -588,9 +583,7 @@ def loss_fwd_bwd(pred, batch, dpred=None, losses=None, mag_weight=0.2):
         losses = torch.empty(3, device=pred.device, dtype=torch.float32)
     a.losses = _dense(losses, "losses")
     lib = _lib.load()
-    need = lib.pg_workspace_bytes_loss(C.byref(a))
-    ws = _loss_ws.get(pred.device, lambda: need, need)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    a.workspace, a.workspace_bytes = _workspace(_loss_ws, pred.device, lib.pg_workspace_bytes_loss(C.byref(a)), "workspace_bytes_loss")
     _lib.check(lib.pg_loss_fwd_bwd(C.byref(a), _stream()), "loss_fwd_bwd")
     return losses
 
@@ -645,12 +638,6 @@ def stft(y, n_fft, hop, polar=False, out=None, single_frame=None, chunk_start=No
     a, out = _stft_args(y, n_fft, hop, polar, out, single_frame, chunk_start, chunk_row, chunk_len)
     _lib.check(_lib.load().pg_stft(C.byref(a), _stream()), "stft")
     return out
-
-
-def _describe(fn, a, what):
-    buf = C.create_string_buffer(256)
-    _lib.check(fn(C.byref(a), buf, 256), what)
-    return buf.value.decode()
 
 
 def stft_describe(*args, **kw):
@@ -790,11 +777,7 @@ def stitch(clips, step, n_out, normalize=False, out=None, return_status=False):
     a.normalize = int(bool(normalize))
     status = None
     if normalize or return_status:
-        need = lib.pg_workspace_bytes_stitch(C.byref(a))
-        if need < 0:
-            _lib.check(int(need), "workspace_bytes_stitch")
-        ws = _stitch_ws.get(clips.device, lambda: need, need)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        a.workspace, a.workspace_bytes = _workspace(_stitch_ws, clips.device, lib.pg_workspace_bytes_stitch(C.byref(a)), "workspace_bytes_stitch")
     if return_status:
         status = (torch.empty((), device=clips.device, dtype=torch.float32), torch.empty((), device=clips.device, dtype=torch.int32))
         a.peak, a.n_nonfinite = status[0].data_ptr(), status[1].data_ptr()
@@ -856,11 +839,7 @@ def wave_compare(x, y, gain=None, out=None):
     out = _compare_out(out, n_sig, x.device, "wave_compare")
     a.out = out.data_ptr()
     lib = _lib.load()
-    need = lib.pg_workspace_bytes_wave_compare(C.byref(a))
-    if need < 0:
-        _lib.check(int(need), "workspace_bytes_wave_compare")
-    ws = _compare_ws.get(x.device, lambda: need, need)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    a.workspace, a.workspace_bytes = _workspace(_compare_ws, x.device, lib.pg_workspace_bytes_wave_compare(C.byref(a)), "workspace_bytes_wave_compare")
     _lib.check(lib.pg_wave_compare(C.byref(a), _stream()), "wave_compare")
     return out
 
@@ -893,11 +872,7 @@ def spec_compare(R, E, gain=None, floor=1e-10, out=None):
     out = _compare_out(out, n_sig, R.device, "spec_compare")
     a.out = out.data_ptr()
     lib = _lib.load()
-    need = lib.pg_workspace_bytes_spec_compare(C.byref(a))
-    if need < 0:
-        _lib.check(int(need), "workspace_bytes_spec_compare")
-    ws = _compare_ws.get(R.device, lambda: need, need)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    a.workspace, a.workspace_bytes = _workspace(_compare_ws, R.device, lib.pg_workspace_bytes_spec_compare(C.byref(a)), "workspace_bytes_spec_compare")
     _lib.check(lib.pg_spec_compare(C.byref(a), _stream()), "spec_compare")
     return out
 
@@ -964,9 +939,7 @@ def _istft_calls(a_t, b_t, audio, hop, mode, normalize, single_frame):
         a.a, a.a_bs = _act3(a_t[s0:s1], "a")
         a.b, a.b_bs = _act3(b_t[s0:s1], "b")
         a.audio = audio[s0:s1].data_ptr()
-        need = _lib.load().pg_workspace_bytes_istft(C.byref(a))
-        ws = _istft_ws.get(a_t.device, lambda: need, need)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        a.workspace, a.workspace_bytes = _workspace(_istft_ws, a_t.device, _lib.load().pg_workspace_bytes_istft(C.byref(a)), "workspace_bytes_istft")
         yield a
 
 
