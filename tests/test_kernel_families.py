@@ -145,3 +145,94 @@ def test_column_tail_launch_policy():
     lib = _lib.load()
     buf = ctypes.create_string_buffer(256)
     assert lib.pg_conv_describe(ctypes.byref(_args(_lib, 64, 1024, 2048, 256, 32, 2, 16, False, schedule=0x60000)), _lib.OP_CONV1D_FWD, buf, 256) == -2
+
+
+# Small problems that reach every instantiation of the stream-K fixup kernel (csrc/conv_fixup.h): wave tile and wave grid of the
+# family's GEMM kernel x epilogue (F, T, T over phase-major rows "Tpm", G) x plain / wide form.
+# ((transposed, Cin, Cout, k, s, p, Lin, B), op, schedule, kernel family, epilogue, fixup form)
+T_, F_ = True, False
+FIXUP_CASES = [
+    # im2col: 4 x 2 blocks per wave, 2 x 2 waves
+    ((T_, 32, 16, 5, 2, 1, 1, 2), "dgrad", 6, "conv_f", "F", "plain"), ((T_, 32, 16, 8, 2, 1, 3, 3), "dgrad", 6, "conv_f", "F", "wide"),
+    ((T_, 32, 16, 5, 2, 1, 1, 2), "fwd", 6, "conv_t", "T", "plain"), ((T_, 32, 16, 8, 2, 1, 3, 3), "fwd", 6, "conv_t", "T", "wide"),
+    ((T_, 36, 17, 5, 2, 1, 9, 2), "wgrad", 6, "conv_g", "G", "plain"), ((F_, 36, 72, 4, 2, 1, 61, 5), "wgrad", 6, "conv_g", "G", "wide"),
+    # raw-window wgrad: 2 x 4 blocks, 2 x 2 waves
+    ((T_, 264, 132, 8, 2, 1, 29, 2), "wgrad", 2, "conv_g_raw", "G", "plain"), ((F_, 36, 72, 4, 2, 1, 61, 5), "wgrad", 2, "conv_g_ps", "G", "wide"),
+    # raw 128 x 256: 2 x 4 blocks, 2 x 2 waves
+    ((F_, 8, 8, 4, 2, 1, 30, 2), "fwd", 10, "conv_raw(128x256)", "F", "plain"), ((F_, 32, 8, 4, 2, 1, 30, 2), "fwd", 10, "conv_raw(128x256)", "F", "wide"),
+    ((F_, 8, 8, 8, 1, 2, 61, 2), "dgrad", 10, "conv_raw(128x256)", "T", "plain"), ((F_, 8, 16, 8, 1, 2, 61, 2), "dgrad", 10, "conv_raw(128x256)", "T", "wide"),
+    ((F_, 8, 8, 8, 2, 1, 30, 2), "dgrad", 10, "conv_raw(128x256)", "Tpm", "plain"), ((F_, 8, 32, 8, 2, 1, 30, 2), "dgrad", 10, "conv_raw(128x256)", "Tpm", "wide"),
+    # raw tall 256 x 128: 2 x 4 blocks, 4 x 1 waves
+    ((F_, 16, 32, 4, 2, 1, 3, 2), "fwd", 2, "conv_raw(tall 256x128)", "F", "plain"), ((F_, 16, 16, 8, 1, 2, 13, 3), "fwd", 2, "conv_raw(tall 256x128)", "F", "wide"),
+    ((F_, 16, 8, 8, 1, 2, 13, 3), "dgrad", 2, "conv_raw(tall 256x128)", "T", "plain"), ((F_, 16, 16, 8, 1, 2, 13, 3), "dgrad", 2, "conv_raw(tall 256x128)", "T", "wide"),
+    ((F_, 16, 32, 4, 2, 1, 3, 2), "dgrad", 2, "conv_raw(tall 256x128)", "Tpm", "plain"), ((T_, 32, 16, 8, 2, 1, 3, 3), "fwd", 2, "conv_raw(tall 256x128)", "Tpm", "wide"),
+    # conv_raw3: 8 x 2 blocks, 1 x 4 waves; plain however many segments a tile has (the first row: 68)
+    ((F_, 136, 130, 8, 2, 1, 62, 2), "fwd", 0x4002, "conv_raw3", "F", "plain"), ((F_, 160, 136, 8, 1, 2, 65, 3), "dgrad", 0x4002, "conv_raw3", "T", "plain"),
+    ((T_, 48, 125, 5, 2, 1, 30, 6), "fwd", 0x4002, "conv_raw3", "Tpm", "plain"),
+    # ... in super-rows of 2 over 3 x 2 tiles: the last super-row is short, and the fixup decodes the tile order itself
+    ((F_, 16, 760, 8, 2, 1, 130, 5), "fwd", 0x14002, "conv_raw3", "F", "plain"), ((F_, 380, 32, 8, 2, 1, 130, 5), "dgrad", 0x14002, "conv_raw3", "Tpm", "plain"),
+]
+# pg_conv_fwd_h (conv_h3: 8 x 2 blocks, 1 x 4 waves; rows of (channel, phase) pairs, never phase-major), schedule 2
+FIXUP_CASES_H = [((F_, 16, 16, 8, 1, 2, 13, 3), "F", "plain"), ((F_, 8, 16, 32, 2, 16, 24, 1), "F", "wide"),
+                 ((T_, 32, 16, 8, 2, 1, 3, 3), "T", "plain"), ((T_, 32, 16, 8, 1, 2, 10, 3), "T", "wide")]
+
+
+def fixup_case_id(c):
+    g = c[0]
+    return f"{'T' if g[0] else 'C'}{g[1]}-{g[2]}-k{g[3]}s{g[4]}-L{g[6]}-B{g[7]}-" + "-".join(str(v) for v in c[1:])
+
+
+def _fields(d):
+    return dict(kv.split("=", 1) for kv in d.split("|")[1:])
+
+
+def _epilogue(desc):
+    """the epilogue a described kernel's fixup runs: G for the wgrads; F / T from the kernel's own form; Tpm for the stride-2 T form of
+    the raw-window kernels (conv_raw, conv_raw3), which store phase-major rows"""
+    m = re.match(r"conv_([a-z0-9_]+)_kernel<(.*)>", desc.split("|")[0])
+    fam, targs = m.group(1), [t.strip() for t in m.group(2).split(",")]
+    if fam in ("f", "t", "g"):
+        return fam.upper()
+    if fam.startswith("g_"):
+        return "G"
+    if targs[2] != "true":
+        return "F"
+    return "Tpm" if fam in ("raw", "raw3") and targs[1] == "2" else "T"
+
+
+def test_every_fixup_instantiation_is_reached_by_a_small_case():
+    from phasegen import _lib, ops
+    reached = set()
+    for geom, op, sched, fam, epi, form in FIXUP_CASES:
+        tr, Cin, Cout, k, s, p, Lin, B = geom
+        opc = {"fwd": (_lib.OP_CONV1D_FWD, _lib.OP_CONVT1D_FWD), "dgrad": (_lib.OP_CONV1D_DGRAD, _lib.OP_CONVT1D_DGRAD),
+               "wgrad": (_lib.OP_CONV1D_WGRAD, _lib.OP_CONVT1D_WGRAD)}[op][tr]
+        d = ops.conv_describe(_args(_lib, B, Cin, Cout, Lin, k, s, p, tr, schedule=sched), opc)
+        f = _fields(d)
+        assert (family(d), _epilogue(d), f["fixup"]) == (fam, epi, form) and "tail" not in f, (geom, op, d)
+        reached.add((fam.replace("conv_g_ps", "conv_g_raw"), epi, form))         # (the two raw-window wgrads share a tile geometry)
+    # conv_raw3 stays plain however many segments a tile has: one tile in 68 segments, where every other family goes wide (from 8)
+    f = _fields(ops.conv_describe(_args(_lib, 2, 136, 130, 62, 8, 2, 1, False, schedule=0x4002), _lib.OP_CONV1D_FWD))
+    assert (f["grid"], f["tiles"], f["whole"], f["fixup"]) == ("68", "1", "0", "plain"), f
+    # super-rows of 2 over 3 tile rows x 2 tile columns
+    for geom, op, sched, *_ in FIXUP_CASES[-2:]:
+        tr, Cin, Cout, k, s, p, Lin, B = geom
+        f = _fields(ops.conv_describe(_args(_lib, B, Cin, Cout, Lin, k, s, p, tr, schedule=sched), _lib.OP_CONV1D_FWD if op == "fwd" else _lib.OP_CONV1D_DGRAD))
+        assert f["tiles"] == "6", f
+    for geom, epi, form in FIXUP_CASES_H:
+        tr, Cin, Cout, k, s, p, Lin, B = geom
+        a = _lib.ConvhArgs()
+        a.B, a.Cin, a.Cout, a.Lin, a.k, a.stride, a.pad, a.transposed = B, Cin, Cout, Lin, k, s, p, int(tr)
+        a.Lout = (Lin - 1) * s - 2 * p + k if tr else (Lin + 2 * p - k) // s + 1
+        a.x_pitch = ops.h_pitch(Lin)
+        a.x_bs = Cin * a.x_pitch
+        a.x = a.w = a.y = 4096
+        a.y_bs = Cout * a.Lout
+        a.workspace, a.workspace_bytes = 4096, _lib.load().pg_workspace_bytes_conv()
+        a.schedule = 2
+        d = ops.conv_fwd_h_describe(a)
+        assert (family(d), _epilogue(d), _fields(d)["fixup"]) == ("conv_h3", epi, form), (geom, d)
+        reached.add(("conv_h3", epi, form))
+    # 25 instantiations: 2 forms x (im2col F T G, raw 128 x 256 F T Tpm G, raw tall F T Tpm, one wave per SIMD F T) + conv_raw3's plain
+    # Tpm; conv_raw3 and conv_h3 share the plain F and T ones, so the table names 27 (family, epilogue, form) triples
+    assert len(reached) == 27, sorted(reached)

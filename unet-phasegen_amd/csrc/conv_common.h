@@ -1,7 +1,9 @@
 // conv_common.h -- shared by the translation units of the convolution kernels (conv_igemm.hip = host side + fixup,
-// conv_im2col.hip, conv_raw.hip, conv_raw_wgrad.hip): problem descriptor, LDS-DMA helpers, MFMA operand modes, stream-K
-// split, epilogues.  Everything lives in an anonymous namespace (each unit gets its own copy); the only symbols with
-// external linkage are the pgconv::launch_* functions declared at the end.
+// conv_im2col.hip, conv_raw.hip, conv_raw_wgrad.hip, conv_raw3.hip, conv_h3.hip): problem descriptor, LDS-DMA helpers, MFMA
+// operand modes, stream-K split, partial-tile store, epilogues.  On top of it: conv_fixup.h (the fixup kernel of the stream-K
+// split, instantiated by conv_igemm.hip only) and conv_w1.h (what the one-wave-per-SIMD kernels of conv_raw3.hip and conv_h3.hip
+// share).  Everything lives in an anonymous namespace (each unit gets its own copy); the only symbols with external linkage are
+// the pgconv::launch_* functions declared at the end.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -321,18 +323,50 @@ __device__ __forceinline__ int logical_wg(int bid, int G, int w) {
     return bid < w ? xcd_remap(bid, w) : w + xcd_remap(bid - w, G - w);
 }
 
-constexpr int ACC_REGS = 128;             // accumulator registers per thread in both tile configurations (8 blocks x 16)
-template <int MB, int NB>
-__device__ __forceinline__ void store_partial(float* ws, int g, int slot, const AccT<MB, NB>& acc, int tid, int nbv = NB) {
-    static_assert(MB * NB * 16 == ACC_REGS, "partial-tile slots are sized for 8 blocks per wave");
-    float* dst = ws + ((long)(g * 2 + slot) * ACC_REGS) * NT + tid;
+// A workgroup's walk over its range of the (tile, slab) space, one tile segment at a time:
+//   Walk wk(p); while (wk.more()) { wk.segment(p, tile, sb, se); ... wk.next(se - sb); }
+// a segment that is not a whole tile leaves its accumulators in slot (wk.g, wk.slot): 0 = the range's first segment, 1 = its last.
+// Two kernels keep the same walk written out, because through this struct hipcc emits a handful of their scalar instructions in
+// another order: the body macro of conv_im2col.hip (conv_t_kernel) and g_ps_f32 of conv_raw_wgrad.hip.
+struct Walk {
+    int g, pos, pos_end, slot;
+    __device__ __forceinline__ Walk(const IgemmParams& p) : g(logical_wg(blockIdx.x, gridDim.x, p.whole)), slot(0) {
+        const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, gridDim.x, p.whole);
+        pos = split_lo(sp, g);
+        pos_end = split_lo(sp, g + 1);
+    }
+    __device__ __forceinline__ bool more() const { return pos < pos_end; }
+    __device__ __forceinline__ void segment(const IgemmParams& p, int& tile, int& sb, int& se) const {     // slabs [sb, se) of `tile`
+        tile = pos / p.nslab; sb = pos - tile * p.nslab;
+        se = min(p.nslab, sb + (pos_end - pos));
+    }
+    __device__ __forceinline__ void next(int nslabs) { pos += nslabs; slot = 1; }
+};
+
+constexpr int ACC_REGS = 128;             // accumulator registers per thread of the two-waves-per-SIMD tiles (8 blocks x 16)
+// An accumulator register read where it is USED: the "a" constraint keeps the value in its AGPR up to this instruction.  With plain
+// uses hipcc split all 256 live ranges of a one-wave-per-SIMD kernel (conv_w1.h) to VGPRs at the loop exit in one go (256
+// v_accvgpr_read in a row) and spilled what did not fit.
+__device__ __forceinline__ float acc_agpr(float v) {
+    float x;
+    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(v));
+    return x;
+}
+// A segment's accumulators into slot (g, slot) of the workspace: MB * NB * 16 planes of 256 floats, thread tid's register n at
+// plane n.  ncols: columns of the problem from this wave's first column on (wave-uniform) -- column blocks without columns are
+// neither written here nor read by the fixup (conv_fixup.h): at batch 1 (65 ... 14 columns in a 256-wide tile) the partial tiles
+// were 40 % of the bytes moved.  AGPR: the one-wave-per-SIMD kernels, whose accumulators are read through acc_agpr.
+template <bool AGPR = false, int MB, int NB>
+__device__ __forceinline__ void store_partial(float* ws, int g, int slot, const AccT<MB, NB>& acc, int tid, int ncols = NB * 32) {
+    static_assert(MB * NB * 16 == ACC_REGS || MB * NB * 16 == 2 * ACC_REGS, "partial-tile slots are sized for 8 or 16 blocks per wave");
+    float* dst = ws + ((long)(g * 2 + slot) * (MB * NB * 16)) * NT + tid;
 #pragma unroll
     for (int i = 0; i < MB; ++i)
 #pragma unroll
         for (int j = 0; j < NB; ++j)
-            if (j < nbv) {           // (column blocks past the problem's last column are neither written nor, by the fixup, read)
+            if (j * 32 < ncols) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) dst[((i * NB + j) * 16 + r) * NT] = acc.c[i][j][r];
+                for (int r = 0; r < 16; ++r) dst[((i * NB + j) * 16 + r) * NT] = AGPR ? acc_agpr(acc.c[i][j][r]) : acc.c[i][j][r];
             }
 }
 
@@ -539,10 +573,8 @@ hipError_t launch_raw_ft_tall(int kind, const IgemmParams& p, int grid, hipStrea
 hipError_t launch_raw_g(const IgemmParams& p, int grid, hipStream_t st, int prec);              // conv_raw_wgrad.hip (fp32: packs first)
 // conv_h3.hip: 4 waves at ONE per SIMD, wave tile 256 x 64, tile 256 x 256
 hipError_t launch_h3(int kind, const IgemmParams& p, int grid, hipStream_t st);
-hipError_t launch_h3_fixup(int kind, const IgemmParams& p, int grid, unsigned split_tiles, bool wide, hipStream_t st);
 // conv_raw3.hip: fp32 raw-window F / T kernels on 4 waves at ONE per SIMD, tile 256 x 256
 bool raw3_covers(int kind, const IgemmParams& p);               // (k, s) pair and whole-slab K; the window-length bound is raw_supported's
 hipError_t launch_raw3(int kind, const IgemmParams& p, int grid, hipStream_t st);
-hipError_t launch_raw3_fixup(int kind, const IgemmParams& p, int grid, unsigned blocks, hipStream_t st);
 bool h_supported(int kind, const IgemmParams& p);               // geometry covered by the bf16-resident kernels (conv_h3.hip)
 }  // namespace pgconv

@@ -7,16 +7,14 @@
 // per fragment set has 26 non-MFMA instructions for 16 MFMAs per k-step (8 + 6 LDS reads, 8 funnel shifts, addresses): 1.6 per
 // MFMA gap, and an MFMA holds the vector issue for only 8 of its 32 cycles -- placed INSIDE the gaps they cost nothing.  The
 // placement is written out: a k-step is 16 CHUNKS (one MFMA + at most one piece of other work) separated by scheduling fences.
-#include "conv_common.h"
+#include "conv_w1.h"
 
 namespace {
 
 constexpr int KB = 32;
 constexpr int H_HEAD = 32;                // zero elements the caller guarantees in front of x (PG_H_HEAD)
-constexpr int NT3 = 256;                  // threads per workgroup
 constexpr int H3_LDS = 156 * 1024;
 constexpr int H3_RING = 3;
-constexpr int H3_REGS = 256;              // accumulator registers per thread: 16 blocks x 16
 #ifndef PG_H3_SPBMAX
 #define PG_H3_SPBMAX 4
 #endif
@@ -28,11 +26,6 @@ __host__ __device__ constexpr int h3_spb(int stg_floats) {
         if (H3_RING * n * stg_floats * 4 <= H3_LDS) return n;
     return 1;
 }
-template <int N> __device__ __forceinline__ void h3_wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit count");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
@@ -42,18 +35,10 @@ typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 // of the lane's parity (conv_h.hip).  The pieces are separate functions because the k-step loop below places them one per MFMA.
 struct H3Frag { f32x4 a[8]; unsigned d[2][6]; u32x4v b[2]; };
 
-// The reads are `asm volatile`: hipcc orders plain LDS loads freely against the scheduling fences of the k-step loop (it sank all eight
-// A reads of a k-step behind its 11th MFMA).  What that costs: the compiler does not count them -- the loop waits for them itself
-// (h3_lgkm0) before the first use of a fragment set.
-__device__ __forceinline__ unsigned h3_lds_addr(const float* p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) float*)p;
-}
-__device__ __forceinline__ void h3_lgkm0() { __builtin_amdgcn_s_waitcnt(0xc07f); }      // lgkmcnt(0), the other counters untouched
-
 // byte address of the lane's 16-byte group of row r in 32-row block 0 of a stage (k-step s, half h); block i is 2048 bytes further
 __device__ __forceinline__ unsigned h3_a_addr(const float* stage, int s, int r, int h) {
     const int sw = (r >> 2) & 3;
-    return h3_lds_addr(stage) + (r * 16 + (((2 * s + h) ^ sw) << 2)) * 4;
+    return w1_lds_addr(stage) + (r * 16 + (((2 * s + h) ^ sw) << 2)) * 4;
 }
 template <int I> __device__ __forceinline__ void h3_load_a(unsigned a_addr, H3Frag& f) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f.a[I]) : "v"(a_addr), "n"(I * 2048));
@@ -63,7 +48,7 @@ template <int TJ, int RSD, int TA>
 __device__ __forceinline__ unsigned h3_b_addr(const float* stage, int s, int h, int bdw_jb) {
     const int qi = TJ == 32 ? 0 : (TJ == 16 ? s : (TJ == 8 ? 2 * s + h : 4 * s + 2 * h));
     const int tap0 = TJ == 32 ? 16 * s + 8 * h : (TJ == 16 ? 8 * h : 0);
-    return h3_lds_addr(stage + TA) + (qi * RSD + bdw_jb + (tap0 >> 1)) * 4;
+    return w1_lds_addr(stage + TA) + (qi * RSD + bdw_jb + (tap0 >> 1)) * 4;
 }
 template <int TJ, int RSD, int JB> __device__ __forceinline__ void h3_load_b(unsigned b_addr, H3Frag& f) {
     typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
@@ -133,7 +118,7 @@ __device__ __forceinline__ void h3_kstep(const H3Frag& cur, H3Frag& nxt, const f
     H3_CHUNK(15, issue(E0 + 3))                // (the 4th slot: only the second k-step of a slab with 7 gathers uses it)
     __builtin_amdgcn_sched_barrier(0);
     if (NEXT) {                                // every read of `nxt` was issued six or more MFMAs (190 cycles) ago
-        h3_lgkm0();
+        w1_lgkm0();
         __builtin_amdgcn_sched_barrier(0);
         h3_finish_b<TJ>(0, bsh, nxt);
         h3_finish_b<TJ>(1, bsh, nxt);
@@ -142,30 +127,8 @@ __device__ __forceinline__ void h3_kstep(const H3Frag& cur, H3Frag& nxt, const f
 #undef H3_CHUNK
 }
 
-// An accumulator register read where it is USED: the "a" constraint keeps the value in its AGPR up to this instruction.  With plain
-// uses hipcc split all 256 live ranges to VGPRs at the loop exit in one go (256 v_accvgpr_read in a row) and spilled what did not fit.
-__device__ __forceinline__ float h3_acc(float v) {
-    float x;
-    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(v));
-    return x;
-}
-
-// cols_left: columns of the problem from this wave's first column on (wave-uniform).  Column blocks without columns are neither
-// written here nor read by the fixup: at batch 1 (65 ... 14 columns in a 256-wide tile) the partial tiles were 40 % of the bytes moved
-__device__ __forceinline__ void store_partial3(float* ws, int g, int slot, const AccT<8, 2>& acc, int tid, int cols_left) {
-    float* dst = ws + ((long)(g * 2 + slot) * H3_REGS) * NT3 + tid;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            if (j * 32 < cols_left) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) dst[((i * 2 + j) * 16 + r) * NT3] = h3_acc(acc.c[i][j][r]);
-            }
-}
-
 template <int KW, int S, bool TKIND>
-__global__ __launch_bounds__(NT3, 1) void conv_h3_kernel(const IgemmParams p) {
+__global__ __launch_bounds__(W1_NT, 1) void conv_h3_kernel(const IgemmParams p) {
     constexpr int TM = 256, TN = 256;
     constexpr int KWP = TKIND ? KW / S : KW;
     constexpr int TJ = KWP < 32 ? KWP : 32, NQ = 32 / TJ;
@@ -192,14 +155,10 @@ __global__ __launch_bounds__(NT3, 1) void conv_h3_kernel(const IgemmParams p) {
     const int Ktot = p.Q * KWP, Mrows = TKIND ? p.M * S : p.M;
     const rsrc_t rw = make_rsrc(p.w, p.w_bytes);
     const rsrc_t rx = make_rsrc(reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(p.x) - H_HEAD), p.x_bytes + 2 * H_HEAD);
-    const int g = logical_wg(blockIdx.x, gridDim.x, p.whole);
-    const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, gridDim.x, p.whole);
-    int pos = split_lo(sp, g);
-    const int pos_end = split_lo(sp, g + 1);
-    int slot = 0;
-    while (pos < pos_end) {
-        const int tile = pos / p.nslab, sb = pos - tile * p.nslab;
-        const int se = min(p.nslab, sb + (pos_end - pos));
+    Walk wk(p);
+    while (wk.more()) {
+        int tile, sb, se;
+        wk.segment(p, tile, sb, se);
         const int m0 = (tile / p.tilesN) * TM, n0 = (tile % p.tilesN) * TN;
         const int b0 = n0 / Lcol, t0 = n0 - b0 * Lcol;
         const int nc0 = min(Lcol - t0, TN);
@@ -264,15 +223,15 @@ __global__ __launch_bounds__(NT3, 1) void conv_h3_kernel(const IgemmParams p) {
         // reads of group i for every wave (its last k-step multiplies registers): group i + 3's gathers may overwrite its slot.
         constexpr int NMID = (SPB - 1) * (NAW + NPW) + 3;
         auto wait_first = [&]() {
-            h3_wait_vmcnt<NGRP>();
+            w1_wait_vmcnt<NGRP>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         };
         auto wait_next = [&]() {
 #ifdef PG_H3_ABL
-            h3_wait_vmcnt<0>();
+            w1_wait_vmcnt<0>();
 #else
-            h3_wait_vmcnt<NMID>();
+            w1_wait_vmcnt<NMID>();
 #endif
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -290,7 +249,7 @@ __global__ __launch_bounds__(NT3, 1) void conv_h3_kernel(const IgemmParams p) {
             h3_load_b<TJ, RSD, 1>(h3_b_addr<TJ, RSD, TA>(lds, 0, h, bdw[1]), f0);
             h3_load_a<0>(aa, f0); h3_load_a<1>(aa, f0); h3_load_a<2>(aa, f0); h3_load_a<3>(aa, f0);
             h3_load_a<4>(aa, f0); h3_load_a<5>(aa, f0); h3_load_a<6>(aa, f0); h3_load_a<7>(aa, f0);
-            h3_lgkm0();
+            w1_lgkm0();
             __builtin_amdgcn_sched_barrier(0);
             h3_finish_b<TJ>(0, bsh, f0);
             h3_finish_b<TJ>(1, bsh, f0);
@@ -318,74 +277,18 @@ __global__ __launch_bounds__(NT3, 1) void conv_h3_kernel(const IgemmParams p) {
             st = st1;
         }
         __syncthreads();
-        // the accumulator reads below are `asm` (h3_acc): hipcc's hazard recogniser does not see them, so the wait states an MFMA
+        // the accumulator reads below are `asm` (acc_agpr): hipcc's hazard recogniser does not see them, so the wait states an MFMA
         // result needs before a VALU may read it (its 8 passes = 32 cycles) are spelled out -- 48 cycles, once per tile segment
         asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15");
         if (sb == 0 && se == p.nslab) {
-            // one 32 x 32 block at a time behind scheduling fences: with all 256 accumulator registers of the wave tile in one
-            // epilogue hipcc moved them to VGPRs wholesale and spilled ~200 of them -- through the MAIN loop as well
-            // (written out: a `#pragma unroll` nest over the 16 blocks exceeds hipcc's unroll budget, stays rolled, and indexes
-            // the accumulators dynamically -- i.e. keeps them in scratch)
 #define H3_EPI(I, J)                                                                                              \
-    {   AccT<1, 1> blk;                                                                                          \
-        _Pragma("unroll") for (int q = 0; q < 16; ++q) blk.c[0][0][q] = h3_acc(acc.c[I][J][q]);                          \
-        __builtin_amdgcn_sched_barrier(0);                                                                       \
-        if (TKIND) epilogue_t<S, 1, 1>(p, blk, m0 + (I) * 32, n0 + (wn * NBW + (J)) * 32, lane, 0, 0);           \
-        else epilogue_f<S, 1, 1>(p, blk, m0 + (I) * 32, n0 + (wn * NBW + (J)) * 32, lane, 0, 0);                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                       \
-    }
-            H3_EPI(0, 0) H3_EPI(0, 1) H3_EPI(1, 0) H3_EPI(1, 1) H3_EPI(2, 0) H3_EPI(2, 1) H3_EPI(3, 0) H3_EPI(3, 1)
-            H3_EPI(4, 0) H3_EPI(4, 1) H3_EPI(5, 0) H3_EPI(5, 1) H3_EPI(6, 0) H3_EPI(6, 1) H3_EPI(7, 0) H3_EPI(7, 1)
+    if (TKIND) epilogue_t<S, 1, 1>(p, blk, m0 + (I) * 32, n0 + (wn * NBW + (J)) * 32, lane, 0, 0);               \
+    else epilogue_f<S, 1, 1>(p, blk, m0 + (I) * 32, n0 + (wn * NBW + (J)) * 32, lane, 0, 0)
+            W1_EPILOGUE(H3_EPI)
 #undef H3_EPI
-        } else store_partial3(p.ws, g, slot, acc, tid, __builtin_amdgcn_readfirstlane(p.B * (TKIND ? p.U : p.Ly) - n0 - (tid >> 6) * 64));
-        pos += se - sb;
-        slot = 1;
+        } else store_partial<true>(p.ws, wk.g, wk.slot, acc, tid, __builtin_amdgcn_readfirstlane(p.B * (TKIND ? p.U : p.Ly) - n0 - (tid >> 6) * 64));
+        wk.next(se - sb);
     }
-}
-
-// fixup of the stream-K split: one workgroup per (split tile, 32 x 32 block index of the wave tile: 16 of them); WIDE (many
-// segments per tile, small-batch inference): four workgroups per block, one per GEMM wave, whose four waves each sum every fourth
-// segment and wave 0 adds the four sums in order (conv_igemm.hip's conv_fixup_kernel has the same two forms)
-template <int KIND, bool WIDE>
-__global__ __launch_bounds__(NT3) void conv_h3_fixup_kernel(const IgemmParams p, int G) {
-    constexpr int MB = 8, NB = 2;
-    __shared__ float red[WIDE ? 3 * 16 * 64 : 1];
-    const int unit = WIDE ? blockIdx.x >> 2 : blockIdx.x, q = WIDE ? threadIdx.x >> 6 : 0;
-    const int tid = WIDE ? (blockIdx.x & 3) * 64 + (threadIdx.x & 63) : threadIdx.x;
-    const int lane = tid & 63, wv = tid >> 6;
-    const int wm = 0, wn = wv;
-    const int tile = p.whole + unit / (MB * NB), blk = unit % (MB * NB), bi = blk / NB, bj = blk - bi * NB;
-    const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, G, p.whole);
-    const int first = tile * p.nslab, last = first + p.nslab - 1;
-    const int g0 = split_owner(sp, first), g1 = split_owner(sp, last);
-    if (g0 == g1 && split_lo(sp, g0) <= first && split_lo(sp, g0 + 1) > last) return;
-    if ((tile % p.tilesN) * p.tn_stride + wn * NB * 32 + bj * 32 >= p.B * (KIND == 0 ? p.Ly : p.U)) return;     // a block without columns
-    AccT<1, 1> acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc.c[0][0][r] = 0.f;
-#pragma unroll 2
-    for (int g = g0 + q; g <= g1; g += WIDE ? 4 : 1) {
-        const int slot = (split_lo(sp, g) / p.nslab == tile) ? 0 : 1;
-        const float* src = p.ws + ((long)(g * 2 + slot) * H3_REGS) * NT3 + tid;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc.c[0][0][r] += src[(blk * 16 + r) * NT3];
-    }
-    if (WIDE) {         // (the returns above are uniform over the workgroup here)
-        if (q) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[((q - 1) * 16 + r) * 64 + lane] = acc.c[0][0][r];
-        }
-        __syncthreads();
-        if (q) return;
-#pragma unroll
-        for (int qq = 0; qq < 3; ++qq)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc.c[0][0][r] += red[(qq * 16 + r) * 64 + lane];
-    }
-    const int m0 = (tile / p.tilesN) * 256 + wm * (MB - 1) * 32 + bi * 32;
-    const int n0 = (tile % p.tilesN) * p.tn_stride + wn * (NB - 1) * 32 + bj * 32;
-    if (KIND == 0) epilogue_f<0, 1, 1>(p, acc, m0, n0, lane, wm, wn);
-    else epilogue_t<0, 1, 1>(p, acc, m0, n0, lane, wm, wn);
 }
 
 template <int KW, int S, bool TK>
@@ -393,10 +296,7 @@ hipError_t launch3(const IgemmParams& p, int grid, hipStream_t st) {
     constexpr int KWP = TK ? KW / S : KW, TJ = KWP < 32 ? KWP : 32, NQ = 32 / TJ, SC = TK ? 1 : S;
     constexpr int NI = (NQ * h3_rsd(SC) / 4 + 63) / 64, STG = 256 * 16 + 4 * ((NI + 3) / 4) * 256;
     constexpr int lds_bytes = H3_RING * h3_spb(STG) * STG * 4;
-    hipError_t e = hipFuncSetAttribute((const void*)conv_h3_kernel<KW, S, TK>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((conv_h3_kernel<KW, S, TK>), dim3(grid), dim3(NT3), lds_bytes, st, p);
-    return hipGetLastError();
+    return w1_launch(conv_h3_kernel<KW, S, TK>, lds_bytes, p, grid, st);
 }
 
 }  // namespace
@@ -444,13 +344,4 @@ hipError_t pgconv::launch_h3(int kind, const IgemmParams& p, int grid, hipStream
     if (p.k == 32) return launch3<32, 2, true>(p, grid, st);
     if (p.s == 1) return launch3<8, 1, true>(p, grid, st);
     return launch3<8, 2, true>(p, grid, st);
-}
-
-hipError_t pgconv::launch_h3_fixup(int kind, const IgemmParams& p, int grid, unsigned split_tiles, bool wide, hipStream_t st) {
-    const dim3 fg(split_tiles * (wide ? 64 : 16));
-    if (kind == KIND_F) { if (wide) hipLaunchKernelGGL((conv_h3_fixup_kernel<0, true>), fg, dim3(NT3), 0, st, p, grid);
-                          else hipLaunchKernelGGL((conv_h3_fixup_kernel<0, false>), fg, dim3(NT3), 0, st, p, grid); }
-    else { if (wide) hipLaunchKernelGGL((conv_h3_fixup_kernel<1, true>), fg, dim3(NT3), 0, st, p, grid);
-           else hipLaunchKernelGGL((conv_h3_fixup_kernel<1, false>), fg, dim3(NT3), 0, st, p, grid); }
-    return hipGetLastError();
 }

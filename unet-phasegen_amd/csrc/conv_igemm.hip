@@ -25,7 +25,10 @@
 //                        LDS-DMA with per-lane source addresses (im2col, phase split, zero padding and the XOR swizzle all
 //                        live in the address).  They serve k = 5, generic (k, s) and shapes whose windows do not fit, and
 //                        stay covered by the tests (schedule bit 2).
-//   conv_igemm.hip       (this file) fixup kernel of the stream-K split; host side: geometry checks, grid policy and the launch
+//   conv_w1.h            what the two one-wave-per-SIMD families share: conv_raw3.hip (fp32 raw-window F / T) and conv_h3.hip
+//                        (bf16-resident forward), 256 x 256 tiles
+//   conv_fixup.h         fixup kernel of the stream-K split, for every family
+//   conv_igemm.hip       (this file) instantiates the fixup kernel; host side: geometry checks, grid policy and the launch
 //                        plan of a call (kernel family, tiles, grid, fixup form, column tail, packed wgrad operands), which
 //                        pg_conv_describe formats, pg_workspace_bytes_wgrad sizes and the C ABI entry points execute.
 //
@@ -40,68 +43,9 @@
 #include <cstring>
 #include <cmath>
 #include <algorithm>
-#include "conv_common.h"
+#include "conv_fixup.h"
 
 namespace {
-
-// ---- fixup: add the partial segments of every split tile in ascending workgroup order, then the epilogue ---------
-// One workgroup per (tile, 32 x 32 block of the wave tile): with few tiles and many segments (small-batch inference: 8 tiles
-// split over 512 workgroups) one workgroup per tile would read 8 MB on its own; per block the reduction is MB*NB times wider.
-// WN = waves of the GEMM kernel along N (2: tile 64 MB x 64 NB; 1: the raw "tall" tile 128 MB x 32 NB).
-// WIDE (small-batch inference: tens of segments per tile): four workgroups per block, one per wave of the GEMM kernel; the four
-// waves of a fixup workgroup each sum every fourth segment (two segments' loads in flight per wave) and wave 0 adds the four
-// sums in order -- a fixed order, chosen by the host from (grid, tiles) alone.  8 tiles x 64 segments: 36 us -> see DESIGN 4.3.
-template <int KIND, int MB, int NB, int WN = 2, bool WIDE = false>
-__global__ __launch_bounds__(NT) void conv_fixup_kernel(const IgemmParams p, int G) {
-    // WN = waves of the GEMM kernel along N: 2 -> 2 x 2 waves, 1 -> 4 x 1 (tall raw tile), 4 -> 1 x 4 (bf16-resident kernels)
-    __shared__ float red[WIDE ? 3 * 16 * 64 : 1];
-    const int unit = WIDE ? blockIdx.x >> 2 : blockIdx.x, q = WIDE ? threadIdx.x >> 6 : 0;
-    const int tid = WIDE ? (blockIdx.x & 3) * 64 + (threadIdx.x & 63) : threadIdx.x;     // the GEMM thread whose accumulators this lane sums
-    const int lane = tid & 63, wv = tid >> 6;
-    const int wm = WN == 2 ? wv >> 1 : (WN == 4 ? 0 : wv), wn = WN == 2 ? wv & 1 : (WN == 4 ? wv : 0);
-    static_assert(MB * NB * 16 == ACC_REGS, "8 blocks per wave tile: the host launches 8 workgroups per tile");
-    // hybrid split: tiles below p.whole were computed whole by one workgroup each -- the grid covers the split tiles only
-    const int tile = p.whole + unit / (MB * NB), blk = unit % (MB * NB), bi = blk / NB, bj = blk - bi * NB;
-    const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, G, p.whole);
-    const int first = tile * p.nslab, last = first + p.nslab - 1;
-    const int g0 = split_owner(sp, first), g1 = split_owner(sp, last);
-    if (g0 == g1 && split_lo(sp, g0) <= first && split_lo(sp, g0 + 1) > last) return;   // computed whole by one workgroup
-    // a 32-column block that starts past the problem's last column holds nothing (few-column problems on the tall tile: the GEMM
-    // kernel did not write it either)
-    if (KIND != 2 && p.n_lo + (tile % p.tilesN) * p.tn_stride + (WN == 2 ? wn * (NB - 1) * 32 : (WN == 4 ? wn * (NB * 32) : 0)) + bj * 32 >= p.B * (KIND == 0 ? p.Ly : p.U)) return;
-    AccT<1, 1> acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc.c[0][0][r] = 0.f;
-#pragma unroll 2
-    for (int g = g0 + q; g <= g1; g += WIDE ? 4 : 1) {
-        const int slot = (split_lo(sp, g) / p.nslab == tile) ? 0 : 1;     // the range's first segment, or its last
-        const float* src = p.ws + ((long)(g * 2 + slot) * ACC_REGS) * NT + tid;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc.c[0][0][r] += src[(blk * 16 + r) * NT];
-    }
-    if (WIDE) {         // (the returns above are uniform over the workgroup here: all four waves stand for the same GEMM wave)
-        if (q) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[((q - 1) * 16 + r) * 64 + lane] = acc.c[0][0][r];
-        }
-        __syncthreads();
-        if (q) return;
-#pragma unroll
-        for (int qq = 0; qq < 3; ++qq)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc.c[0][0][r] += red[(qq * 16 + r) * 64 + lane];
-    }
-    // the epilogues place block (0, 0) of wave (wm, wn) at m0 + wm * 32, n0 + wn * 32: shift the origin to block (bi, bj)
-    const int m0 = (tile / p.tilesN) * ((4 / WN) * 32 * MB) + wm * (MB - 1) * 32 + bi * 32;
-    // column tiles are p.tn_stride columns apart: the tile width, except the k = 5 wgrad's 255 (51 whole channels) of 256
-    const int nt0 = p.n_lo + (tile % p.tilesN) * p.tn_stride;
-    const int n0 = nt0 + wn * (NB - 1) * 32 + bj * 32;
-    if (KIND == 0) epilogue_f<0, 1, 1>(p, acc, m0, n0, lane, wm, wn);
-    else if (KIND == 3)       // stride-2 raw T kernels (phase-major rows): block row bi is phase bi of the wave's 32 output channels
-        epilogue_t_pm<1, 1>(p, acc, (tile / p.tilesN) * ((4 / WN) * 16 * MB) + wm * 32, nt0 + wn * (NB * 32) + bj * 32, lane, bi);
-    else if (KIND == 1) epilogue_t<0, 1, 1>(p, acc, m0, n0, lane, wm, wn);
-    else epilogue_g<0, 1, 1>(p, acc, m0, n0, lane, wm, wn, nt0 + p.tn_stride);
-}
 
 // ------------------------------------------------------------------------------------------------------------
 // host side
@@ -515,19 +459,26 @@ int plan_h3(const pg_convh_args* a, ConvPlan& pl) {
     return PG_OK;
 }
 
-template <int KIND, int MB, int NB, int WN>
-hipError_t fixup(const ConvPart& c, hipStream_t st) {
+// The fixup of a part's split tiles: one instantiation per (wave tile and wave grid of the family's GEMM kernel, epilogue, form).
+hipError_t launch_fixup(const ConvPlan& pl, const ConvPart& c, hipStream_t st) {
+    typedef void (*Fn)(const IgemmParams, int);
+#define FIX2(KIND, MB, NB, WN) {conv_fixup_kernel<KIND, MB, NB, WN, false>, conv_fixup_kernel<KIND, MB, NB, WN, true>}
+    static const Fn table[4][4][2] = {      // [geometry][FixupKind][wide]
+        {FIX2(FIX_F, WMB, 2, 2), FIX2(FIX_T, WMB, 2, 2), FIX2(FIX_G, WMB, 2, 2), {}},                       // im2col: 4 x 2 blocks, 2 x 2 waves
+        {FIX2(FIX_F, 2, 4, 2), FIX2(FIX_T, 2, 4, 2), FIX2(FIX_G, 2, 4, 2), FIX2(FIX_T_PM, 2, 4, 2)},        // raw 128 x 256 (F / T / G): 2 x 4, 2 x 2
+        {FIX2(FIX_F, 2, 4, 1), FIX2(FIX_T, 2, 4, 1), {}, FIX2(FIX_T_PM, 2, 4, 1)},                          // raw tall: 2 x 4, 4 x 1
+        // one wave per SIMD: 8 x 2, 1 x 4 (conv_raw3 takes the plain form only, set_grid; conv_h3 has no phase-major rows)
+        {FIX2(FIX_F, 8, 2, 4), FIX2(FIX_T, 8, 2, 4), {}, {conv_fixup_kernel<FIX_T_PM, 8, 2, 4, false>, nullptr}}};
+#undef FIX2
+    const int geom = c.fam == FAM_IM2COL ? 0 : (c.fam == FAM_RAW_TALL ? 2 : (c.fam == FAM_RAW3 || c.fam == FAM_H3 ? 3 : 1));
+    // the stride-2 raw-window T kernels (conv_raw_impl.h, conv_raw3.hip) store phase-major rows
+    const bool pm = pl.kind == KIND_T && c.p.s == 2 && (c.fam == FAM_RAW || c.fam == FAM_RAW_TALL || c.fam == FAM_RAW3);
     const bool wide = c.fixup == FIXUP_WIDE;
-    const dim3 fg((unsigned)((c.tiles - c.p.whole) * (wide ? 32 : 8)));
-    if (wide) hipLaunchKernelGGL((conv_fixup_kernel<KIND, MB, NB, WN, true>), fg, dim3(NT), 0, st, c.p, c.grid);
-    else hipLaunchKernelGGL((conv_fixup_kernel<KIND, MB, NB, WN, false>), fg, dim3(NT), 0, st, c.p, c.grid);
+    const Fn fn = table[geom][pm ? FIX_T_PM : (int)pl.kind][wide];
+    if (!fn) return hipErrorInvalidDeviceFunction;
+    const long blocks = (c.tiles - c.p.whole) * (geom == 3 ? 16 : 8) * (wide ? 4 : 1);      // (tile, block of the wave tile [, GEMM wave])
+    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(NT), 0, st, c.p, c.grid);
     return hipGetLastError();
-}
-// raw-window F / T kernels: the stride-2 T kernels store phase-major rows (fixup KIND 3)
-template <int WN>
-hipError_t fixup_raw(Kind kind, const ConvPart& c, hipStream_t st) {
-    if (kind == KIND_F) return fixup<0, 2, 4, WN>(c, st);
-    return c.p.s == 2 ? fixup<3, 2, 4, WN>(c, st) : fixup<1, 2, 4, WN>(c, st);
 }
 
 // The kernel of one part: named as rocprofv3 names it (profiles/*_kernel_stats.csv) into `name`, or, with name == NULL, launched
@@ -536,38 +487,35 @@ hipError_t part_kernel(const ConvPlan& pl, const ConvPart& c, hipStream_t st, ch
     const IgemmParams& p = c.p;
     const Kind kind = pl.kind;
     const char* tk = kind == KIND_T ? "true" : "false";
-    const bool fix = c.fixup != FIXUP_NONE;
     hipError_t e = hipSuccess;
     switch (c.fam) {
         case FAM_RAW_TALL:
             if (name) snprintf(name, 96, "conv_raw_kernel<%d, %d, %s, %d, 1>", p.k, p.s, tk, pl.prec);
-            else if ((e = pgconv::launch_raw_ft_tall(kind, p, c.grid, st, pl.prec)) == hipSuccess && fix) e = fixup_raw<1>(kind, c, st);
+            else e = pgconv::launch_raw_ft_tall(kind, p, c.grid, st, pl.prec);
             break;
         case FAM_RAW:
             if (name) snprintf(name, 96, "conv_raw_kernel<%d, %d, %s, %d, 2>", p.k, p.s, tk, pl.prec);
-            else if ((e = pgconv::launch_raw_ft(kind, p, c.grid, st, pl.prec)) == hipSuccess && fix) e = fixup_raw<2>(kind, c, st);
+            else e = pgconv::launch_raw_ft(kind, p, c.grid, st, pl.prec);
             break;
         case FAM_G_RAW:
         case FAM_G_PS:          // (fp32: the launcher packs the operands first)
             if (name) snprintf(name, 96, "conv_g_%s_kernel<%d, %d, %d>", c.fam == FAM_G_PS ? "ps" : "raw", p.k, p.s, pl.prec);
-            else if ((e = pgconv::launch_raw_g(p, c.grid, st, pl.prec)) == hipSuccess && fix) e = fixup<2, 2, 4, 2>(c, st);
+            else e = pgconv::launch_raw_g(p, c.grid, st, pl.prec);
             break;
         case FAM_IM2COL:
             if (name) snprintf(name, 96, "conv_%c_kernel<0, 0, %d>", "ftg"[kind], pl.prec);
-            else if ((e = pgconv::launch_im2col(kind, p, c.grid, st, pl.prec)) == hipSuccess && fix)
-                e = kind == KIND_F ? fixup<0, WMB, 2, 2>(c, st) : (kind == KIND_T ? fixup<1, WMB, 2, 2>(c, st) : fixup<2, WMB, 2, 2>(c, st));
+            else e = pgconv::launch_im2col(kind, p, c.grid, st, pl.prec);
             break;
         case FAM_RAW3:
             if (name) snprintf(name, 96, "conv_raw3_kernel<%d, %d, %s, %s>", p.k, p.s, tk, p.act_x == PG_ACT_NONE ? "false" : "true");
-            else if ((e = pgconv::launch_raw3(kind, p, c.grid, st)) == hipSuccess && fix)
-                e = pgconv::launch_raw3_fixup(kind, p, c.grid, (unsigned)((c.tiles - p.whole) * 16), st);
+            else e = pgconv::launch_raw3(kind, p, c.grid, st);
             break;
         case FAM_H3:
             if (name) snprintf(name, 96, "conv_h3_kernel<%d, %d, %s>", kind == KIND_T && p.k == 5 ? 8 : p.k, p.s, tk);
-            else if ((e = pgconv::launch_h3(kind, p, c.grid, st)) == hipSuccess && fix)
-                e = pgconv::launch_h3_fixup(kind, p, c.grid, (unsigned)(c.tiles - p.whole), c.fixup == FIXUP_WIDE, st);
+            else e = pgconv::launch_h3(kind, p, c.grid, st);
             break;
     }
+    if (!name && e == hipSuccess && c.fixup != FIXUP_NONE) e = launch_fixup(pl, c, st);
     return e;
 }
 

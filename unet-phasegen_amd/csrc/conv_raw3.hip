@@ -15,32 +15,15 @@
 // Covered: fp32 operands (precision 0), F: k = 32 / 8 / 4 at stride 2 and k = 8 at stride 1; T: k = 32 / 8 / 4 at stride 2 (phase-major
 // weight image), k = 8 at stride 1, and k = 5 at stride 2 in both forms (a virtual k = 8); whole 16-deep slabs only (Cin a multiple of
 // 16 / taps-per-channel).  Everything else -- the bf16 operand modes, K tails, small problems -- stays on conv_raw.hip / conv_raw_tall.hip / conv_im2col.hip.
-#include "conv_common.h"
+#include "conv_w1.h"
 
 namespace {
 
-constexpr int NT3 = 256;                  // threads per workgroup
 constexpr int R3_RING = 3;
-constexpr int R3_REGS = 256;              // accumulator registers per thread: 16 blocks x 16
 constexpr int R3_TM = 256, R3_TN = 256;
 constexpr int R3_SLOTS = 12;              // gather slots per half-slab (behind MFMAs 12, 16, ... 56 of its 64)
 
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-
-template <int N> __device__ __forceinline__ void r3_wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit count");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-__device__ __forceinline__ void r3_lgkm0() { __builtin_amdgcn_s_waitcnt(0xc07f); }      // lgkmcnt(0), the other counters untouched
-__device__ __forceinline__ unsigned r3_lds_addr(const float* p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) float*)p;
-}
-// an accumulator register read where it is USED (conv_h3.hip: h3_acc)
-__device__ __forceinline__ float r3_acc(float v) {
-    float x;
-    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(v));
-    return x;
-}
 
 // ---- fragments of one HALF-slab: k = 8 h + 4 c + 0..3 of a 16-deep slab (lane half h, half-slab c) ---------------------------
 // A (weight tile): eight ds_read_b128.  Plain image (F, T at stride 1): 16-byte group (2 h + c) of row r of each of the 8 row blocks,
@@ -53,12 +36,12 @@ __device__ __forceinline__ float r3_acc(float v) {
 struct R3Frag { f32x4 a[8]; unsigned d[2][4]; float b[2][4]; };
 
 template <bool PM> __device__ __forceinline__ unsigned r3_a_addr(const float* stage, int c, int r, int h) {
-    if (PM) return r3_lds_addr(stage) + (r * 32 + (((4 * h + 2 * c) ^ ((r >> 1) & 7)) << 2)) * 4;
-    return r3_lds_addr(stage) + (r * 16 + (((2 * h + c) ^ ((r >> 2) & 3)) << 2)) * 4;
+    if (PM) return w1_lds_addr(stage) + (r * 32 + (((4 * h + 2 * c) ^ ((r >> 1) & 7)) << 2)) * 4;
+    return w1_lds_addr(stage) + (r * 16 + (((2 * h + c) ^ ((r >> 2) & 3)) << 2)) * 4;
 }
 // PM: the pair's second group is the first XOR 1 -> its address differs by +-16 bytes depending on the lane: a second register
 template <bool PM> __device__ __forceinline__ unsigned r3_a_addr2(const float* stage, int c, int r, int h) {
-    return r3_lds_addr(stage) + (r * 32 + (((4 * h + 2 * c + 1) ^ ((r >> 1) & 7)) << 2)) * 4;
+    return w1_lds_addr(stage) + (r * 32 + (((4 * h + 2 * c + 1) ^ ((r >> 1) & 7)) << 2)) * 4;
 }
 template <bool PM, int I> __device__ __forceinline__ void r3_load_a(unsigned a0, unsigned a1, R3Frag& f) {
     if (PM) {       // I = 2 ob + t: group t of channel block ob (32 rows x 128 bytes = 4096 bytes per block)
@@ -79,7 +62,7 @@ __device__ __forceinline__ unsigned r3_b_addr(const float* bw, int c, int h, int
     const int lanepart = (TJ == 16) ? (DESC ? -8 * h : 8 * h) : (8 / TJ) * h * RS;
     // TJ = 4: the half-slab is one channel's four taps; TJ = 2: two channels' two taps each (the second RS floats further: r3_load_b)
     const int so = TJ >= 8 ? (DESC ? 4 - 4 * c : 4 * c) : (TJ == 4 ? c * RS : 2 * c * RS);
-    return r3_lds_addr(bw) + (bbase_jb + lanepart - (DESC ? TD - 1 : 0) + so) * 4;
+    return w1_lds_addr(bw) + (bbase_jb + lanepart - (DESC ? TD - 1 : 0) + so) * 4;
 }
 // W2 = byte distance of the pair's second read: 0 -> dwords 2, 3 of the same run; else (TJ = 2) dwords 0, 1 of the next channel's window
 template <int JB, int P, int W2 = 0> __device__ __forceinline__ void r3_load_b(unsigned b_addr, R3Frag& f) {
@@ -155,7 +138,7 @@ __device__ __forceinline__ void r3_half(const R3Frag& cur, R3Frag& nxt, const fl
     R3_CHUNK(61, (void)0)
     nxt = cur;
 #else
-    R3_CHUNK(60, r3_lgkm0())
+    R3_CHUNK(60, w1_lgkm0())
     __builtin_amdgcn_sched_barrier(0);
     R3_CHUNK(61, (r3_finish_b<DESC, ACT, TJ == 2>(nxt, slope)))
 #endif
@@ -166,19 +149,9 @@ __device__ __forceinline__ void r3_half(const R3Frag& cur, R3Frag& nxt, const fl
 #undef R3_CHUNK
 }
 
-__device__ __forceinline__ void store_partial_r3(float* ws, int g, int slot, const AccT<8, 2>& acc, int tid) {
-    float* dst = ws + ((long)(g * 2 + slot) * R3_REGS) * NT3 + tid;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dst[((i * 2 + j) * 16 + r) * NT3] = r3_acc(acc.c[i][j][r]);
-}
-
 // TKIND false: F (conv fwd / convT dgrad);  TKIND true: T (convT fwd / conv dgrad in gather form)
 template <int KW, int S, bool TKIND, bool ACT>
-__global__ __launch_bounds__(NT3, 1) void conv_raw3_kernel(const IgemmParams p) {
+__global__ __launch_bounds__(W1_NT, 1) void conv_raw3_kernel(const IgemmParams p) {
     constexpr int TM = R3_TM, TN = R3_TN;
     constexpr int TA = TM * BK;                       // floats of the weight tile (16 KB)
     constexpr int AE16 = TM / 64;                     // 16-byte gather instructions per wave for the weight tile
@@ -192,7 +165,7 @@ __global__ __launch_bounds__(NT3, 1) void conv_raw3_kernel(const IgemmParams p) 
     constexpr bool PM = TKIND && S == 2;              // phase-major weight image
     constexpr bool T16 = TKIND && S == 1;             // taps of a channel contiguous in memory and in K
     constexpr int RS = SC == 1 ? RS1 : RS2;           // floats reserved per channel window
-    constexpr int NPC = (RS + NT3 - 1) / NT3;         // gather pieces per thread and window
+    constexpr int NPC = (RS + W1_NT - 1) / W1_NT;         // gather pieces per thread and window
     constexpr int NT0 = (!TKIND && KWP == 32) ? 2 : 1;   // F with 32-tap channels: a channel spans two slabs (tap offset 0 / 16)
     constexpr int STG = TA + NQ * RS;                 // floats per LDS stage (one slab)
     constexpr int ND = AE16 + NQ * NPC;               // gathers per wave and slab
@@ -214,14 +187,10 @@ __global__ __launch_bounds__(NT3, 1) void conv_raw3_kernel(const IgemmParams p) 
     const int wq = p.M * KW;                          // T: weight stride between input channels
     const int pm_f = ((lane & 7) ^ (((wv & 1) << 2) | (lane >> 4))) << 2;      // conv_raw_impl.h: the logical chunk this lane carries
     const int pm_ql = pm_f / (2 * TJ), pm_within = pm_f - pm_ql * 2 * TJ;
-    const int g = logical_wg(blockIdx.x, gridDim.x, p.whole);
-    const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, gridDim.x, p.whole);
-    int pos = split_lo(sp, g);
-    const int pos_end = split_lo(sp, g + 1);
-    int slot = 0;
-    while (pos < pos_end) {
-        const int tile = pos / p.nslab, sb = pos - tile * p.nslab;
-        const int se = min(p.nslab, sb + (pos_end - pos));
+    Walk wk(p);
+    while (wk.more()) {
+        int tile, sb, se;
+        wk.segment(p, tile, sb, se);
         int tmi, tni;
         tile_decode(p, tile, tmi, tni);
         const int m0 = tmi * TM, n0 = tni * TN;
@@ -308,15 +277,15 @@ __global__ __launch_bounds__(NT3, 1) void conv_raw3_kernel(const IgemmParams p) 
         // slab i + 2 is gathered into slab i - 1's stage from slab i's first half on, and the last reads of that stage (slab i - 1's
         // second-half fragments) were issued and waited for in slab i - 1's FIRST half, in front of slab i - 1's barrier.
         auto wait_first = [&]() {
-            r3_wait_vmcnt<ND>();
+            w1_wait_vmcnt<ND>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         };
         auto wait_next = [&]() {
 #if defined(PG_R3_DBG) || defined(PG_R3_ABL)
-            r3_wait_vmcnt<0>();
+            w1_wait_vmcnt<0>();
 #else
-            r3_wait_vmcnt<ND0>();
+            w1_wait_vmcnt<ND0>();
 #endif
 #if !(defined(PG_R3_ABL) && PG_R3_ABL == 5)
             __builtin_amdgcn_s_barrier();
@@ -337,7 +306,7 @@ __global__ __launch_bounds__(NT3, 1) void conv_raw3_kernel(const IgemmParams p) 
             r3_load_b<0, 0, W2>(b0a, f0); r3_load_b<0, 1, W2>(b0a, f0); r3_load_b<1, 0, W2>(b1a, f0); r3_load_b<1, 1, W2>(b1a, f0);
             r3_load_a<PM, 0>(a0, a1, f0); r3_load_a<PM, 1>(a0, a1, f0); r3_load_a<PM, 2>(a0, a1, f0); r3_load_a<PM, 3>(a0, a1, f0);
             r3_load_a<PM, 4>(a0, a1, f0); r3_load_a<PM, 5>(a0, a1, f0); r3_load_a<PM, 6>(a0, a1, f0); r3_load_a<PM, 7>(a0, a1, f0);
-            r3_lgkm0();
+            w1_lgkm0();
             __builtin_amdgcn_sched_barrier(0);
             r3_finish_b<TKIND, ACT, TJ == 2>(f0, slopeB);
         }
@@ -360,26 +329,19 @@ __global__ __launch_bounds__(NT3, 1) void conv_raw3_kernel(const IgemmParams p) 
         // the accumulator reads below are `asm`: the wait states an MFMA result needs before a VALU may read it, spelled out
         asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15");
 #if defined(PG_R3_ABL) && PG_R3_ABL == 7      /* 4 + no epilogue: one store per wave keeps the loop alive */
-        if (p.nslab < 0) store_partial_r3(p.ws, g, slot, acc, tid);
-        else if (lane == 0) p.y[wv] = r3_acc(acc.c[0][0][0]);
-        pos += se - sb; slot = 1; continue;
+        if (p.nslab < 0) store_partial<true>(p.ws, wk.g, wk.slot, acc, tid);
+        else if (lane == 0) p.y[wv] = acc_agpr(acc.c[0][0][0]);
+        wk.next(se - sb); continue;
 #endif
         if (sb == 0 && se == p.nslab) {
 #define R3_EPI(I, J)                                                                                              \
-    {   AccT<1, 1> blk;                                                                                          \
-        _Pragma("unroll") for (int q = 0; q < 16; ++q) blk.c[0][0][q] = r3_acc(acc.c[I][J][q]);                  \
-        __builtin_amdgcn_sched_barrier(0);                                                                       \
-        if (PM) epilogue_t_pm<1, 1>(p, blk, m0 / 2 + ((I) >> 1) * 32, n0 + (wn * 2 + (J)) * 32, lane, (I) & 1);  \
-        else if (TKIND) epilogue_t<S, 1, 1>(p, blk, m0 + (I) * 32, n0 + (wn * 2 + (J)) * 32, lane, 0, 0);        \
-        else epilogue_f<S, 1, 1>(p, blk, m0 + (I) * 32, n0 + (wn * 2 + (J)) * 32, lane, 0, 0);                   \
-        __builtin_amdgcn_sched_barrier(0);                                                                       \
-    }
-            R3_EPI(0, 0) R3_EPI(0, 1) R3_EPI(1, 0) R3_EPI(1, 1) R3_EPI(2, 0) R3_EPI(2, 1) R3_EPI(3, 0) R3_EPI(3, 1)
-            R3_EPI(4, 0) R3_EPI(4, 1) R3_EPI(5, 0) R3_EPI(5, 1) R3_EPI(6, 0) R3_EPI(6, 1) R3_EPI(7, 0) R3_EPI(7, 1)
+    if (PM) epilogue_t_pm<1, 1>(p, blk, m0 / 2 + ((I) >> 1) * 32, n0 + (wn * 2 + (J)) * 32, lane, (I) & 1);      \
+    else if (TKIND) epilogue_t<S, 1, 1>(p, blk, m0 + (I) * 32, n0 + (wn * 2 + (J)) * 32, lane, 0, 0);            \
+    else epilogue_f<S, 1, 1>(p, blk, m0 + (I) * 32, n0 + (wn * 2 + (J)) * 32, lane, 0, 0)
+            W1_EPILOGUE(R3_EPI)
 #undef R3_EPI
-        } else store_partial_r3(p.ws, g, slot, acc, tid);
-        pos += se - sb;
-        slot = 1;
+        } else store_partial<true>(p.ws, wk.g, wk.slot, acc, tid);
+        wk.next(se - sb);
     }
 #if PG_ABL == 8
     if (tid == 0 && p.ws && blockIdx.x == gridDim.x / 2) {
@@ -390,43 +352,11 @@ __global__ __launch_bounds__(NT3, 1) void conv_raw3_kernel(const IgemmParams p) 
 #endif
 }
 
-// fixup of the stream-K split: one workgroup per (split tile, 32 x 32 block of the wave tile: 16 of them).
-// KIND 0: F, 1: T at stride 1, 3: T at stride 2 (phase-major rows: block row bi = phase bi & 1 of channel block bi >> 1)
-template <int KIND>
-__global__ __launch_bounds__(NT3) void conv_raw3_fixup_kernel(const IgemmParams p, int G) {
-    constexpr int MB = 8, NB = 2;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int tile = p.whole + blockIdx.x / (MB * NB), blk = blockIdx.x % (MB * NB), bi = blk / NB, bj = blk - bi * NB;
-    const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, G, p.whole);
-    const int first = tile * p.nslab, last = first + p.nslab - 1;
-    const int g0 = split_owner(sp, first), g1 = split_owner(sp, last);
-    if (g0 == g1 && split_lo(sp, g0) <= first && split_lo(sp, g0 + 1) > last) return;
-    AccT<1, 1> acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc.c[0][0][r] = 0.f;
-    for (int g = g0; g <= g1; ++g) {
-        const int slot = (split_lo(sp, g) / p.nslab == tile) ? 0 : 1;
-        const float* src = p.ws + ((long)(g * 2 + slot) * R3_REGS) * NT3 + tid;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc.c[0][0][r] += src[(blk * 16 + r) * NT3];
-    }
-    int tmi, tni;
-    tile_decode(p, tile, tmi, tni);
-    const int mt = tmi * R3_TM, n0 = tni * p.tn_stride + (wv * NB + bj) * 32;
-    if (KIND == 0) epilogue_f<0, 1, 1>(p, acc, mt + bi * 32, n0, lane, 0, 0);
-    else if (KIND == 1) epilogue_t<0, 1, 1>(p, acc, mt + bi * 32, n0, lane, 0, 0);
-    else epilogue_t_pm<1, 1>(p, acc, mt / 2 + (bi >> 1) * 32, n0, lane, bi & 1);
-}
-
 template <int KW, int S, bool TK, bool ACT>
 hipError_t launch3a(const IgemmParams& p, int grid, hipStream_t st) {
     constexpr int KWV = KW == 5 ? 8 : KW, KWP = TK ? KWV / S : KWV, TJ = KWP < 16 ? KWP : 16, NQ = 16 / TJ, SC = TK ? 1 : S;
     constexpr int lds_bytes = R3_RING * (R3_TM * BK + NQ * (SC == 1 ? RS1 : RS2)) * 4;
-    // (the attribute belongs to (function, current device): set on every call, nothing cached between calls)
-    hipError_t e = hipFuncSetAttribute((const void*)conv_raw3_kernel<KW, S, TK, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((conv_raw3_kernel<KW, S, TK, ACT>), dim3(grid), dim3(NT3), lds_bytes, st, p);
-    return hipGetLastError();
+    return w1_launch(conv_raw3_kernel<KW, S, TK, ACT>, lds_bytes, p, grid, st);
 }
 template <int KW, int S, bool TK>
 hipError_t launch3(const IgemmParams& p, int grid, hipStream_t st) {
@@ -454,11 +384,4 @@ hipError_t pgconv::launch_raw3(int kind, const IgemmParams& p, int grid, hipStre
     if (p.k == 5) return launch3<5, 2, true>(p, grid, st);
     if (p.s == 1) return launch3<8, 1, true>(p, grid, st);
     return launch3<8, 2, true>(p, grid, st);
-}
-
-hipError_t pgconv::launch_raw3_fixup(int kind, const IgemmParams& p, int grid, unsigned blocks, hipStream_t st) {
-    if (kind == KIND_F) hipLaunchKernelGGL((conv_raw3_fixup_kernel<0>), dim3(blocks), dim3(NT3), 0, st, p, grid);
-    else if (p.s == 2) hipLaunchKernelGGL((conv_raw3_fixup_kernel<3>), dim3(blocks), dim3(NT3), 0, st, p, grid);
-    else hipLaunchKernelGGL((conv_raw3_fixup_kernel<1>), dim3(blocks), dim3(NT3), 0, st, p, grid);
-    return hipGetLastError();
 }

@@ -195,14 +195,10 @@ __global__ __launch_bounds__(NT, 2) void conv_raw_kernel(const IgemmParams p) {
     // channel ql of the slab, taps `within ..` of W[q][o][:]
     const int pm_f = ((lane & 7) ^ (((wv & 1) << 2) | (lane >> 4))) << 2;
     const int pm_ql = pm_f / (2 * TJ), pm_within = pm_f - pm_ql * 2 * TJ;
-    const int g = logical_wg(blockIdx.x, gridDim.x, p.whole);
-    const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, gridDim.x, p.whole);
-    int pos = split_lo(sp, g);
-    const int pos_end = split_lo(sp, g + 1);
-    int slot = 0;
-    while (pos < pos_end) {
-        const int tile = pos / p.nslab, sb = pos - tile * p.nslab;
-        const int se = min(p.nslab, sb + (pos_end - pos));
+    Walk wk(p);
+    while (wk.more()) {
+        int tile, sb, se;
+        wk.segment(p, tile, sb, se);
         const int m0 = (tile / p.tilesN) * TM, n0 = p.n_lo + (tile % p.tilesN) * TN;
         const int b0 = n0 / Lcol, t0 = n0 - b0 * Lcol;            // sample / position of the tile's first column
         const int nseg = (t0 + TN - 1) / Lcol + 1;
@@ -401,9 +397,8 @@ __global__ __launch_bounds__(NT, 2) void conv_raw_kernel(const IgemmParams p) {
             if (PM) epilogue_t_pm<2, 4>(p, acc, m0 / 2 + wm * 32, n0 + wn * 128, lane, 0);
             else if (TKIND) epilogue_t<S, 2, 4>(p, acc, m0, n0, lane, wm, wn);
             else epilogue_f<S, 2, 4>(p, acc, m0, n0, lane, wm, wn);
-        } else store_partial(p.ws, g, slot, acc, tid, nbv);
-        pos += se - sb;
-        slot = 1;
+        } else store_partial(p.ws, wk.g, wk.slot, acc, tid, nbv * 32);
+        wk.next(se - sb);
     }
 #if PG_ABL == 8
     if (tid == 0 && p.ws && blockIdx.x == gridDim.x / 2) {

@@ -37,14 +37,10 @@ __device__ __forceinline__ void g_raw_bf(const IgemmParams& p) {
     const rsrc_t rp = make_rsrc(p.pt, p.pt_bytes), rx = make_rsrc(p.x, p.x_bytes);
     const float slopeA = pg_act_slope(p.act_p), slopeB = pg_act_slope(p.act_x);
     const int pbs4 = (int)p.pt_bs * 4, xbs4 = (int)p.x_bs * 4;
-    const int g = logical_wg(blockIdx.x, gridDim.x, p.whole);
-    const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, gridDim.x, p.whole);
-    int pos = split_lo(sp, g);
-    const int pos_end = split_lo(sp, g + 1);
-    int slot = 0;
-    while (pos < pos_end) {
-        const int tile = pos / p.nslab, sb = pos - tile * p.nslab;
-        const int se = min(p.nslab, sb + (pos_end - pos));
+    Walk wk(p);
+    while (wk.more()) {
+        int tile, sb, se;
+        wk.segment(p, tile, sb, se);
         const int m0 = (tile / p.tilesN) * RBM, n0 = (tile % p.tilesN) * C::TNV;
         const int qbase = (tile % p.tilesN) * C::NQT;
 
@@ -253,9 +249,8 @@ __device__ __forceinline__ void g_raw_bf(const IgemmParams& p) {
 #undef GRAW_CHOFF
 #undef GRAW_VV
         if (sb == 0 && se == p.nslab) epilogue_g<S, 2, 4>(p, acc, m0, n0, lane, wm, wn, n0 + C::TNV);
-        else store_partial(p.ws, g, slot, acc, tid);
-        pos += se - sb;
-        slot = 1;
+        else store_partial(p.ws, wk.g, wk.slot, acc, tid);
+        wk.next(se - sb);
     }
 }
 
@@ -288,14 +283,10 @@ __device__ __forceinline__ void g_ps_bf(const IgemmParams& p) {
     const float slopeA = pg_act_slope(p.act_p), slopeB = pg_act_slope(p.act_x);
     const int pbs4 = (int)p.pt_bs * 4, xbs4 = (int)p.x_bs * 4;
     const int cps = (p.LP + 15) >> 4;                                  // slabs (chunks of 16 frames) per sample
-    const int g = logical_wg(blockIdx.x, gridDim.x, p.whole);
-    const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, gridDim.x, p.whole);
-    int pos = split_lo(sp, g);
-    const int pos_end = split_lo(sp, g + 1);
-    int slot = 0;
-    while (pos < pos_end) {
-        const int tile = pos / p.nslab, sb = pos - tile * p.nslab;
-        const int se = min(p.nslab, sb + (pos_end - pos));
+    Walk wk(p);
+    while (wk.more()) {
+        int tile, sb, se;
+        wk.segment(p, tile, sb, se);
         const int m0 = (tile / p.tilesN) * RBM, n0 = (tile % p.tilesN) * C::TNV;
         const int qbase = (tile % p.tilesN) * C::NQT;
 
@@ -421,9 +412,8 @@ __device__ __forceinline__ void g_ps_bf(const IgemmParams& p) {
 #undef GPS_ISSUE
         (void)mb;
         if (sb == 0 && se == p.nslab) epilogue_g<S, 2, 4>(p, acc, m0, n0, lane, wm, wn, n0 + C::TNV);
-        else store_partial(p.ws, g, slot, acc, tid);
-        pos += se - sb;
-        slot = 1;
+        else store_partial(p.ws, wk.g, wk.slot, acc, tid);
+        wk.next(se - sb);
     }
 }
 
@@ -455,14 +445,10 @@ __device__ __forceinline__ void g_raw_f32(const IgemmParams& p) {
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wv >> 1, wn = wv & 1;
     const rsrc_t rp = make_rsrc(p.pk, p.pk_bytes), rx = make_rsrc(p.qk, p.qk_bytes);
     const int qbs4 = p.qk_bs * 4, klast4 = (p.nslab - 1) * BK * 4;
-    const int g = logical_wg(blockIdx.x, gridDim.x, p.whole);
-    const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, gridDim.x, p.whole);
-    int pos = split_lo(sp, g);
-    const int pos_end = split_lo(sp, g + 1);
-    int slot = 0;
-    while (pos < pos_end) {
-        const int tile = pos / p.nslab, sb = pos - tile * p.nslab;
-        const int se = min(p.nslab, sb + (pos_end - pos));
+    Walk wk(p);
+    while (wk.more()) {
+        int tile, sb, se;
+        wk.segment(p, tile, sb, se);
         const int m0 = (tile / p.tilesN) * RBM, n0 = (tile % p.tilesN) * C::TNV;
         const int qbase = (tile % p.tilesN) * C::NQT;
         int pv[2], woff[NE2];
@@ -575,9 +561,8 @@ __device__ __forceinline__ void g_raw_f32(const IgemmParams& p) {
         PG_STAMP_FLUSH
 #undef GRF_ISSUE
         if (sb == 0 && se == p.nslab) epilogue_g<S, 2, 4>(p, acc, m0, n0, lane, wm, wn, n0 + C::TNV);
-        else store_partial(p.ws, g, slot, acc, tid);
-        pos += se - sb;
-        slot = 1;
+        else store_partial(p.ws, wk.g, wk.slot, acc, tid);
+        wk.next(se - sb);
     }
 }
 
@@ -594,6 +579,7 @@ __device__ __forceinline__ void g_ps_f32(const IgemmParams& p) {
     const rsrc_t rp = make_rsrc(p.pk, p.pk_bytes), rx = make_rsrc(p.qk, p.qk_bytes);
     const int pbs4 = p.M * p.Kp * 4, qbs4 = p.qk_bs * 4;
     const int cps = p.Kp >> 4;                                         // slabs (chunks of 16 frames) per sample
+    // (the walk written out: through Walk hipcc orders a handful of scalar instructions of this kernel differently)
     const int g = logical_wg(blockIdx.x, gridDim.x, p.whole);
     const Split sp = make_split(p.tilesM * p.tilesN, p.nslab, gridDim.x, p.whole);
     int pos = split_lo(sp, g);
