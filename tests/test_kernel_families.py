@@ -236,3 +236,122 @@ def test_every_fixup_instantiation_is_reached_by_a_small_case():
     # 25 instantiations: 2 forms x (im2col F T G, raw 128 x 256 F T Tpm G, raw tall F T Tpm, one wave per SIMD F T) + conv_raw3's plain
     # Tpm; conv_raw3 and conv_h3 share the plain F and T ones, so the table names 27 (family, epilogue, form) triples
     assert len(reached) == 27, sorted(reached)
+
+
+# ---- the engine's argument patterns (tests/test_z_conv_views_gpu.py runs every row) -----------------------------------------------
+# phasegen/unet.py hands the conv entry points channel slices of wider buffers, fuses an activation (and a second output) into the
+# forward's store and accumulates the dgrad into its own addend.  VIEW_CASES are the small problems on which the GPU module runs
+# those patterns through every kernel family's own epilogue and through every fixup instantiation, in FIXUP_CASES' row format with
+# "none" (no tile is split) and "tail" (conv_raw3 over the full 256-wide tiles, the tall tile over the rest) as further forms.
+
+
+def _one_tile_per_workgroup(case):
+    """the same problem with work-split bits 0-1 = 1 (family bits kept: 6 -> 5, 10 -> 9, 2 -> 1, 0x4002 -> 0x4001): the GEMM kernel's
+    own epilogue stores every tile"""
+    geom, op, sched, fam, epi, _ = case
+    return (geom, op, (sched & ~3) | 1, fam, epi, "none")
+
+
+TAIL = 0x40000 | 0x4000         # conv_raw3 wherever it covers the problem, its column tail always split off
+VIEW_CASES = FIXUP_CASES + [_one_tile_per_workgroup(c) for c in FIXUP_CASES] + [
+    # column tails.  F: 5 x 63 = 315 columns.  T / Tpm forward and an F dgrad (add / ref through the tail's epilogue): rows of
+    # test_ops_gpu._random_geoms_one_wave(32, 20261005) whose plan has a tail.  No Conv1d dgrad of that sweep has one (their columns are
+    # B * U <= 256, or the window does not fit), so the two T-form dgrads are the k = 8 layers with the F row's 5 x 63 / 3 x 100 columns
+    ((F_, 32, 250, 8, 2, 1, 130, 5), "fwd", TAIL, "conv_raw3", "F", "tail"), ((T_, 250, 96, 8, 2, 6, 129, 2), "dgrad", TAIL, "conv_raw3", "F", "tail"),
+    ((T_, 16, 470, 8, 1, 2, 100, 5), "fwd", TAIL, "conv_raw3", "T", "tail"), ((F_, 250, 32, 8, 1, 2, 100, 3), "dgrad", TAIL, "conv_raw3", "T", "tail"),
+    ((T_, 32, 250, 32, 2, 25, 129, 5), "fwd", TAIL, "conv_raw3", "Tpm", "tail"), ((F_, 125, 32, 8, 2, 1, 130, 5), "dgrad", TAIL, "conv_raw3", "Tpm", "tail"),
+    # packed fp32 wgrads (test_wgrad_packed_gpu.GEOMS[0], [2], [-1]): flat K, per-sample slabs, k = 5's 255-column tiles
+    ((F_, 40, 48, 32, 2, 16, 258, 2), "wgrad", 1, "conv_g_raw", "G", "none"), ((F_, 40, 48, 32, 2, 16, 258, 2), "wgrad", 2, "conv_g_raw", "G", "wide"),
+    ((F_, 33, 40, 8, 1, 2, 129, 3), "wgrad", 1, "conv_g_ps", "G", "none"), ((F_, 33, 40, 8, 1, 2, 129, 3), "wgrad", 2, "conv_g_ps", "G", "wide"),
+    ((T_, 64, 103, 5, 2, 1, 30, 2), "wgrad", 1, "conv_g_ps", "G", "none"), ((T_, 64, 103, 5, 2, 1, 30, 2), "wgrad", 2, "conv_g_ps", "G", "plain"),
+    # runtime (k, s) = (7, 3) and its transposed twin (test_ops_gpu.GEOMS): the im2col kernels' S = 0 instantiation
+    ((F_, 24, 40, 7, 3, 2, 50, 2), "fwd", 0, "conv_f", "F", "none"), ((F_, 24, 40, 7, 3, 2, 50, 2), "dgrad", 0, "conv_t", "T", "none"),
+    ((F_, 24, 40, 7, 3, 2, 50, 2), "wgrad", 0, "conv_g", "G", "none"), ((T_, 24, 40, 7, 3, 2, 17, 2), "fwd", 0, "conv_t", "T", "none"),
+    ((T_, 24, 40, 7, 3, 2, 17, 2), "dgrad", 0, "conv_f", "F", "none"), ((T_, 24, 40, 7, 3, 2, 17, 2), "wgrad", 0, "conv_g", "G", "none"),
+]
+# families with bf16 / bf16x3 operand modes of their own (conv_raw3 is fp32 only: its problems go to conv_raw at those precisions)
+BF16_FAMILIES = ("conv_f", "conv_t", "conv_g", "conv_raw(128x256)", "conv_raw(tall 256x128)", "conv_g_raw", "conv_g_ps")
+# (channel offset, further channels behind) of a view inside its buffer: 4 channels in front leave the view 16-byte aligned whatever
+# the frame count; 1 in front puts it an odd number of floats into the buffer where the frame count is odd (a base pointer aligned to 4
+# bytes only) and keeps the sibling directly in front where it is even
+VIEW_PAIRS = ((4, 1), (1, 2))
+
+
+def view_layout(case, pair):
+    """{operand: (channel offset, channels behind, channels, frames, batch stride)} of a row's call under VIEW_PAIRS[pair]: every
+    operand a channel slice buf[:, off:off + C] of a (B, off + C + extra, L) buffer of its own width, so that no two batch strides of a
+    call are equal; "xb": the forward's / wgrad's x as batch[:, 0] of a (B, 2, C, L) batch."""
+    (tr, Cin, Cout, k, s, p, Lin, B), op = case[0], case[1]
+    Lout = (Lin - 1) * s - 2 * p + k if tr else (Lin + 2 * p - k) // s + 1
+    names = {"fwd": ("x", "y", "y2"), "dgrad": ("dy", "dx", "add", "ref"), "wgrad": ("dy",)}[op]
+    off, extra = VIEW_PAIRS[pair]
+    out, seen = {}, set()
+    if op != "dgrad":
+        out["xb"] = (0, 0, Cin, Lin, 2 * Cin * Lin)
+        seen.add(2 * Cin * Lin)
+    for i, n in enumerate(names):
+        C, L = (Cin, Lin) if n in ("x", "dx", "add", "ref") else (Cout, Lout)
+        e = extra + i
+        while (off + C + e) * L in seen or (off + C + e) * L == C * L:
+            e += 1
+        seen.add((off + C + e) * L)
+        out[n] = (off, e, C, L, (off + C + e) * L)
+    return out
+
+
+def _view_args(_lib, case, pair, precision=0):
+    """the row's ConvArgs with the batch strides the GPU module passes (pair None: dense)"""
+    tr, Cin, Cout, k, s, p, Lin, B = case[0]
+    a = _args(_lib, B, Cin, Cout, Lin, k, s, p, tr, precision=precision, schedule=case[2])
+    if case[1] == "fwd":
+        a.y2, a.y2_bs, a.y_act, a.y2_act = 4096, a.y_bs, 1, 2
+    if case[1] == "dgrad":
+        a.dx_add, a.dx_add_bs, a.dx_ref, a.dx_ref_bs, a.dx_mask = 4096, a.dx_bs, 4096, a.dx_bs, 1
+    if pair is not None:
+        lay = view_layout(case, pair)
+        for n, f in (("x", "x_bs"), ("y", "y_bs"), ("y2", "y2_bs"), ("dy", "dy_bs"), ("dx", "dx_bs"), ("add", "dx_add_bs"), ("ref", "dx_ref_bs")):
+            if n in lay:
+                setattr(a, f, lay[n][4])
+        if case[1] == "wgrad":
+            a.x_bs = lay["xb"][4]
+    return a
+
+
+def _opcode(_lib, case):
+    return {"fwd": (_lib.OP_CONV1D_FWD, _lib.OP_CONVT1D_FWD), "dgrad": (_lib.OP_CONV1D_DGRAD, _lib.OP_CONVT1D_DGRAD),
+            "wgrad": (_lib.OP_CONV1D_WGRAD, _lib.OP_CONVT1D_WGRAD)}[case[1]][case[0][0]]
+
+
+def test_view_cases_plan_is_the_declared_one_and_independent_of_strides():
+    """Every VIEW_CASES row's plan names the row's family, epilogue and fixup form ("tail": a conv_raw3 launch plus the tall-tile tail),
+    and is the same string for dense operands, for both view layouts of tests/test_z_conv_views_gpu.py and for the forward's x given as
+    batch[:, 0]: the GPU module may compare a call on views bit for bit with the call on dense copies.  The rows whose family has bf16
+    operand modes keep it (and their epilogue and form) at those precisions."""
+    from phasegen import _lib, ops
+    assert VIEW_CASES[:len(FIXUP_CASES)] == FIXUP_CASES and len(set(VIEW_CASES)) == len(VIEW_CASES)
+    for case in VIEW_CASES:
+        geom, op, sched, fam, epi, form = case
+        opc = _opcode(_lib, case)
+        for prec in (0, 1, 2) if fam in BF16_FAMILIES else (0,):
+            dense = ops.conv_describe(_view_args(_lib, case, None, prec), opc)
+            f = _fields(dense)
+            assert (family(dense), _epilogue(dense)) == (fam, epi), (case, prec, dense)
+            if form == "tail":
+                assert dense.startswith("conv_raw3_kernel<") and "|tail=conv_raw_kernel<" in dense and ", 0, 1>,grid=" in dense.split("|tail=")[1], (case, dense)
+            else:
+                assert f["fixup"] == form and "tail" not in f, (case, prec, dense)
+            for pair in range(len(VIEW_PAIRS)):
+                lay = view_layout(case, pair)
+                strides = [v[4] for v in lay.values()]
+                assert len(set(strides)) == len(strides) and all(v[4] != v[2] * v[3] for v in lay.values()), (case, lay)
+                a = _view_args(_lib, case, pair, prec)
+                assert ops.conv_describe(a, opc) == dense, (case, pair, prec)
+                if op == "fwd":
+                    a.x_bs = lay["xb"][4]
+                    assert ops.conv_describe(a, opc) == dense, (case, pair, prec, "batch[:, 0]")
+                if op == "dgrad":                           # the in-place form: the addend is the dx view, the mask source dense
+                    a.dx_add_bs, a.dx_ref_bs = a.dx_bs, geom[1] * geom[6]
+                    assert ops.conv_describe(a, opc) == dense, (case, pair, prec, "in place")
+    # what the table holds: every fixup instantiation of the fp32 entry points, every family's own epilogue, three kinds of tail
+    assert {(c[3], c[4]) for c in VIEW_CASES if c[5] == "none"} >= {(c[3], c[4]) for c in FIXUP_CASES}
+    assert {c[4] for c in VIEW_CASES if c[5] == "tail"} == {"F", "T", "Tpm"}
