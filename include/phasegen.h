@@ -247,6 +247,36 @@ int pg_stft_describe(const pg_stft_args* a, char* buf, int32_t buflen);
 /* The integer framing map alone (bit-exact contract): idx[t, k] = sample index of tap k of frame t. */
 int pg_stft_frame_index(int32_t n_samples, int32_t n_fft, int32_t hop, int32_t n_frames, int32_t* idx, void* stream);
 
+/* Training batches straight from raw audio: pg_stft of n_signals CROPS of one flat device buffer that holds every track (every
+ * channel) back to back, fused with the data set's standardisation (preproc_mdb.py:182) and data.py:39-47.  An entry point of its
+ * own with a struct of its own (pg_stft_args keeps its 80 bytes); PG_VERSION is unchanged.
+ *   Framing: pg_stft's, applied to the crop: signal s is n_samples samples long, sample q of it is src[crop_begin[s] + q] for
+ *   q < lim = clamp(crop_end[s] - crop_begin[s], 0, n_samples) and ZERO for q >= lim -- the reference's zero-padded tail
+ *   (preproc_mdb.py:86-88), applied first; the reflect padding of n_fft/2 then happens inside the crop's n_samples.  Window, DC
+ *   drop and [re; im] stacking are pg_stft's.
+ *   Memory contract: for signal s no address outside [crop_begin[s], crop_begin[s] + lim) is ever read, so a crop that runs off the
+ *   end of its track never sees the next track.  The CALLER guarantees 0 <= crop_begin[s] and crop_end[s] <= the number of floats
+ *   in src for every s: the arrays live on the device and the host cannot check them.
+ *   Arithmetic contract: the bits of pg_stft (same single_frame) on the gathered, zero-padded crops, then -- with stats --
+ *   pg_standardize with the same stats: v = (v - (float)mean) / (float)std in fp32, an IEEE division, nothing contracted, on re AND
+ *   im of every cell (the Nyquist bin's zero imaginary part becomes (0 - mean) / std), then -- with polar -- pg_polar (use_exp = 1).
+ *   stats == NULL and polar == 0 give the bits of the chunked pg_stft.  A row's result does not depend on n_signals or on its
+ *   position in the batch.  Kernel families and selection rules are pg_stft's (pg_stft_crops_describe names the launch).
+ *   Errors (host side): NULL src / out / crop_begin / crop_end PG_ERR_NULL; n_fft PG_ERR_UNSUPPORTED; sizes, n_frames PG_ERR_SHAPE;
+ *   stats not 8-byte or out not 4-byte aligned PG_ERR_ALIGN. */
+typedef struct pg_stft_crops_args {
+    int32_t n_signals, n_samples, n_fft, hop, n_frames, polar;  /* as pg_stft_args; n_samples = crop length                  */
+    int32_t single_frame, _pad0;                                /* transform schedule, as pg_stft_args                        */
+    const float* src;                 /* ONE flat device buffer holding every track (every channel) back to back             */
+    const int64_t* crop_begin;        /* n_signals device entries: index in src of sample 0 of crop s                        */
+    const int64_t* crop_end;          /* n_signals device entries: index one past the last sample crop s may read (the end   */
+                                      /*   of ITS track).  lim = clamp(end - begin, 0, n_samples); samples q >= lim are 0    */
+    const double* stats;              /* optional (NULL): device {mean, std}; v = (v - (float)mean) / (float)std on re AND im */
+    float* out;                       /* (n_signals, 2, n_fft/2, n_frames), dense                                            */
+} pg_stft_crops_args;                 /* 72 bytes */
+int pg_stft_crops(const pg_stft_crops_args* a, void* stream);
+int pg_stft_crops_describe(const pg_stft_crops_args* a, char* buf, int32_t buflen);   /* launch plan without launching, as pg_stft_describe */
+
 /* data.py:39-47 on its own: in (N,2,...) [re; im] -> out (N,2,...) [log1p|z| ; angle]; inner = bins*frames. */
 typedef struct pg_polar_args { int64_t n_items; int64_t inner; const float* in; float* out;
                                int32_t use_exp; /* data.py:39 use_exp: 1 -> log1p|z|, 0 -> |z| */ int32_t _pad0; } pg_polar_args;

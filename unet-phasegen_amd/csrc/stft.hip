@@ -105,8 +105,35 @@ __device__ __forceinline__ Src signal_src(const pg_stft_args& a, int sig) {
     lim = lim < 0 ? 0 : (lim > a.n_samples ? a.n_samples : lim);
     return { a.y + row * a.src_stride + st, (int)lim };
 }
+// pg_stft_crops: signal `sig` is a crop of one flat buffer with a limit of its own, the end of ITS track (nothing at or past
+// p + lim is ever dereferenced: the memory contract of the call)
+__device__ __forceinline__ Src signal_src(const pg_stft_crops_args& a, int sig) {
+    const long st = a.crop_begin[sig];
+    long lim = a.crop_end[sig] - st;
+    lim = lim < 0 ? 0 : (lim > a.n_samples ? a.n_samples : lim);
+    return { a.src + st, (int)lim };
+}
+// row-per-signal source of the un-chunked instantiations (the crops call has none: its kernels are CHUNKED ones)
+__device__ __forceinline__ const float* plain_src(const pg_stft_args& a) { return a.y; }
+__device__ __forceinline__ const float* plain_src(const pg_stft_crops_args&) { return nullptr; }
 
-__global__ __launch_bounds__(FFT_THREADS) void stft_kernel(const pg_stft_args a) {
+// What a store epilogue does to (re, im) between the split and the polar conversion.  pg_stft: nothing (an empty type, so its
+// kernels carry no trace of it).  pg_stft_crops: pg_standardize's arithmetic in registers -- fp32 (v - mean) / std, IEEE division.
+struct NoNorm {};
+struct Norm { float mean, sd; bool on; };
+__device__ __forceinline__ NoNorm load_norm(const pg_stft_args&) { return {}; }
+__device__ __forceinline__ Norm load_norm(const pg_stft_crops_args& a) {
+    if (!a.stats) return { 0.f, 1.f, false };
+    return { (float)a.stats[0], (float)a.stats[1], true };
+}
+__device__ __forceinline__ void standardize(const NoNorm&, float&, float&) {}
+__device__ __forceinline__ void standardize(const Norm& n, float& re, float& im) {
+    if (n.on) { re = (re - n.mean) / n.sd; im = (im - n.mean) / n.sd; }
+}
+
+// The three kernel families below are written once, as device functions over the argument struct (pg_stft_args or
+// pg_stft_crops_args); each __global__ kernel is one instantiation of its family's body.
+template <class Args> __device__ __forceinline__ void stft_r2_body(const Args& a) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     const int N = a.n_fft, bins = N >> 1;
     float2* buf0 = smem; float2* buf1 = smem + N; float2* tw = smem + 2 * N;
@@ -121,8 +148,10 @@ __global__ __launch_bounds__(FFT_THREADS) void stft_kernel(const pg_stft_args a)
     const float2* X = fft_lds(buf0, buf1, tw, N, 1.f);
     float* o_re = a.out + ((long)sig * 2 * bins) * a.n_frames + t;
     float* o_im = o_re + (long)bins * a.n_frames;
+    const auto nrm = load_norm(a);
     for (int k = 1 + threadIdx.x; k <= bins; k += blockDim.x) {      // bin 0 (DC) dropped, preproc_mdb.py:93
         float2 v = X[k];
+        standardize(nrm, v.x, v.y);
         if (a.polar) {
             float mg, an;
             pg_polar_one(v.x, v.y, 1, mg, an);
@@ -134,6 +163,8 @@ __global__ __launch_bounds__(FFT_THREADS) void stft_kernel(const pg_stft_args a)
         }
     }
 }
+__global__ __launch_bounds__(FFT_THREADS) void stft_kernel(const pg_stft_args a) { stft_r2_body(a); }
+__global__ __launch_bounds__(FFT_THREADS) void stft_crops_kernel(const pg_stft_crops_args a) { stft_r2_body(a); }
 
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -233,8 +264,11 @@ __device__ float2* fft_frames_t(float2* x, float2* y, const float2* tw, int M) {
 template <int DIR> __device__ __forceinline__ float2* fft_frames(float2* x, float2* y, const float2* tw, int M) { return fft_frames_t<DIR, PF>(x, y, tw, M); }
 
 // one output row, SF consecutive frames: a 16 B store when the row segment is aligned, scalar stores otherwise
-__device__ __forceinline__ void stft_store_row(const pg_stft_args& a, float* o_re, float* o_im, long row, int nfr, bool vec,
+template <class Args, class NR>
+__device__ __forceinline__ void stft_store_row(const Args& a, const NR& nrm, float* o_re, float* o_im, long row, int nfr, bool vec,
                                                float (&re)[SF], float (&im)[SF]) {
+#pragma unroll
+    for (int f = 0; f < SF; ++f) standardize(nrm, re[f], im[f]);
     if (a.polar) {
 #pragma unroll
         for (int f = 0; f < SF; ++f) {
@@ -270,9 +304,9 @@ __device__ __forceinline__ GroupWalk group_walk(int total) {
     return w;
 }
 
-template <bool CHUNKED>   // CHUNKED: signals are chunks of longer source rows (pg_stft_args.chunk_start); its own instantiation so
-                          // that the plain path keeps its vector loads and register budget
-__global__ __launch_bounds__(BT) void stft_frames_kernel(const pg_stft_args a) {
+// CHUNKED: signals are chunks of longer source rows (pg_stft_args.chunk_start) or crops of a flat buffer (pg_stft_crops_args); its
+// own instantiation so that the plain path keeps its vector loads and register budget
+template <class Args, bool CHUNKED> __device__ __forceinline__ void stft_frames_body(const Args& a) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     const int N = a.n_fft, M = N >> 1;
     float2* x = smem; float2* y = smem + SF * M; float2* tw = smem + 2 * SF * M;
@@ -288,8 +322,9 @@ __global__ __launch_bounds__(BT) void stft_frames_kernel(const pg_stft_args a) {
 #pragma unroll
     for (int i = 0; i < K_ITERS; ++i)
         sincospif(-(float)(1 + threadIdx.x + i * BT) / (float)M, &ss[i], &sc[i]);   // w = exp(-2 pi i / n_fft)
-    const bool vec2 = !CHUNKED && ((a.hop | a.n_samples) & 1) == 0 && (((uintptr_t)a.y) & 7) == 0;   // sample pairs are 8 B aligned
+    const bool vec2 = !CHUNKED && ((a.hop | a.n_samples) & 1) == 0 && (((uintptr_t)plain_src(a)) & 7) == 0;   // sample pairs are 8 B aligned
     const bool vec4 = (a.n_frames & 3) == 0 && (((uintptr_t)a.out) & 15) == 0;               // row segments are 16 B aligned
+    const auto nrm = load_norm(a);
     __syncthreads();
     // sample pairs of one group -> registers (windowing and the LDS write happen one iteration later, so the loads of
     // group i+1 are in flight during the passes of group i)
@@ -299,7 +334,7 @@ __global__ __launch_bounds__(BT) void stft_frames_kernel(const pg_stft_args a) {
         const int nfr = min(SF, a.n_frames - t0);
         const float* sgn; int lim;
         if (CHUNKED) { const Src src = signal_src(a, sig); sgn = src.p; lim = src.lim; }
-        else { sgn = a.y + (long)sig * a.n_samples; lim = a.n_samples; }
+        else { sgn = plain_src(a) + (long)sig * a.n_samples; lim = a.n_samples; }
         auto at = [&](int q) { return (!CHUNKED || q < lim) ? sgn[q] : 0.f; };
 #pragma unroll
         for (int i = 0; i < M_ITERS; ++i) {
@@ -359,19 +394,21 @@ __global__ __launch_bounds__(BT) void stft_frames_kernel(const pg_stft_args a) {
                     rk[f] = E.x + T.x; ik[f] = E.y + T.y;
                     rm[f] = E.x - T.x; im[f] = T.y - E.y;
                 }
-                stft_store_row(a, o_re, o_im, k - 1, nfr, vec, rk, ik);
-                if (k != M - k) stft_store_row(a, o_re, o_im, M - k - 1, nfr, vec, rm, im);
+                stft_store_row(a, nrm, o_re, o_im, k - 1, nfr, vec, rk, ik);
+                if (k != M - k) stft_store_row(a, nrm, o_re, o_im, M - k - 1, nfr, vec, rm, im);
             }
         }
         if (threadIdx.x == 0) {                                               // Nyquist bin: X[M] = Re Z0 - Im Z0
             float rn[SF], in[SF];
 #pragma unroll
             for (int f = 0; f < SF; ++f) { const float2 Z0 = Z[f * M]; rn[f] = Z0.x - Z0.y; in[f] = 0.f; }
-            stft_store_row(a, o_re, o_im, M - 1, nfr, vec, rn, in);
+            stft_store_row(a, nrm, o_re, o_im, M - 1, nfr, vec, rn, in);
         }
         lds_barrier();                                                      // Z may live in the buffer the next group loads into
     }
 }
+template <bool CHUNKED> __global__ __launch_bounds__(BT) void stft_frames_kernel(const pg_stft_args a) { stft_frames_body<pg_stft_args, CHUNKED>(a); }
+__global__ __launch_bounds__(BT) void stft_crops_frames_kernel(const pg_stft_crops_args a) { stft_frames_body<pg_stft_crops_args, true>(a); }
 
 // SF consecutive frames of spectrum row `bin` (1-based FFT bin): the raw values of both tensors (frames past the end read as zero) ...
 struct RowRaw { float va[SF], vb[SF]; };
@@ -675,8 +712,11 @@ constexpr int WT = NW * 64;                                 // threads; a thread
 template <int P> constexpr size_t wave_lds() { return (size_t)(NW * WaveFft<P>::REG + WaveFft<P>::T1N + WaveFft<P>::T2N) * sizeof(float2); }
 
 // one output row, 4 of the group's 8 frames (half = 0 / 1): as stft_store_row
-__device__ __forceinline__ void stft_store_row4(const pg_stft_args& a, float* o_re, float* o_im, long row, int half, int nfr, bool vec,
+template <class Args, class NR>
+__device__ __forceinline__ void stft_store_row4(const Args& a, const NR& nrm, float* o_re, float* o_im, long row, int half, int nfr, bool vec,
                                                 float (&re)[4], float (&im)[4]) {
+#pragma unroll
+    for (int f = 0; f < 4; ++f) standardize(nrm, re[f], im[f]);
     if (a.polar) {
 #pragma unroll
         for (int f = 0; f < 4; ++f) {                         // (fenced: measured 87 us against 91-93 with the four chains interleaved)
@@ -704,8 +744,7 @@ __device__ __forceinline__ void stft_store_row4(const pg_stft_args& a, float* o_
 // STFT, n_fft = 128 P: wave w of a workgroup transforms frame t0 + w of its group of NW frames; the split X[k] = E[k] + w^k O[k], the
 // optional polar epilogue and the row stores (two 16 B pieces = 32 B per row and workgroup) are the workgroup-wide phase, reading the
 // waves' spectra from LDS.
-template <bool CHUNKED, int P>
-__global__ __launch_bounds__(WT, CHUNKED ? 2 : 4) void stft_w_kernel(const pg_stft_args a) {
+template <class Args, bool CHUNKED, int P> __device__ __forceinline__ void stft_w_body(const Args& a) {
     using W = WaveFft<P>;
     extern __shared__ __attribute__((aligned(16))) float2 wsm[];
     float2 (*regs)[W::REG] = (float2 (*)[W::REG])wsm;
@@ -719,8 +758,9 @@ __global__ __launch_bounds__(WT, CHUNKED ? 2 : 4) void stft_w_kernel(const pg_st
     float sc2 = 0.f, ss2 = 0.f;                               // split factors of this thread's bin pairs k = 1 + (tid >> 1) + 256 i
     sincospif(-(float)(1 + (int)(threadIdx.x >> 1)) / (float)M, &ss, &sc);
     if (PAIRS > 1) sincospif(-(float)(257 + (int)(threadIdx.x >> 1)) / (float)M, &ss2, &sc2);
-    const bool vec2 = !CHUNKED && ((a.hop | a.n_samples) & 1) == 0 && (((uintptr_t)a.y) & 7) == 0;   // sample pairs are 8 B aligned
+    const bool vec2 = !CHUNKED && ((a.hop | a.n_samples) & 1) == 0 && (((uintptr_t)plain_src(a)) & 7) == 0;   // sample pairs are 8 B aligned
     const bool vec4 = (a.n_frames & 3) == 0 && (((uintptr_t)a.out) & 15) == 0;               // row segments are 16 B aligned
+    const auto nrm = load_norm(a);
     // This wave's frame of group g as RAW sample pairs v[r] = (y[2 m], y[2 m + 1]), m = lane + 64 r (reflect padding by index math: the
     // bit-exact part of the contract).  Issued one group AHEAD, into the registers the finished transform has just vacated, so the
     // samples travel while the workgroup splits, converts and stores the current group.
@@ -730,7 +770,7 @@ __global__ __launch_bounds__(WT, CHUNKED ? 2 : 4) void stft_w_kernel(const pg_st
         if (wave >= min(NW, a.n_frames - t0)) return;
         const float* sgn; int lim;
         if (CHUNKED) { const Src src = signal_src(a, sig); sgn = src.p; lim = src.lim; }
-        else { sgn = a.y + (long)sig * a.n_samples; lim = a.n_samples; }
+        else { sgn = plain_src(a) + (long)sig * a.n_samples; lim = a.n_samples; }
         auto at = [&](int q) { return (!CHUNKED || q < lim) ? sgn[q] : 0.f; };
         const int start = (t0 + wave) * a.hop - M;                              // frame tap k sits at sample start + k
         const bool inside = start >= 0 && start + N <= a.n_samples;
@@ -793,19 +833,23 @@ __global__ __launch_bounds__(WT, CHUNKED ? 2 : 4) void stft_w_kernel(const pg_st
                     rk[f] = E.x + T.x; ik[f] = E.y + T.y;
                     rm[f] = E.x - T.x; im[f] = T.y - E.y;
                 }
-                stft_store_row4(a, o_re, o_im, k - 1, half, nfr, vec, rk, ik);
-                if (k != M - k) stft_store_row4(a, o_re, o_im, M - k - 1, half, nfr, vec, rm, im);
+                stft_store_row4(a, nrm, o_re, o_im, k - 1, half, nfr, vec, rk, ik);
+                if (k != M - k) stft_store_row4(a, nrm, o_re, o_im, M - k - 1, half, nfr, vec, rm, im);
                 else {                                                        // the self-paired threads also own the Nyquist bin:
                     float rn[4], in[4];                                       // X[M] = Re Z0 - Im Z0
 #pragma unroll
                     for (int f = 0; f < 4; ++f) { const float2 Z0 = regs[4 * half + f][0]; rn[f] = Z0.x - Z0.y; in[f] = 0.f; }
-                    stft_store_row4(a, o_re, o_im, M - 1, half, nfr, vec, rn, in);
+                    stft_store_row4(a, nrm, o_re, o_im, M - 1, half, nfr, vec, rn, in);
                 }
             }
         }
         lds_barrier();                                                        // the regions are the next group's work space
     }
 }
+template <bool CHUNKED, int P>
+__global__ __launch_bounds__(WT, CHUNKED ? 2 : 4) void stft_w_kernel(const pg_stft_args a) { stft_w_body<pg_stft_args, CHUNKED, P>(a); }
+template <int P>                                             // (a chunked instantiation: two workgroups per CU, as stft_w_kernel<true, P>)
+__global__ __launch_bounds__(WT, 2) void stft_crops_w_kernel(const pg_stft_crops_args a) { stft_w_body<pg_stft_crops_args, true, P>(a); }
 
 // the workgroup-wide build of the NW half-length spectra Z_f[k] (natural order) from the spectrum rows of one group: lanes 2 i and
 // 2 i + 1 read the two 16 B halves of the same rows (a wave's load instruction covers 32 rows x 32 contiguous bytes)
@@ -1198,6 +1242,7 @@ hipError_t batched_lds_ready() {
     const struct { const void* fn; int lds; } big[] = {
         {(const void*)stft_frames_kernel<false>, lds}, {(const void*)stft_frames_kernel<true>, lds}, {(const void*)istft_frames4_kernel, lds},
         {(const void*)stft_w_kernel<false, 16>, w16}, {(const void*)stft_w_kernel<true, 16>, w16},
+        {(const void*)stft_crops_frames_kernel, lds}, {(const void*)stft_crops_w_kernel<16>, w16},
         {(const void*)istft_frames_w_kernel<16>, w16}, {(const void*)istft_ola_w_kernel<16>, w16}};
     hipError_t e = hipSuccess;
     for (const auto& k : big)
@@ -1214,7 +1259,8 @@ hipError_t batched_lds_ready() {
 //   stft_w_kernel / istft_frames_w      one wave per frame: n_fft = 1024 (P = 8) and 2048 (P = 16)
 //   istft_ola_w_kernel + istft_seam     overlap-add inside the transform: n_fft 1024 / 2048 at hop = n_fft / 4 into 16 B-aligned audio
 //   istft_ola4_kernel                   overlap-add of a frame workspace: behind every other inverse transform
-enum Kern { STFT_R2, STFT_FRAMES, STFT_W, ISTFT_R2, ISTFT_FRAMES4, ISTFT_FRAMES_W, ISTFT_OLA_W, ISTFT_SEAM, ISTFT_OLA4, ISTFT_NORM };
+//   stft_crops_kernel / _frames_kernel / _w_kernel<P>   pg_stft_crops: the crops instantiations of the three forward families, same rules
+enum Kern { STFT_R2, STFT_FRAMES, STFT_W, STFT_CROPS_R2, STFT_CROPS_FRAMES, STFT_CROPS_W, ISTFT_R2, ISTFT_FRAMES4, ISTFT_FRAMES_W, ISTFT_OLA_W, ISTFT_SEAM, ISTFT_OLA4, ISTFT_NORM };
 struct Launch { Kern k; bool chunked; int P; unsigned gx, gy, block; size_t lds; };    // chunked, P: template arguments; gy = 0: a 1-D grid
 struct StftPlan { Launch l[1]; int n; };
 struct IstftPlan {
@@ -1232,6 +1278,13 @@ Launch wave_launch(Kern k, bool chunked, int n_fft, int n_signals, int n_frames)
 }
 size_t radix2_lds(int n_fft) { return (size_t)(2 * n_fft + n_fft / 2) * sizeof(float2); }
 
+// the forward transform's selection rule, shared by pg_stft and pg_stft_crops (r2 / frames / w: the caller's kernels of the three families)
+Launch stft_launch(Kern r2, Kern frames, Kern w, bool chunked, int n_fft, int single_frame, int n_signals, int n_frames) {
+    if (n_fft > BATCHED_MAX_NFFT || single_frame) return {r2, false, 0, (unsigned)(n_signals * n_frames), 0, FFT_THREADS, radix2_lds(n_fft)};
+    if (n_fft == 2048 || n_fft == 1024) return wave_launch(w, chunked, n_fft, n_signals, n_frames);
+    return {frames, chunked, 0, (unsigned)batched_grid(n_signals * ((n_frames + SF - 1) / SF)), 0, BT, batched_lds(n_fft)};
+}
+
 int plan_stft(const pg_stft_args* a, StftPlan& pl) {
     if (!a || !a->y || !a->out) return pg_fail(PG_ERR_NULL, "stft: y, out required");
     if (!pow2(a->n_fft) || a->n_fft < 32 || a->n_fft > 4096) return pg_fail(PG_ERR_UNSUPPORTED, "stft: n_fft must be a power of two in [32, 4096]");
@@ -1239,12 +1292,21 @@ int plan_stft(const pg_stft_args* a, StftPlan& pl) {
     if (a->n_frames != 1 + a->n_samples / a->hop) return pg_fail(PG_ERR_SHAPE, "stft: n_frames must equal 1 + n_samples / hop");
     if (a->chunk_start && (a->src_len <= 0 || a->src_stride < a->src_len)) return pg_fail(PG_ERR_SHAPE, "stft: chunked source needs 0 < src_len <= src_stride");
     if (!a->chunk_start && a->chunk_row) return pg_fail(PG_ERR_NULL, "stft: chunk_row without chunk_start");
-    const bool chunked = a->chunk_start != nullptr;
     pl.n = 1;
-    if (a->n_fft > BATCHED_MAX_NFFT || a->single_frame)
-        pl.l[0] = {STFT_R2, false, 0, (unsigned)(a->n_signals * a->n_frames), 0, FFT_THREADS, radix2_lds(a->n_fft)};
-    else if (a->n_fft == 2048 || a->n_fft == 1024) pl.l[0] = wave_launch(STFT_W, chunked, a->n_fft, a->n_signals, a->n_frames);
-    else pl.l[0] = {STFT_FRAMES, chunked, 0, (unsigned)batched_grid(a->n_signals * ((a->n_frames + SF - 1) / SF)), 0, BT, batched_lds(a->n_fft)};
+    pl.l[0] = stft_launch(STFT_R2, STFT_FRAMES, STFT_W, a->chunk_start != nullptr, a->n_fft, a->single_frame, a->n_signals, a->n_frames);
+    return PG_OK;
+}
+
+// pg_stft_crops: the same checks on the shared fields, the same selection, the crops instantiation of the selected family
+int plan_stft_crops(const pg_stft_crops_args* a, StftPlan& pl) {
+    if (!a || !a->src || !a->out || !a->crop_begin || !a->crop_end) return pg_fail(PG_ERR_NULL, "stft_crops: src, crop_begin, crop_end, out required");
+    if (!pow2(a->n_fft) || a->n_fft < 32 || a->n_fft > 4096) return pg_fail(PG_ERR_UNSUPPORTED, "stft_crops: n_fft must be a power of two in [32, 4096]");
+    if (a->n_signals <= 0 || a->hop <= 0 || a->n_samples <= a->n_fft / 2) return pg_fail(PG_ERR_SHAPE, "stft_crops: bad sizes (reflect padding needs n_samples > n_fft/2)");
+    if (a->n_frames != 1 + a->n_samples / a->hop) return pg_fail(PG_ERR_SHAPE, "stft_crops: n_frames must equal 1 + n_samples / hop");
+    if ((int64_t)a->n_signals * a->n_frames > INT32_MAX) return pg_fail(PG_ERR_SHAPE, "stft_crops: n_signals * n_frames must fit in 31 bits");
+    if ((((uintptr_t)a->stats) & 7) || (((uintptr_t)a->out) & 3)) return pg_fail(PG_ERR_ALIGN, "stft_crops: stats must be 8-byte, out 4-byte aligned");
+    pl.n = 1;
+    pl.l[0] = stft_launch(STFT_CROPS_R2, STFT_CROPS_FRAMES, STFT_CROPS_W, true, a->n_fft, a->single_frame, a->n_signals, a->n_frames);
     return PG_OK;
 }
 
@@ -1301,7 +1363,7 @@ int plan_istft(const pg_istft_args* a, IstftPlan& pl) {
 #define PG_UNPACK(...) __VA_ARGS__
 #define PG_RUN(args, ...) do { if (name) snprintf(name, 64, "%s", #__VA_ARGS__); \
                                else hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(l.block), l.lds, st, PG_UNPACK args); } while (0)
-void run(const Launch& l, const pg_stft_args* s, const pg_istft_args* i, const IstftPlan* pl, hipStream_t st, char* name = nullptr) {
+void run(const Launch& l, const pg_stft_args* s, const pg_stft_crops_args* c, const pg_istft_args* i, const IstftPlan* pl, hipStream_t st, char* name = nullptr) {
     const dim3 grid(l.gx, l.gy ? l.gy : 1);
     float* partial = pl ? (float*)((char*)i->workspace + pl->part_off) : nullptr;
     float* data = pl ? (float*)((char*)i->workspace + pl->data_off) : nullptr;          // frames, or tails
@@ -1312,6 +1374,9 @@ void run(const Launch& l, const pg_stft_args* s, const pg_istft_args* i, const I
         if (l.P == 16) { if (l.chunked) PG_RUN((*s), stft_w_kernel<true, 16>); else PG_RUN((*s), stft_w_kernel<false, 16>); }
         else { if (l.chunked) PG_RUN((*s), stft_w_kernel<true, 8>); else PG_RUN((*s), stft_w_kernel<false, 8>); }
         break;
+    case STFT_CROPS_R2: PG_RUN((*c), stft_crops_kernel); break;
+    case STFT_CROPS_FRAMES: PG_RUN((*c), stft_crops_frames_kernel); break;
+    case STFT_CROPS_W: if (l.P == 16) PG_RUN((*c), stft_crops_w_kernel<16>); else PG_RUN((*c), stft_crops_w_kernel<8>); break;
     case ISTFT_R2: PG_RUN((*i, data), istft_frames_kernel); break;
     case ISTFT_FRAMES4: PG_RUN((*i, data), istft_frames4_kernel); break;
     case ISTFT_FRAMES_W: if (l.P == 16) PG_RUN((*i, data), istft_frames_w_kernel<16>); else PG_RUN((*i, data), istft_frames_w_kernel<8>); break;
@@ -1325,11 +1390,11 @@ void run(const Launch& l, const pg_stft_args* s, const pg_istft_args* i, const I
 #undef PG_UNPACK
 
 // "kernel<template args>,grid=X[xY],block=T,lds=B" per launch, in launch order, joined by '|'
-void describe(const Launch* l, int n, const pg_stft_args* s, const pg_istft_args* i, const IstftPlan* pl, char* buf, int buflen) {
+void describe(const Launch* l, int n, const pg_stft_args* s, const pg_stft_crops_args* c, const pg_istft_args* i, const IstftPlan* pl, char* buf, int buflen) {
     int at = 0;
     for (int k = 0; k < n && at < buflen - 1; ++k) {
         char name[64], gy[16] = "";
-        run(l[k], s, i, pl, nullptr, name);
+        run(l[k], s, c, i, pl, nullptr, name);
         if (l[k].gy) snprintf(gy, sizeof(gy), "x%u", l[k].gy);
         at += snprintf(buf + at, (size_t)(buflen - at), "%s%s,grid=%u%s,block=%u,lds=%zu", k ? "|" : "", name, l[k].gx, gy, l[k].block, l[k].lds);
     }
@@ -1337,10 +1402,10 @@ void describe(const Launch* l, int n, const pg_stft_args* s, const pg_istft_args
 
 int launched() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? PG_OK : pg_fail((int)e, hipGetErrorString(e)); }
 
-int execute(const Launch* l, int n, const pg_stft_args* s, const pg_istft_args* i, const IstftPlan* pl, void* stream) {
+int execute(const Launch* l, int n, const pg_stft_args* s, const pg_stft_crops_args* c, const pg_istft_args* i, const IstftPlan* pl, void* stream) {
     const hipError_t e = batched_lds_ready();
     if (e != hipSuccess) return pg_fail((int)e, hipGetErrorString(e));
-    for (int k = 0; k < n; ++k) run(l[k], s, i, pl, (hipStream_t)stream);
+    for (int k = 0; k < n; ++k) run(l[k], s, c, i, pl, (hipStream_t)stream);
     return launched();
 }
 
@@ -1349,7 +1414,7 @@ int execute(const Launch* l, int n, const pg_stft_args* s, const pg_istft_args* 
 extern "C" int pg_stft(const pg_stft_args* a, void* stream) {
     StftPlan pl;
     if (int e = plan_stft(a, pl)) return e;
-    return execute(pl.l, pl.n, a, nullptr, nullptr, stream);
+    return execute(pl.l, pl.n, a, nullptr, nullptr, nullptr, stream);
 }
 
 // launch plan of a pg_stft call without launching it (as pg_conv_describe; pointers must be non-NULL, they are not read)
@@ -1357,7 +1422,22 @@ extern "C" int pg_stft_describe(const pg_stft_args* a, char* buf, int32_t buflen
     if (!buf || buflen < 128) return pg_fail(PG_ERR_NULL, "stft_describe: buf of >= 128 bytes required");
     StftPlan pl;
     if (int e = plan_stft(a, pl)) return e;
-    describe(pl.l, pl.n, a, nullptr, nullptr, buf, buflen);
+    describe(pl.l, pl.n, a, nullptr, nullptr, nullptr, buf, buflen);
+    return PG_OK;
+}
+
+extern "C" int pg_stft_crops(const pg_stft_crops_args* a, void* stream) {
+    StftPlan pl;
+    if (int e = plan_stft_crops(a, pl)) return e;
+    return execute(pl.l, pl.n, nullptr, a, nullptr, nullptr, stream);
+}
+
+// launch plan of a pg_stft_crops call without launching it (as pg_stft_describe)
+extern "C" int pg_stft_crops_describe(const pg_stft_crops_args* a, char* buf, int32_t buflen) {
+    if (!buf || buflen < 128) return pg_fail(PG_ERR_NULL, "stft_crops_describe: buf of >= 128 bytes required");
+    StftPlan pl;
+    if (int e = plan_stft_crops(a, pl)) return e;
+    describe(pl.l, pl.n, nullptr, a, nullptr, nullptr, buf, buflen);
     return PG_OK;
 }
 
@@ -1378,7 +1458,7 @@ extern "C" int64_t pg_workspace_bytes_istft(const pg_istft_args* a) {
 extern "C" int pg_istft(const pg_istft_args* a, void* stream) {
     IstftPlan pl;
     if (int e = plan_istft(a, pl)) return e;
-    return execute(pl.l, pl.n, nullptr, a, &pl, stream);
+    return execute(pl.l, pl.n, nullptr, nullptr, a, &pl, stream);
 }
 
 // launch plan of a pg_istft call without launching it (as pg_stft_describe)
@@ -1386,7 +1466,7 @@ extern "C" int pg_istft_describe(const pg_istft_args* a, char* buf, int32_t bufl
     if (!buf || buflen < 128) return pg_fail(PG_ERR_NULL, "istft_describe: buf of >= 128 bytes required");
     IstftPlan pl;
     if (int e = plan_istft(a, pl)) return e;
-    describe(pl.l, pl.n, nullptr, a, &pl, buf, buflen);
+    describe(pl.l, pl.n, nullptr, nullptr, a, &pl, buf, buflen);
     return PG_OK;
 }
 

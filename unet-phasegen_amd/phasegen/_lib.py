@@ -106,6 +106,14 @@ class StftArgs(C.Structure):
                 ("chunk_start", C.c_void_p), ("chunk_row", C.c_void_p), ("src_len", C.c_int64), ("src_stride", C.c_int64)]
 
 
+class StftCropsArgs(C.Structure):
+    """pg_stft_crops_args: STFT of crops of one flat buffer, fused with standardisation and polar (include/phasegen.h)."""
+    _fields_ = [("n_signals", C.c_int32), ("n_samples", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32),
+                ("n_frames", C.c_int32), ("polar", C.c_int32), ("single_frame", C.c_int32), ("_pad0", C.c_int32),
+                ("src", C.c_void_p), ("crop_begin", C.c_void_p), ("crop_end", C.c_void_p), ("stats", C.c_void_p),
+                ("out", C.c_void_p)]
+
+
 class MomentsArgs(C.Structure):
     _fields_ = [("n", C.c_int64), ("x", C.c_void_p), ("stats", C.c_void_p), ("workspace", C.c_void_p),
                 ("workspace_bytes", C.c_int64)]
@@ -197,6 +205,8 @@ SYMBOLS = {
     "pg_adam_step": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p]),
     "pg_stft": (C.c_int, [C.POINTER(StftArgs), C.c_void_p]),
     "pg_stft_describe": (C.c_int, [C.POINTER(StftArgs), C.c_char_p, C.c_int32]),
+    "pg_stft_crops": (C.c_int, [C.POINTER(StftCropsArgs), C.c_void_p]),
+    "pg_stft_crops_describe": (C.c_int, [C.POINTER(StftCropsArgs), C.c_char_p, C.c_int32]),
     "pg_stft_frame_index": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pg_polar": (C.c_int, [C.POINTER(PolarArgs), C.c_void_p]),
     "pg_workspace_bytes_istft": (C.c_int64, [C.POINTER(IstftArgs)]),

@@ -645,6 +645,62 @@ def stft_describe(*args, **kw):
     return _describe(_lib.load().pg_stft_describe, _stft_args(*args, **kw)[0], "stft_describe")
 
 
+def stats_tensor(stats, device):
+    """The two-double device tensor {mean, std} pg_stft_crops / pg_standardize read, from a ``(mean, std)`` pair of Python floats (one
+    upload: callers that run many batches build it once) or from such a tensor (returned as it is).  std must be finite and > 0."""
+    if torch.is_tensor(stats):
+        if stats.dtype != torch.float64 or stats.numel() != 2 or not stats.is_cuda or not stats.is_contiguous():
+            raise TypeError("stats must be a dense device tensor of two float64 values {mean, std}")
+        return stats
+    mean, std = (float(v) for v in stats)
+    if not (mean == mean and abs(mean) != float("inf")) or not (0.0 < std < float("inf")):
+        raise ValueError(f"stats: mean must be finite and std finite and positive, got ({mean}, {std})")
+    return torch.tensor([mean, std], dtype=torch.float64).to(device)
+
+
+def _stft_crops_args(src, crop_begin, crop_end, crop_len, n_fft, hop, polar=False, stats=None, out=None, single_frame=None):
+    """The pg_stft_crops_args of one ops.stft_crops call, the tensor it fills and the tensors the struct points to."""
+    if src.dim() != 1:
+        raise ValueError("stft_crops: src is ONE flat buffer (1-D)")
+    for t, name in ((crop_begin, "crop_begin"), (crop_end, "crop_end")):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.device != src.device:
+            raise TypeError(f"stft_crops: {name} must be a 1-D int64 tensor on src's device")
+    n_sig, n_samp = crop_begin.numel(), int(crop_len)
+    if crop_end.numel() != n_sig:
+        raise ValueError("stft_crops: crop_begin and crop_end need one entry per crop each")
+    if stats is not None:
+        stats = stats_tensor(stats, src.device)
+    nf = 1 + n_samp // hop
+    if out is None:
+        out = torch.empty(n_sig, 2, n_fft // 2, nf, device=src.device, dtype=torch.float32)
+    elif tuple(out.shape) != (n_sig, 2, n_fft // 2, nf):
+        raise ValueError(f"stft_crops: out must be {(n_sig, 2, n_fft // 2, nf)}, got {tuple(out.shape)}")
+    a = _lib.StftCropsArgs()
+    a.n_signals, a.n_samples, a.n_fft, a.hop, a.n_frames, a.polar = n_sig, n_samp, n_fft, hop, nf, int(polar)
+    a.single_frame = _tls.stft_single if single_frame is None else int(bool(single_frame))
+    a.src, a.out = _dense(src, "src"), _dense(out, "out")
+    a.crop_begin, a.crop_end = _dense_as(crop_begin, torch.int64, "crop_begin"), _dense_as(crop_end, torch.int64, "crop_end")
+    a.stats = stats.data_ptr() if stats is not None else None
+    return a, out, stats
+
+
+def stft_crops(src, crop_begin, crop_end, crop_len, n_fft, hop, polar=False, stats=None, out=None, single_frame=None):
+    """One launch from raw audio to a training batch: crop s is the ``crop_len`` samples of the flat device buffer ``src`` from
+    crop_begin[s], read up to crop_end[s] (the end of its track) and zero beyond -> (n_crops, 2, n_fft/2, 1 + crop_len // hop), the
+    bits of ``stft`` on the gathered crops, then ``standardize_with_`` (``stats``: a two-double device tensor or a (mean, std) pair
+    of Python floats; the pair is uploaded on every call, so loops pass ``stats_tensor(...)``), then ``polar``.
+    The caller guarantees 0 <= crop_begin and crop_end <= src.numel(): the device arrays are not checked."""
+    a, out, _keep = _stft_crops_args(src, crop_begin, crop_end, crop_len, n_fft, hop, polar, stats, out, single_frame)
+    _lib.check(_lib.load().pg_stft_crops(C.byref(a), _stream()), "stft_crops")
+    return out
+
+
+def stft_crops_describe(*args, **kw):
+    """pg_stft_crops_describe for the arguments of ``stft_crops``."""
+    a, _out, _keep = _stft_crops_args(*args, **kw)
+    return _describe(_lib.load().pg_stft_crops_describe, a, "stft_crops_describe")
+
+
 _RES_TYPES = {"kaiser_best": _lib.RS_KAISER_BEST, "kaiser_fast": _lib.RS_KAISER_FAST,
               _lib.RS_KAISER_BEST: _lib.RS_KAISER_BEST, _lib.RS_KAISER_FAST: _lib.RS_KAISER_FAST}
 _resample_banks = {}     # (U, D, quality, device) -> device copy of pg_resample_bank's output (read-only; at most 226 KB each)
@@ -881,16 +937,27 @@ _moments_ws = _StreamCache()
 _caches.append(_moments_ws)
 
 
-def standardize_(x):
-    """preproc_mdb.py:182 in place on a dense float32 tensor: x = (x - x.mean()) / x.std() over the WHOLE array (population
-    std, moments reduced in double).  Returns the (mean, std) device tensor (2 doubles)."""
+def moments(x, stats=None):
+    """pg_moments: (mean, population std) of a dense float32 tensor, reduced in double, into the two-double device tensor ``stats``
+    (allocated when None; a row of a larger float64 tensor lets a loop collect many results and read them back once)."""
     lib = _lib.load()
     ws = _moments_ws.get(x.device, lib.pg_workspace_bytes_moments)
-    stats = torch.empty(2, dtype=torch.float64, device=x.device)
+    if stats is None:
+        stats = torch.empty(2, dtype=torch.float64, device=x.device)
+    elif not (stats.is_cuda and stats.dtype == torch.float64 and stats.numel() == 2 and stats.is_contiguous()):
+        raise TypeError("moments: stats must be a dense device tensor of two float64 values")
     a = _lib.MomentsArgs()
     a.n, a.x, a.stats = x.numel(), _dense(x, "x"), stats.data_ptr()
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
     _lib.check(lib.pg_moments(C.byref(a), _stream()), "moments")
+    return stats
+
+
+def standardize_(x):
+    """preproc_mdb.py:182 in place on a dense float32 tensor: x = (x - x.mean()) / x.std() over the WHOLE array (population
+    std, moments reduced in double).  Returns the (mean, std) device tensor (2 doubles)."""
+    lib = _lib.load()
+    stats = moments(x)
     _lib.check(lib.pg_standardize(C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(stats.data_ptr()), _stream()), "standardize")
     return stats
 

@@ -1,8 +1,10 @@
 """Feature extraction of preproc_mdb.py on device: wav loading + rate change + chunking + STFT +
 global normalisation + shuffled split, producing the on-disk format data.py consumes: (N, 2, n_fft/2, frames) float32
-``{genre}_audio_{train,val}.npy``.  MedleyDB walking and stem mixing (preproc_mdb.py:15-64) stay out of scope; so do
-compressed audio formats: the input is wav files (``load_audio``, ``get_mix_chunks``) or already-loaded arrays / device tensors,
-at the target rate or -- with ``osr`` -- at another one.
+``{genre}_audio_{train,val}.npy``.  That file is no longer the only way to train: ``dataset_stats`` gives the normalisation of the
+aligned-chunk set without materialising it, and ``phasegen.data.AudioCropLoader`` (``train.py --audio``) draws the same chunks and
+fresh random crops from the raw audio every epoch.  MedleyDB walking and stem mixing (preproc_mdb.py:15-64) stay out of scope; so
+do compressed audio formats and augmentations beyond the reference's random crops: the input is wav files (``load_audio``,
+``get_mix_chunks``) or already-loaded arrays / device tensors, at the target rate or -- with ``osr`` -- at another one.
 
   load           preproc_mdb.py:112    the loading half of librosa.load: scipy's wav reader, integer PCM scaled to [-1, 1),
                  channels averaged to mono
@@ -18,6 +20,8 @@ at the target rate or -- with ``osr`` -- at another one.
   normalise      preproc_mdb.py:182    (x - mean) / std over the WHOLE array (re and im together, population std):
                  pg_moments (double accumulators, two-pass) + pg_standardize in place
   split          preproc_mdb.py:174-184 shuffled indices, first n_val clips -> val, rest -> train
+  statistics     preproc_mdb.py:182    ``dataset_stats``: the same (mean, std) from blocks of aligned chunks through one reusable
+                 buffer (chunked pg_stft + pg_moments per block, combined on the host in float64)
 """
 import os
 
@@ -119,6 +123,70 @@ def get_mix_chunks(fn, t_slice, n_fft, hop_length, n_random, rsr, osr=44100, rng
     a_len = min(m.shape[-1] for m in mix)
     audio = torch.stack([m[:a_len] for m in mix])
     return chunk_audio(audio, t_slice, n_fft, hop_length, n_random, np.random.default_rng() if rng is None else rng, dev)
+
+
+def as_channels(audio, device=None):
+    """A track as a dense (channels, samples) float32 device tensor: mono arrays gain the channel axis; device tensors stay where
+    they are."""
+    if torch.is_tensor(audio):
+        ad = audio.to(audio.device if device is None and audio.is_cuda else _device_of(device), torch.float32)
+    else:
+        ad = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(_device_of(device))
+    if ad.dim() == 1:
+        ad = ad[None]
+    if ad.dim() != 2:
+        raise ValueError(f"a track is (samples,) or (channels, samples), got {tuple(ad.shape)}")
+    return ad.contiguous()
+
+
+def combine_moments(parts):
+    """(n, mean, population std) of the union of disjoint blocks given as (n, mean, std) triples, in float64: the pairwise update of
+    Chan, Golub and LeVeque on (n, mean, M2 = n std^2)."""
+    n, mean, m2 = 0, 0.0, 0.0
+    for nb, mb, sb in parts:
+        nb, mb, sb = int(nb), float(mb), float(sb)
+        if nb == 0:
+            continue
+        tot = n + nb
+        d = mb - mean
+        m2 = m2 + nb * sb * sb + d * d * (n * nb / tot)
+        mean = mean + d * (nb / tot)
+        n = tot
+    if n == 0:
+        raise ValueError("combine_moments: no samples")
+    return n, mean, float(np.sqrt(m2 / n))
+
+
+def dataset_stats(tracks, t_slice, n_fft, hop_length, device=None, block=64):
+    """The (mean, std) ``build_dataset(..., n_random=0, return_stats=True)`` computes -- over [re; im] of the aligned chunks of every
+    track (every channel), population std -- without materialising the set: ``block`` chunks at a time go through one chunked STFT
+    into one reusable buffer and pg_moments; the per-block (n, mean, std) are combined on the host in float64
+    (``combine_moments``) after ONE read-back.  tracks: mono arrays, (channels, samples) arrays or device tensors at the target rate."""
+    dev = _device_of(device)
+    bins, frames = n_fft // 2, 1 + t_slice // hop_length
+    block = max(1, int(block))
+    buf = torch.empty(block, 2, bins, frames, device=dev)
+    plan = []                                                            # (track tensor, starts, rows) per block
+    for t in tracks:
+        ad = as_channels(t, dev)
+        n_ch, a_len = ad.shape
+        starts = np.repeat(np.arange(0, a_len, t_slice, dtype=np.int64), n_ch)          # (chunk, channel) order, as chunk_audio
+        rows = np.tile(np.arange(n_ch, dtype=np.int32), len(starts) // n_ch)
+        for s0 in range(0, len(starts), block):
+            plan.append((ad, starts[s0:s0 + block], rows[s0:s0 + block]))
+    if not plan:
+        raise ValueError("dataset_stats: no tracks")
+    res = torch.empty(len(plan), 2, dtype=torch.float64, device=dev)
+    counts = []
+    for i, (ad, st, rw) in enumerate(plan):
+        k = len(st)
+        ops.stft(ad, n_fft, hop_length, out=buf[:k], chunk_start=torch.from_numpy(st).to(dev), chunk_row=torch.from_numpy(rw).to(dev),
+                 chunk_len=t_slice)
+        ops.moments(buf[:k], res[i])
+        counts.append(k * 2 * bins * frames)
+    res = res.cpu().numpy()
+    _, mean, std = combine_moments((n, m, s) for n, (m, s) in zip(counts, res))
+    return mean, std
 
 
 def build_dataset(tracks, chunk_seconds=4.064, rsr=16000, n_fft=2048, hop_length=512, n_random=0, n_val=40, seed=0,

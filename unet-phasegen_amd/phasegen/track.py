@@ -69,13 +69,19 @@ def _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, r
     dev = a2.device
     with torch.cuda.device(dev), torch.no_grad():
         # signal order (clip, channel), as preproc.chunk_audio
-        st = torch.tensor(np.repeat(np.arange(n_clips, dtype=np.int64) * step, n_ch), device=dev)
-        rows = torch.tensor(np.tile(np.arange(n_ch, dtype=np.int32), n_clips), device=dev)
+        starts = np.repeat(np.arange(n_clips, dtype=np.int64) * step, n_ch)
+        chans = np.tile(np.arange(n_ch, dtype=np.int64), n_clips)
+        if stats is not None:
+            # the training set's statistics: STFT, standardisation and polar in ONE launch (pg_stft_crops; the same bits as the three
+            # calls below).  Channel c is the region [c a_len, (c + 1) a_len) of the flat buffer.
+            begin = torch.from_numpy(chans * a_len + starts).to(dev)
+            end = torch.from_numpy((chans + 1) * a_len).to(dev)
+            an.pol = ops.stft_crops(a2.reshape(-1), begin, end, T, n_fft, hop_length, polar=True, stats=(stats[0], stats[1]))
+            return an
+        # the track's own moments need the unnormalised tensor: three launches
+        st, rows = torch.from_numpy(starts).to(dev), torch.from_numpy(chans.astype(np.int32)).to(dev)
         x = ops.stft(a2, n_fft, hop_length, chunk_start=st, chunk_row=rows, chunk_len=T)      # (n_clips * n_ch, 2, bins, frames)
-        if stats is None:
-            ops.standardize_(x)
-        else:
-            ops.standardize_with_(x, stats[0], stats[1])
+        ops.standardize_(x)
         an.pol = ops.polar(x)
     return an
 

@@ -10,6 +10,10 @@ synchronises every step at train.py:64-65).
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N train.py ...``; one process per GPU,
 RCCL all-reduce of gradients, each rank reads clips rank::world of every epoch's permutation.
 
+``--audio PATH [PATH ...]`` trains from raw wav files instead of ``--train``: the tracks are resampled to ``--rsr`` on the device
+and ``phasegen.data.AudioCropLoader`` draws fresh crops every epoch (one fused STFT + standardise + polar launch per batch); the
+(mean, std) it normalises with go to ``{log_dir}/audio_stats.npy``, the file ``reconstruct.py --stats`` reads.
+
 Out of scope here: the TensorBoard validation dump of train.py:69-124 -- a JSON-lines log is
 written instead.
 """
@@ -45,13 +49,21 @@ def main():
     ap.add_argument("--grad_compress", choices=["none", "bf16"], default="none", help="payload of the data-parallel gradient all-reduce")
     ap.add_argument("--precision", choices=["fp32", "bf16x3", "bf16"], default="fp32",
                     help="MFMA operand mode of the convolutions (pg_conv_args.precision): fp32 = the reference's arithmetic")
+    ap.add_argument("--audio", nargs="+", default=None, metavar="PATH",
+                    help="train from raw audio: wav files or directories of them; fresh crops every epoch through "
+                         "phasegen.data.AudioCropLoader instead of --train")
+    ap.add_argument("--rsr", type=int, default=16000, help="--audio: sample rate the tracks are resampled to (preproc_mdb.py:204)")
+    ap.add_argument("--n_random", type=int, default=30, help="--audio: random crops after every aligned chunk (preproc_mdb.py:205)")
+    ap.add_argument("--chunk", type=float, default=4.064, help="--audio: seconds per clip (preproc_mdb.py:203)")
+    ap.add_argument("--stats", default=None, metavar="FILE",
+                    help="--audio: *_audio_stats.npy with the (mean, std) to normalise with (default: computed from the tracks)")
     a = ap.parse_args()
 
     import numpy as np
     import torch
     import torch.distributed as dist
     from phasegen import detgen
-    from phasegen.data import SpectrogramLoader, get_fft_npy_loader
+    from phasegen.data import AudioCropLoader, SpectrogramLoader, get_fft_npy_loader
     from phasegen.model import UNetModel
     from phasegen.trainer import Trainer
     from phasegen.validate import validation_metrics
@@ -66,6 +78,22 @@ def main():
     if a.synthetic:
         d = torch.from_numpy(detgen.make_batch(a.synthetic, a.channels, a.frames, seed=1)).cuda()
         loader = SpectrogramLoader(d, torch.zeros(a.synthetic, 1, device=d.device), a.batch_size, True, rank, world, seed=0)
+    elif a.audio:
+        from phasegen import preproc
+        files = []
+        for p in a.audio:                                                     # directories: their wav files, by name
+            files += sorted(os.path.join(p, f) for f in os.listdir(p) if f.lower().endswith(".wav")) if os.path.isdir(p) else [p]
+        assert files, "--audio: no wav files"
+        tracks = []
+        for f in files:
+            y, sr = preproc.load_audio(f)
+            tracks.append(preproc.resample(y, sr, a.rsr))
+        stats = tuple(float(v) for v in np.load(a.stats)) if a.stats else None
+        loader = AudioCropLoader(tracks, a.batch_size, t_slice=int(a.chunk * a.rsr), n_fft=a.n_fft, hop_length=a.hop, n_random=a.n_random,
+                                 stats=stats, rank=rank, world=world, seed=0)
+        if rank == 0:                                                         # what reconstruct.py --stats reads
+            os.makedirs(a.log_dir, exist_ok=True)
+            np.save(os.path.join(a.log_dir, "audio_stats.npy"), np.array(loader.stats, np.float64))
     else:
         loader = get_fft_npy_loader([a.train], [0, 1], batch_size=a.batch_size, precon=True, rank=rank, world=world, seed=0)
     trainer = Trainer(model, lr=a.lr, grad_compress=None if a.grad_compress == "none" else a.grad_compress)
