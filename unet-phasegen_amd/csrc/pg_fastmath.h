@@ -2,7 +2,8 @@
 // (exp(m) - 1) e^{j phi}), written for the VALU budget of an HBM-bound kernel.  libm's hypotf + log1pf + atan2f cost ~115 VALU
 // instructions per bin-frame (63 us of the 164 us fused STFT at 64 x 256 frames of 2048 points, measured round 3); sincosf with its
 // Payne-Hanek tail ~100.  These take ~40 and ~22.  Accuracy (float64 reference, tests/test_signal_gpu.py and the G4 golden of the
-// imported data.py at 2e-6 absolute): atan2 <= 3e-7 rad, log1p <= 1 ulp, sincos <= 2.5e-7 absolute for |phi| <= 100.
+// imported data.py at 2e-6 absolute): atan2 <= 3e-7 rad, log1p <= 1 ulp, sincos <= 2.5e-7 + 6e-8 |phi| absolute (checked over
+// |phi| <= 100, where the second term -- the rounding of phi / pi -- is 6e-6: tests/test_z_gl_blocks_gpu.py).
 // Branch cuts are atan2f's own (signed zeros, both axes exact).  Coefficients: tools/fit/fit_math.py (Remez on the absolute error,
 // checked in float32 Horner arithmetic).  One definition each, used by every kernel that needs it, so that the fused STFT+polar
 // kernel and the standalone polar kernel stay bit-identical.

@@ -208,6 +208,9 @@ __global__ __launch_bounds__(256) void shadow_kernel(const float* __restrict__ w
 }
 
 // (B, C, L) fp32 rows -> (B, C, pitch) bf16 rows, activation applied first; the tail [L, pitch) of every row is zeroed.
+// The activation is the select x >= 0 ? x : slope * x, not pg_act_apply's fmaxf(x, slope * x): the two agree bit for bit on every
+// finite x, on +inf and on NaN, but under ReLU fmaxf(-inf, 0 * -inf) hands -inf through as a "rectified" value where the select
+// stores the NaN of 0 * -inf (tests/test_z_pointwise_gpu.py).
 __global__ __launch_bounds__(256) void cast_rows_kernel(const pg_cast_args a) {
     const long rows = (long)a.B * a.C, total = rows * a.pitch;
     const float slope = pg_act_slope(a.act);
@@ -215,7 +218,7 @@ __global__ __launch_bounds__(256) void cast_rows_kernel(const pg_cast_args a) {
         const long row = e / a.pitch; const int l = (int)(e - row * a.pitch);
         const long b = row / a.C, c = row - b * a.C;
         float v = 0.f;
-        if (l < a.L) { v = a.x[b * a.x_bs + c * a.L + l]; v = pg_act_apply(v, slope); }
+        if (l < a.L) { v = a.x[b * a.x_bs + c * a.L + l]; v = v >= 0.f ? v : slope * v; }
         a.y[b * a.y_bs + c * a.pitch + l] = pg_bf16_bits(v);
     }
 }
