@@ -384,6 +384,56 @@ typedef struct pg_stitch_args {
 int64_t pg_workspace_bytes_stitch(const pg_stitch_args* a);  /* host; negative = error code */
 int     pg_stitch(const pg_stitch_args* a, void* stream);
 
+/* The spectral-domain track join (phasegen/track.py, join="spectral"): instead of inverting every clip and crossfading waveforms
+ * (pg_stitch), the clips' PHASES are joined on the track's global frame grid and the track is inverted by ONE pg_istft with the exact
+ * magnitudes.  Two streaming entry points with structs of their own; PG_VERSION is unchanged.  The reference has no counterpart; the
+ * arithmetic below is the contract.  Common geometry: clip k covers the global frames k sf .. k sf + frames - 1 (sf = frame stride
+ * between clips).  Both kernels move 4 frames of a row per thread, as 16-byte accesses where sf, frames, the row lengths, the strides
+ * and the pointers allow (pg_spec_clips: and src_per_out == 1.0) and frame by frame otherwise; both paths give the same bits.  Index
+ * arithmetic is 64-bit.  The library allocates nothing and keeps nothing.
+ *
+ * pg_spec_clips: clip windows of a plane P (n_ch, bins, F_src) fp32, frames fastest, channels p_stride >= bins F_src elements apart
+ *   (the log-magnitude or the angle plane of a (n_ch, 2, bins, F) polar tensor by pointer and stride), optionally resampled along
+ *   time -> out (n_clips, n_ch, bins, frames), dense: the model's input order (clip, channel).
+ *   Output frame f of clip k is global output frame g = k sf + f; its source position is p = (double)g * src_per_out (src_per_out =
+ *   1 / stretch); i0 = min((int64)floor(p), F_src - 1), i1 = min(i0 + 1, F_src - 1), w = (float)(p - floor(p)).  With a = P[c, b, i0]
+ *   and b1 = P[c, b, i1]: out = a bit for bit when w == 0, otherwise out = fl(a + fl(w fl(b1 - a))) in fp32, nothing contracted.
+ *   Hence src_per_out == 1.0 is a pure copy (frames past the source's end repeat its last frame), and n_clips = 1, frames = F_out
+ *   resamples a whole plane.  A (clip, channel) result does not depend on n_clips, n_ch or its position, bit for bit.
+ *   Errors (host side, before any launch): NULL args / P / out PG_ERR_NULL; non-positive sizes, sf < 1, src_per_out not finite or
+ *   <= 0, p_stride < bins F_src PG_ERR_SHAPE; P or out not 4-byte aligned PG_ERR_ALIGN.
+ *
+ * pg_phase_join: phi (n_clips, n_ch, bins, frames) with clip stride, channel stride and row pitch in elements (the first `bins` rows
+ *   of a model output (n, 2 bins, frames) are read in place) -> out (n_ch, bins, F_out) dense, F_out = (n_clips - 1) sf + frames.
+ *   Vf = frames - sf frames are shared by neighbouring clips, 1 <= Vf and 2 Vf <= frames (at most two clips cover a frame); ramp is
+ *   a DEVICE copy of pg_stitch_ramp(Vf) (any Vf positive floats will do).
+ *   Global frame g: k = min(g div sf, n_clips - 1), j = g - k sf.  If k >= 1 and j < Vf the frame is shared: with a = ramp[Vf-1-j],
+ *   b = ramp[j], lo = phi[k-1][j + sf], hi = phi[k][j]:   zr = fl(fl(a cos lo) + fl(b cos hi)), zi = fl(fl(a sin lo) + fl(b sin hi)),
+ *   out = atan2(zi, zr) -- the weighted circular mean, in (-pi, pi]; if zr == 0 and zi == 0, or either is not finite, out =
+ *   (b >= a ? hi : lo).  Every other frame is phi[k][j] copied bit for bit (NOT wrapped: pg_istft mode 0 takes any angle).  sin, cos
+ *   and atan2 are the library's own (csrc/pg_fastmath.h: those pg_istft mode 0 and pg_polar use; absolute errors 2.5e-7 + 6e-8 |phi|
+ *   and 3e-7).  The result does not depend on n_ch or on the channel's position, bit for bit.
+ *   Errors (host side, before any launch): NULL args / phi / out / ramp PG_ERR_NULL; non-positive sizes, sf < 1, Vf < 1, 2 Vf >
+ *   frames, row_pitch < frames, a channel or clip stride (where applied) shorter than its rows PG_ERR_SHAPE; phi, out or ramp not
+ *   4-byte aligned PG_ERR_ALIGN. */
+typedef struct pg_spec_clips_args {
+    int32_t n_clips, n_ch, bins, frames;         /* output (n_clips, n_ch, bins, frames)                                */
+    int32_t sf, _pad0;                           /* clip k begins at global output frame k sf; sf >= 1                  */
+    int64_t F_src;                               /* frames per row of P                                                 */
+    double  src_per_out;                         /* source frames per output frame = 1 / stretch; finite, > 0          */
+    const float* P; int64_t p_stride;            /* (n_ch, bins, F_src), channels p_stride >= bins F_src elements apart */
+    float* out;
+} pg_spec_clips_args;                            /* 64 bytes */
+int pg_spec_clips(const pg_spec_clips_args* a, void* stream);
+typedef struct pg_phase_join_args {
+    int32_t n_clips, n_ch, bins, frames;
+    int32_t sf, _pad0;                           /* Vf = frames - sf; 1 <= Vf, 2 Vf <= frames                           */
+    const float* phi; int64_t clip_stride, ch_stride, row_pitch;   /* phi[k][c][b][f] = phi[k clip_stride + c ch_stride + b row_pitch + f] */
+    float* out;                                  /* (n_ch, bins, (n_clips-1) sf + frames), dense                        */
+    const float* ramp;                           /* DEVICE copy of pg_stitch_ramp(Vf)                                   */
+} pg_phase_join_args;                            /* 72 bytes */
+int pg_phase_join(const pg_phase_join_args* a, void* stream);
+
 /* How far a reconstruction is from its source, reduced on the device: the sums from which SI-SDR / SNR (waveforms) and spectral
  * convergence / log-spectral distance (spectrograms) are formed on the host (phasegen/metrics.py).  The reference has no counterpart
  * (validate.py takes mean absolute waveform errors of three dataset clips on the host); the arithmetic below is the contract.

@@ -161,6 +161,21 @@ class StitchArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class SpecClipsArgs(C.Structure):
+    """pg_spec_clips_args: clip windows of a spectrogram plane, optionally resampled along time (include/phasegen.h)."""
+    _fields_ = [("n_clips", C.c_int32), ("n_ch", C.c_int32), ("bins", C.c_int32), ("frames", C.c_int32),
+                ("sf", C.c_int32), ("_pad0", C.c_int32), ("F_src", C.c_int64), ("src_per_out", C.c_double),
+                ("P", C.c_void_p), ("p_stride", C.c_int64), ("out", C.c_void_p)]
+
+
+class PhaseJoinArgs(C.Structure):
+    """pg_phase_join_args: one phase per global frame from the phases of overlapped clips (include/phasegen.h)."""
+    _fields_ = [("n_clips", C.c_int32), ("n_ch", C.c_int32), ("bins", C.c_int32), ("frames", C.c_int32),
+                ("sf", C.c_int32), ("_pad0", C.c_int32),
+                ("phi", C.c_void_p), ("clip_stride", C.c_int64), ("ch_stride", C.c_int64), ("row_pitch", C.c_int64),
+                ("out", C.c_void_p), ("ramp", C.c_void_p)]
+
+
 class WaveCompareArgs(C.Structure):
     """pg_wave_compare_args: six sums per signal of a reference / estimate pair of waveforms (include/phasegen.h)."""
     _fields_ = [("n_signals", C.c_int32), ("_pad0", C.c_int32), ("n", C.c_int64),
@@ -222,6 +237,8 @@ SYMBOLS = {
     "pg_stitch_ramp": (C.c_int, [C.c_void_p, C.c_int32]),
     "pg_workspace_bytes_stitch": (C.c_int64, [C.POINTER(StitchArgs)]),
     "pg_stitch": (C.c_int, [C.POINTER(StitchArgs), C.c_void_p]),
+    "pg_spec_clips": (C.c_int, [C.POINTER(SpecClipsArgs), C.c_void_p]),
+    "pg_phase_join": (C.c_int, [C.POINTER(PhaseJoinArgs), C.c_void_p]),
     "pg_workspace_bytes_wave_compare": (C.c_int64, [C.POINTER(WaveCompareArgs)]),
     "pg_wave_compare": (C.c_int, [C.POINTER(WaveCompareArgs), C.c_void_p]),
     "pg_workspace_bytes_spec_compare": (C.c_int64, [C.POINTER(SpecCompareArgs)]),

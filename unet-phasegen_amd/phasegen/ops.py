@@ -841,6 +841,80 @@ def stitch(clips, step, n_out, normalize=False, out=None, return_status=False):
     return (out, status[0], status[1]) if return_status else out
 
 
+def spec_clips(plane, n_clips, frames, sf, src_per_out=1.0, out=None):
+    """Clip windows of a spectrogram plane, optionally resampled along time (pg_spec_clips): plane (n_ch, bins, F_src) float32 on the
+    device, frames contiguous, rows F_src apart, the channel stride free (``pol[:, 0]`` of a (n_ch, 2, bins, F) polar tensor is read in
+    place) -> (n_clips, n_ch, bins, frames), dense.  Frame f of clip k is the plane at position (k * sf + f) * src_per_out, linearly
+    interpolated between its two neighbours and clamped at the last frame; src_per_out == 1.0 copies.  n_clips = 1, frames = F_out
+    resamples the whole plane."""
+    if not (torch.is_tensor(plane) and plane.is_cuda and plane.dtype == torch.float32 and plane.dim() == 3):
+        raise ValueError("spec_clips: plane must be a 3-D float32 device tensor (n_ch, bins, F_src)")
+    _on_current_device(plane, "plane")
+    n_ch, bins, F_src = plane.shape
+    n_clips, frames, sf, src_per_out = int(n_clips), int(frames), int(sf), float(src_per_out)
+    if min(n_ch, bins, F_src, n_clips, frames) < 1 or sf < 1:
+        raise ValueError(f"spec_clips: sizes must be positive (plane {tuple(plane.shape)}, n_clips {n_clips}, frames {frames}, sf {sf})")
+    if not 0.0 < src_per_out < float("inf"):
+        raise ValueError(f"spec_clips: src_per_out must be finite and positive, got {src_per_out}")
+    if (F_src > 1 and plane.stride(2) != 1) or (bins > 1 and plane.stride(1) != F_src):
+        raise ValueError(f"spec_clips: frames must be contiguous and rows F_src apart (strides {plane.stride()})")
+    p_stride = plane.stride(0) if n_ch > 1 else bins * F_src
+    if p_stride < bins * F_src:
+        raise ValueError(f"spec_clips: channels overlap in memory (strides {plane.stride()})")
+    want = (n_clips, n_ch, bins, frames)
+    if out is None:
+        out = torch.empty(want, device=plane.device, dtype=torch.float32)
+    elif tuple(out.shape) != want:
+        raise ValueError(f"spec_clips: out must be {want}, got {tuple(out.shape)}")
+    a = _lib.SpecClipsArgs()
+    a.n_clips, a.n_ch, a.bins, a.frames, a.sf, a.F_src, a.src_per_out = n_clips, n_ch, bins, frames, sf, F_src, src_per_out
+    a.P, a.p_stride, a.out = plane.data_ptr(), p_stride, _dense(out, "out")
+    _lib.check(_lib.load().pg_spec_clips(C.byref(a), _stream()), "spec_clips")
+    return out
+
+
+def phase_join(phi, sf, ramp=None, out=None):
+    """One phase per global frame from the phases of overlapped clips (pg_phase_join): phi (n_clips, n_ch, bins, frames) float32 on
+    the device, frames contiguous, the other three strides free (``y.view(n_clips, n_ch, 2 * bins, frames)[:, :, :bins]`` of a model
+    output is read in place); clip k begins at global frame k * sf and shares Vf = frames - sf frames (1 <= Vf, 2 * Vf <= frames)
+    with the next one -> (n_ch, bins, (n_clips - 1) * sf + frames).  A shared frame gets the circular mean of its two phases under
+    the sin^2 ramp of ``stitch`` (``ramp``: Vf device floats to use instead), every other frame its clip's phase bit for bit."""
+    if not (torch.is_tensor(phi) and phi.is_cuda and phi.dtype == torch.float32 and phi.dim() == 4):
+        raise ValueError("phase_join: phi must be a 4-D float32 device tensor (n_clips, n_ch, bins, frames)")
+    _on_current_device(phi, "phi")
+    n_clips, n_ch, bins, frames = phi.shape
+    sf = int(sf)
+    Vf = frames - sf
+    if min(n_clips, n_ch, bins, frames) < 1:
+        raise ValueError(f"phase_join: empty phi {tuple(phi.shape)}")
+    if sf < 1 or Vf < 1 or 2 * Vf > frames:
+        raise ValueError(f"phase_join: sf {sf} with clips of {frames} frames (need 1 <= frames - sf and 2 * (frames - sf) <= frames)")
+    if frames > 1 and phi.stride(3) != 1:
+        raise ValueError(f"phase_join: frames must be contiguous (strides {phi.stride()})")
+    row_pitch = phi.stride(2) if bins > 1 else frames
+    plane = (bins - 1) * row_pitch + frames
+    ch_stride = phi.stride(1) if n_ch > 1 else plane
+    clip_stride = phi.stride(0) if n_clips > 1 else n_ch * max(ch_stride, plane)
+    if row_pitch < frames or ch_stride < plane or clip_stride < plane:
+        raise ValueError(f"phase_join: rows overlap in memory (strides {phi.stride()})")
+    F_out = (n_clips - 1) * sf + frames
+    want = (n_ch, bins, F_out)
+    if out is None:
+        out = torch.empty(want, device=phi.device, dtype=torch.float32)
+    elif tuple(out.shape) != want:
+        raise ValueError(f"phase_join: out must be {want}, got {tuple(out.shape)}")
+    if ramp is None:
+        ramp = _stitch_ramp(Vf, phi.device)
+    elif tuple(ramp.shape) != (Vf,):
+        raise ValueError(f"phase_join: ramp must hold Vf = {Vf} floats, got {tuple(ramp.shape)}")
+    a = _lib.PhaseJoinArgs()
+    a.n_clips, a.n_ch, a.bins, a.frames, a.sf = n_clips, n_ch, bins, frames, sf
+    a.phi, a.clip_stride, a.ch_stride, a.row_pitch = phi.data_ptr(), clip_stride, ch_stride, row_pitch
+    a.out, a.ramp = _dense(out, "out"), _dense(ramp, "ramp")
+    _lib.check(_lib.load().pg_phase_join(C.byref(a), _stream()), "phase_join")
+    return out
+
+
 _compare_ws = _StreamCache()
 _caches.append(_compare_ws)
 

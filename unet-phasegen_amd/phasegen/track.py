@@ -15,9 +15,21 @@ device:
   ISTFT          audio.synthesize, un-normalised clips of T = hop * (frames - 1) samples
   stitch         ops.stitch: sin^2 crossfade over the overlap, finite check and peak normalisation over the whole result
 
+``join="spectral"`` joins the clips on the track's global FRAME grid instead (clip k = frames k sf .. k sf + frames - 1, sf = step /
+hop): ONE whole-track STFT per channel (ops.stft_crops), clip windows of its log-magnitude plane (ops.spec_clips), the same forward,
+ONE phase per frame (ops.phase_join: where two clips overlap, the circular mean of their phases under the stitch's ramp), ONE ISTFT
+with the plane's exact magnitudes.  ``stretch`` resamples the magnitudes along time in the same kernel (the result is ``stretch``
+times as long at the same pitch) and ``pitch_shift`` resamples that back (same length, other pitch).  ``spectral_plan`` is the plan.
+
 ``evaluate_track`` runs the analysis once, synthesises the track from several phase sources (the model's, none at all, the
 analysis' own, Griffin-Lim's) and reports ``metrics.compare_audio`` of each against the input.
 """
+import collections
+import fractions
+import functools
+import inspect
+import math
+
 import numpy as np
 import torch
 
@@ -47,11 +59,11 @@ PHASES = ("unet", "zero", "original", "griffinlim")
 
 class _Analysis:
     """What every phase source shares: the track at ``sr`` (a2: (channels, a_len)), the clip plan and the clips' [log1p|z| ; angle]."""
-    __slots__ = ("a2", "mono", "n_ch", "a_len", "T", "step", "n_clips", "bins", "pol")
+    __slots__ = ("a2", "mono", "n_ch", "a_len", "T", "step", "n_clips", "bins", "pol", "plan", "stretch")
 
 
-def _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type):
-    """resample -> chunked STFT -> standardise -> polar, once per track."""
+def _load(audio, osr, sr, res_type):
+    """The track at ``sr`` on the device, as an _Analysis with a2, mono, n_ch and a_len set."""
     if osr is not None:
         a = preproc.resample(audio, osr, sr, res_type=res_type)
     elif torch.is_tensor(audio):
@@ -62,8 +74,15 @@ def _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, r
         raise ValueError(f"reconstruct_track: audio must be (samples,) or (channels, samples), got {tuple(a.shape)}")
     an = _Analysis()
     an.mono = a.dim() == 1
-    an.a2 = a2 = (a[None] if an.mono else a).contiguous()
-    an.n_ch, an.a_len = n_ch, a_len = a2.shape
+    an.a2 = (a[None] if an.mono else a).contiguous()
+    an.n_ch, an.a_len = an.a2.shape
+    return an
+
+
+def _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type):
+    """resample -> chunked STFT -> standardise -> polar, once per track."""
+    an = _load(audio, osr, sr, res_type)
+    a2, n_ch, a_len = an.a2, an.n_ch, an.a_len
     an.T, an.step, an.n_clips = T, step, n_clips = track_plan(a_len, frames, hop_length, overlap_frames)
     an.bins = n_fft // 2
     dev = a2.device
@@ -114,6 +133,107 @@ def _synthesise(an, model, phase, hop_length, clip_batch, normalize, gl_iters=25
     return out
 
 
+JOINS = ("waveform", "spectral")
+SpectralPlan = collections.namedtuple("SpectralPlan", "sf Vf a_out n_clips F_out F_src n_src")
+
+
+def spectral_plan(a_len, frames, hop_length, overlap_frames, stretch=1.0):
+    """The frame-grid plan of the spectral join for a track of ``a_len`` samples played ``stretch`` times as long (host only):
+      sf = frames - 1 - overlap_frames     frame stride between clips (``track_plan``'s step / hop)
+      Vf = overlap_frames + 1              frames two neighbouring clips share (their edge frames coincide even without overlap)
+      a_out = round(a_len * stretch)       output samples;  n_clips = track_plan(a_out, ...)'s
+      F_out = (n_clips - 1) * sf + frames  output frames: hop * (F_out - 1) >= a_out samples come out of the ISTFT
+      F_src = floor((F_out - 1) / stretch) + 2     source frames, so that F_src - 1 >= (F_out - 1) / stretch: the interpolation's
+                                                   upper neighbour exists for every output frame
+      n_src = hop * (F_src - 1)            length of the analysed signal, the track zero-filled past a_len
+    ValueError: ``stretch`` not finite or outside [0.25, 4], whatever ``track_plan`` raises, 2 * Vf > frames (odd ``frames`` at the
+    largest overlap: more than two clips would cover a frame)."""
+    stretch = float(stretch)
+    if not (stretch == stretch and 0.25 <= stretch <= 4.0):
+        raise ValueError(f"spectral_plan: stretch must be finite and within [0.25, 4], got {stretch}")
+    a_len, frames, hop_length, overlap_frames = int(a_len), int(frames), int(hop_length), int(overlap_frames)
+    if a_len < 1:
+        raise ValueError(f"spectral_plan: a_len {a_len} must be positive")
+    a_out = int(round(a_len * stretch))
+    _T, _step, n_clips = track_plan(a_out, frames, hop_length, overlap_frames)
+    sf, Vf = frames - 1 - overlap_frames, overlap_frames + 1
+    if 2 * Vf > frames:
+        raise ValueError(f"spectral_plan: overlap_frames {overlap_frames} + 1 shared frames exceed half a clip of {frames} frames")
+    F_out = (n_clips - 1) * sf + frames
+    F_src = int(math.floor((F_out - 1) / stretch)) + 2
+    return SpectralPlan(sf, Vf, a_out, n_clips, F_out, F_src, hop_length * (F_src - 1))
+
+
+def _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch):
+    """resample -> ONE whole-track STFT per channel -> standardise -> polar: an.pol (n_ch, 2, bins, F_src) on the global frame grid."""
+    an = _load(audio, osr, sr, res_type)
+    a2, n_ch, a_len = an.a2, an.n_ch, an.a_len
+    an.stretch = float(stretch)
+    an.plan = pl = spectral_plan(a_len, frames, hop_length, overlap_frames, stretch)
+    an.n_clips, an.bins = pl.n_clips, n_fft // 2
+    dev = a2.device
+    with torch.cuda.device(dev), torch.no_grad():
+        if stats is not None:
+            # channel c is the region [c a_len, (c + 1) a_len) of the flat buffer; the crop is zero past its end (pg_stft_crops)
+            begin = torch.arange(n_ch, dtype=torch.int64) * a_len
+            an.pol = ops.stft_crops(a2.reshape(-1), begin.to(dev), (begin + a_len).to(dev), pl.n_src, n_fft, hop_length, polar=True,
+                                    stats=(stats[0], stats[1]))
+            return an
+        # the track's own moments (zero tail included) need the unnormalised tensor: three launches on the zero-padded track
+        padded = torch.zeros(n_ch, pl.n_src, device=dev, dtype=torch.float32)
+        n = min(a_len, pl.n_src)
+        padded[:, :n] = a2[:, :n]
+        x = ops.stft(padded, n_fft, hop_length)                                               # (n_ch, 2, bins, F_src)
+        ops.standardize_(x)
+        an.pol = ops.polar(x)
+    return an
+
+
+def _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize):
+    """One phase source -> the track (channels, a_out) through the spectral join: clip windows of the log-magnitude plane, forward,
+    ONE phase per global frame (ops.phase_join), ONE ISTFT with the plane's own magnitudes; raises when a sample is not finite."""
+    pl, n_ch, bins = an.plan, an.n_ch, an.bins
+    spo = 1.0 / an.stretch
+    with torch.cuda.device(an.a2.device), torch.no_grad():
+        logmag = an.pol[:, 0]                                                                 # (n_ch, bins, F_src), read in place
+        if phase == "zero":
+            ph = torch.zeros(n_ch, bins, pl.F_out, device=logmag.device)                      # (the join of zeros is zero)
+        elif phase == "original":
+            ph = ops.phase_join(ops.spec_clips(an.pol[:, 1], pl.n_clips, frames, pl.sf, spo), pl.sf)
+        else:
+            x = ops.spec_clips(logmag, pl.n_clips, frames, pl.sf, spo).view(pl.n_clips * n_ch, bins, frames)   # (clip, channel) order
+            n_sig = x.shape[0]
+            if n_sig <= clip_batch:       # one forward: the phase half of its (n_sig, 2 bins, frames) output is joined in place
+                phi = model.forward(x, per_clip=True).view(pl.n_clips, n_ch, 2 * bins, frames)[:, :, :bins]
+            else:
+                phi = torch.empty(pl.n_clips, n_ch, bins, frames, device=logmag.device)
+                flat = phi.view(n_sig, bins, frames)
+                for i in range(0, n_sig, clip_batch):
+                    flat[i:i + clip_batch] = model.forward(x[i:i + clip_batch], per_clip=True)[:, :bins]
+            ph = ops.phase_join(phi, pl.sf)
+        # the magnitudes on the output grid: the plane itself, cut (or time-resampled) to F_out frames by the same kernel
+        mag = ops.spec_clips(logmag, 1, pl.F_out, pl.F_out, spo)[0]
+        audio = ops.istft(mag, ph, hop_length, mode=0, normalize=False)                       # (n_ch, hop * (F_out - 1))
+        out, _, bad = ops.stitch(audio[:, None, :pl.a_out], pl.a_out, pl.a_out, normalize=normalize, return_status=True)
+        if int(bad.item()) != 0:
+            raise ValueError("Audio buffer is not finite everywhere")
+    return out
+
+
+def _check_join(who, join, stretch, phase_list):
+    if join not in JOINS:
+        raise ValueError(f"{who}: join must be 'waveform' or 'spectral', got {join!r}")
+    stretch = float(stretch)
+    if stretch != 1.0 and join != "spectral":
+        raise ValueError(f"{who}: stretch {stretch} needs join='spectral'")
+    for p in phase_list:
+        if join == "spectral" and p == "griffinlim":
+            raise ValueError(f"{who}: phase 'griffinlim' is not available under join='spectral'")
+        if stretch != 1.0 and p not in ("unet", "zero"):
+            raise ValueError(f"{who}: stretch {stretch} needs phase 'unet' or 'zero', got {p!r} (the analysis' own phase does not fit a resampled spectrogram)")
+    return stretch
+
+
 def peak_normalize(audio):
     """utils.py:42 for a whole track on the device: audio (samples,) or (channels, samples) divided by its joint peak -- the second
     launch of pg_stitch over one clip per channel, so ``peak_normalize(reconstruct_track(..., normalize=False))`` has the bits of
@@ -125,6 +245,45 @@ def peak_normalize(audio):
     return out[0] if audio.dim() == 1 else out
 
 
+def _keyword_options(impl, **options):
+    """Decorator for the two public track functions: the decorated ``def`` states the POSITIONAL parameter list and the docstring --
+    the list callers of the waveform-only functions have always seen, which stays as it is (``inspect.signature`` reports it) -- and
+    the call itself goes to ``impl`` with, in addition, the keyword-only ``options`` (name=default), which may be passed by keyword
+    only.  ``fn.options`` lists them."""
+    def deco(fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def call(*args, **kw):
+            opts = {k: kw.pop(k, d) for k, d in options.items()}
+            bound = sig.bind(*args, **kw)
+            bound.apply_defaults()
+            return impl(**bound.arguments, **opts)
+        call.options = dict(options)
+        return call
+    return deco
+
+
+def _reconstruct_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phase, normalize,
+                       join, stretch):
+    """``reconstruct_track`` with its keyword-only options spelled out."""
+    if phase not in ("unet", "original", "zero"):
+        raise ValueError(f"reconstruct_track: phase must be 'unet', 'original' or 'zero', got {phase!r}")
+    if phase == "unet" and model is None:
+        raise ValueError("reconstruct_track: phase='unet' needs a model")
+    if clip_batch < 1:
+        raise ValueError("reconstruct_track: clip_batch must be positive")
+    stretch = _check_join("reconstruct_track", join, stretch, (phase,))
+    if join == "spectral":
+        an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch)
+        out = _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize)
+        return out[0] if an.mono else out
+    an = _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type)
+    out = _synthesise(an, model, phase, hop_length, clip_batch, normalize)
+    return out[0] if an.mono else out
+
+
+@_keyword_options(_reconstruct_track, join="waveform", stretch=1.0)
 def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None,
                       osr=None, sr=16000, res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True):
     """audio (samples,) or (channels, samples), host array or device tensor, at ``sr`` -- or at ``osr`` when given (resampled to
@@ -132,28 +291,17 @@ def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, over
     predicted by ``model`` (phase="unet"), kept from the analysis (phase="original": the chunk / stitch round trip) or all zero
     (phase="zero", the reference's "no phase" comparator); ``model`` may be None for the last two.  ``stats`` = (mean, std) of the
     training set; None: the track's own moments.  ``normalize``: peak-normalise over all channels jointly (utils.py:42 for the whole
-    track).  Raises ValueError("Audio buffer is not finite everywhere") as ``audio.generate_audio`` does."""
-    if phase not in ("unet", "original", "zero"):
-        raise ValueError(f"reconstruct_track: phase must be 'unet', 'original' or 'zero', got {phase!r}")
-    if phase == "unet" and model is None:
-        raise ValueError("reconstruct_track: phase='unet' needs a model")
-    if clip_batch < 1:
-        raise ValueError("reconstruct_track: clip_batch must be positive")
-    an = _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type)
-    out = _synthesise(an, model, phase, hop_length, clip_batch, normalize)
-    return out[0] if an.mono else out
+    track).  Raises ValueError("Audio buffer is not finite everywhere") as ``audio.generate_audio`` does.
+    Keyword-only options (``reconstruct_track.options``; the positional parameter list above is the waveform-only call's and stays):
+    ``join="waveform"`` inverts every clip and crossfades the waveforms (ops.stitch); ``join="spectral"`` joins the clips' PHASES on
+    the track's frame grid (ops.phase_join: one phase per frame, the circular mean where two clips overlap) and inverts the whole
+    track once with its exact magnitudes.  ``stretch=1.0`` (spectral join, phase "unet" or "zero"): the magnitudes are resampled
+    along time and the result has round(a_len * stretch) samples per channel at the same pitch."""
 
 
-def evaluate_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
-                   res_type="kaiser_best", clip_batch=64, phases=("unet", "zero", "original"), gl_iters=250, gl_seed=0, floor=1e-10,
-                   return_audio=False):
-    """The quality report of a track: ONE analysis (as ``reconstruct_track``), then for every entry of ``phases`` -- "unet" (the
-    model's phase), "zero" (none), "original" (the analysis' own: what the chunk / stitch round trip alone costs), "griffinlim"
-    (``audio.griffin_lim_batch`` on exp(logmag) - 1 per clip, ``gl_iters`` iterations from noise seeded ``gl_seed`` + clip index) --
-    the un-normalised stitched track and ``metrics.compare_audio(input at sr, track, n_fft, hop_length, floor)``.
-    -> {"n_samples", "sr", "n_clips", "metrics": {phase: dict}} and, with ``return_audio``, "audio": {phase: device tensor shaped
-    like the input}.  The "unet" audio has the bits of ``reconstruct_track(..., normalize=False)``.  ``model`` may be None when
-    "unet" is not asked for."""
+def _evaluate_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phases, gl_iters,
+                    gl_seed, floor, return_audio, join):
+    """``evaluate_track`` with its keyword-only option spelled out."""
     phases = tuple(phases)
     for p in phases:
         if p not in PHASES:
@@ -164,15 +312,67 @@ def evaluate_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap
         raise ValueError("evaluate_track: phase 'unet' needs a model")
     if clip_batch < 1:
         raise ValueError("evaluate_track: clip_batch must be positive")
-    an = _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type)
+    _check_join("evaluate_track", join, 1.0, phases)
+    if join == "spectral":
+        an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, 1.0)
+    else:
+        an = _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type)
     ref = an.a2[0] if an.mono else an.a2
-    res = {"n_samples": int(an.a_len), "sr": int(sr), "n_clips": int(an.n_clips), "metrics": {}}
+    res = {"n_samples": int(an.a_len), "sr": int(sr), "n_clips": int(an.n_clips), "join": join, "metrics": {}}
     if return_audio:
         res["audio"] = {}
     for p in phases:
-        out = _synthesise(an, model, p, hop_length, clip_batch, False, gl_iters, gl_seed)
+        if join == "spectral":
+            out = _synthesise_spectral(an, model, p, hop_length, frames, clip_batch, False)
+        else:
+            out = _synthesise(an, model, p, hop_length, clip_batch, False, gl_iters, gl_seed)
         out = out[0] if an.mono else out
         res["metrics"][p] = metrics.compare_audio(ref, out, n_fft, hop_length, floor)
         if return_audio:
             res["audio"][p] = out
     return res
+
+
+@_keyword_options(_evaluate_track, join="waveform")
+def evaluate_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
+                   res_type="kaiser_best", clip_batch=64, phases=("unet", "zero", "original"), gl_iters=250, gl_seed=0, floor=1e-10,
+                   return_audio=False):
+    """The quality report of a track: ONE analysis (as ``reconstruct_track``), then for every entry of ``phases`` -- "unet" (the
+    model's phase), "zero" (none), "original" (the analysis' own: what the chunk / stitch round trip alone costs), "griffinlim"
+    (``audio.griffin_lim_batch`` on exp(logmag) - 1 per clip, ``gl_iters`` iterations from noise seeded ``gl_seed`` + clip index) --
+    the un-normalised stitched track and ``metrics.compare_audio(input at sr, track, n_fft, hop_length, floor)``.
+    -> {"n_samples", "sr", "n_clips", "join", "metrics": {phase: dict}} and, with ``return_audio``, "audio": {phase: device tensor
+    shaped like the input}.  The "unet" audio has the bits of ``reconstruct_track(..., normalize=False)``.  ``model`` may be None
+    when "unet" is not asked for.  Keyword-only option (``evaluate_track.options``): ``join="waveform"`` or ``"spectral"``, as in
+    ``reconstruct_track`` ("griffinlim" is not available under "spectral")."""
+
+
+def pitch_ratio(semitones, max_denominator=1024):
+    """(stretch, Fraction p / q): the stretch 2 ** (semitones / 12) and the rational p / q closest to it with q <= 1024, the most
+    phases pg_resample takes (its taps stay below 2048 for every ratio up to 4).  Resampling by q / p shifts the pitch by p / q
+    instead of the exact ratio: at most 0.85 cent off for any shift within two octaves, at most 0.027 cent for a whole number of
+    semitones (1200 log2((p / q) / stretch), evaluated for every shift in steps of 0.001 semitone)."""
+    stretch = 2.0 ** (float(semitones) / 12.0)
+    if not (stretch == stretch and 0.25 <= stretch <= 4.0):
+        raise ValueError(f"pitch_shift: semitones must be within [-24, 24], got {semitones}")
+    return stretch, fractions.Fraction(stretch).limit_denominator(max_denominator)
+
+
+def pitch_shift(model, audio, semitones, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
+                res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True):
+    """Pitch shift by ``semitones`` (within two octaves) without a change of tempo: the track is stretched by 2 ** (semitones / 12)
+    through the spectral join (``reconstruct_track(join="spectral", stretch=...)``: same pitch, longer or shorter) and played back
+    faster or slower by the same ratio (``preproc.resample`` by q / p, see ``pitch_ratio`` for the error in cents), then trimmed or
+    zero-padded to the input's length at ``sr``.  -> float32 device tensor shaped like the input at ``sr``."""
+    stretch, ratio = pitch_ratio(semitones)
+    a = preproc.resample(audio, osr, sr, res_type=res_type) if osr is not None else audio
+    a_len = int(a.shape[-1])
+    out = reconstruct_track(model, a, n_fft, hop_length, frames, overlap_frames, stats, None, sr, res_type, clip_batch, phase,
+                            normalize=False, join="spectral", stretch=stretch)
+    if ratio != 1:
+        out = preproc.resample(out, ratio.numerator, ratio.denominator, res_type=res_type)
+    if out.shape[-1] >= a_len:
+        out = out[..., :a_len]
+    else:
+        out = torch.nn.functional.pad(out, (0, a_len - out.shape[-1]))
+    return peak_normalize(out) if normalize else out.contiguous()

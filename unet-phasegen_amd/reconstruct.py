@@ -12,6 +12,10 @@ log-spectral distance of the track against the input at ``--sr``, for the model'
 ``--report_phases`` (``zero``: no phase at all, ``original``: the analysis' own phase, i.e. what chunking and stitching alone cost,
 ``griffinlim``: ``--gl_iters`` Griffin-Lim iterations from noise), written as JSON.  The model still runs once and the wav is the
 same file, byte for byte.
+
+``--join spectral`` joins the clips in the spectrogram domain (one phase per frame of the track, one ISTFT with the exact
+magnitudes) instead of crossfading their waveforms.  ``--stretch R`` plays the track R times as long at the same pitch and
+``--pitch SEMITONES`` shifts its pitch at the same tempo; both imply the spectral join, and neither can be reported against the input.
 """
 import argparse
 import json
@@ -42,7 +46,22 @@ def main():
     parser.add_argument("--report_phases", default="unet,zero,original",
                         help="comma list of phase sources to report: unet, zero, original, griffinlim ('unet' is always included)")
     parser.add_argument("--gl_iters", default=250, type=int, help="Griffin-Lim iterations of the 'griffinlim' report phase")
+    parser.add_argument("--join", choices=["waveform", "spectral"], default=None,
+                        help="how overlapped clips become one track: crossfade the clips' waveforms (default), or join their phases "
+                             "on the track's frame grid and invert once with the exact magnitudes")
+    parser.add_argument("--stretch", default=None, type=float, metavar="R",
+                        help="play R times as long at the same pitch, 0.25 <= R <= 4 (implies --join spectral)")
+    parser.add_argument("--pitch", default=None, type=float, metavar="SEMITONES",
+                        help="shift the pitch at the same tempo, within +-24 semitones (implies --join spectral)")
     args = parser.parse_args()
+    if args.stretch is not None and args.pitch is not None:
+        parser.error("--stretch and --pitch exclude each other")
+    modified = (args.stretch is not None and args.stretch != 1.0) or args.pitch is not None
+    if modified and args.join == "waveform":
+        parser.error("--stretch and --pitch need --join spectral")
+    if modified and args.report is not None:
+        parser.error("--report compares against the input: it works with --join, not with --stretch or --pitch")
+    join = "spectral" if (modified or args.stretch is not None) and args.join is None else (args.join or "waveform")
     n_fft = 2 * args.channels if args.n_fft is None else args.n_fft
     hop = n_fft // 4 if args.hop is None else args.hop
     if n_fft != 2 * args.channels:
@@ -76,10 +95,12 @@ def main():
     start = time.time()
     kw = dict(n_fft=n_fft, hop_length=hop, frames=args.frames, overlap_frames=args.overlap_frames, stats=stats, osr=file_sr, sr=args.sr)
     report = None
-    if args.report is None:
-        out = track.reconstruct_track(model, audio, **kw)
+    if args.pitch is not None:
+        out = track.pitch_shift(model, audio, args.pitch, **kw)
+    elif args.report is None:
+        out = track.reconstruct_track(model, audio, join=join, stretch=1.0 if args.stretch is None else args.stretch, **kw)
     else:
-        report = track.evaluate_track(model, audio, phases=phases, gl_iters=args.gl_iters, return_audio=True, **kw)
+        report = track.evaluate_track(model, audio, phases=phases, gl_iters=args.gl_iters, return_audio=True, join=join, **kw)
         out = track.peak_normalize(report.pop("audio")["unet"])
     out = out.cpu().numpy()
     took = time.time() - start
