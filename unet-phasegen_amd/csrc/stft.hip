@@ -41,6 +41,12 @@ __device__ __host__ __forceinline__ int reflect_index(int pos, int n) {
 }
 
 __device__ __forceinline__ float hann(int k, int n) { return 0.5f - 0.5f * cospif(2.0f * (float)k / (float)n); }
+// The same window as sin^2(pi k / n), for the taps a frame is MULTIPLIED by.  hann() is within u / 2 absolutely, which is all a
+// window-sum-square needs, but near the frame edges that is nothing relative to the window itself (tap 1 of 64: 2.4e-3): a frame
+// whose only samples sit in its first or last taps (the first frame behind a chunk's zero tail) came out 10 times less accurate,
+// relative to its own norm, than an fp32 transform with a rounded window (tests/test_z_signal_values_gpu.py, crops-f4).  sinpif is
+// accurate relative to its value, so this form is within a few u of the window at every tap.
+__device__ __forceinline__ float hann_tap(int k, int n) { const float s = sinpif((float)k / (float)n); return s * s; }
 
 // Maximum of mx over a workgroup of WAVES waves, returned to every thread (a maximum is exact in any order): shuffle butterfly, one
 // LDS slot per wave, fold.  red[] is free again after the caller's next barrier.
@@ -142,7 +148,7 @@ template <class Args> __device__ __forceinline__ void stft_r2_body(const Args& a
     fill_twiddles(tw, N);
     for (int k = threadIdx.x; k < N; k += blockDim.x) {
         const int idx = reflect_index(t * a.hop + k - (N >> 1), a.n_samples);
-        buf0[k] = make_float2((idx < src.lim ? src.p[idx] : 0.f) * hann(k, N), 0.f);
+        buf0[k] = make_float2((idx < src.lim ? src.p[idx] : 0.f) * hann_tap(k, N), 0.f);
     }
     __syncthreads();
     const float2* X = fft_lds(buf0, buf1, tw, N, 1.f);
@@ -317,7 +323,7 @@ template <class Args, bool CHUNKED> __device__ __forceinline__ void stft_frames_
 #pragma unroll
     for (int i = 0; i < M_ITERS; ++i) {
         const int m = threadIdx.x + i * BT;
-        w0[i] = hann(2 * m, N); w1[i] = hann(2 * m + 1, N);
+        w0[i] = hann_tap(2 * m, N); w1[i] = hann_tap(2 * m + 1, N);
     }
 #pragma unroll
     for (int i = 0; i < K_ITERS; ++i)
@@ -454,7 +460,7 @@ __global__ __launch_bounds__(BT) void istft_frames4_kernel(const pg_istft_args a
 #pragma unroll
     for (int i = 0; i < M_ITERS; ++i) {
         const int m = threadIdx.x + i * BT;
-        w0[i] = inv * hann(2 * m, N); w1[i] = inv * hann(2 * m + 1, N);
+        w0[i] = inv * hann_tap(2 * m, N); w1[i] = inv * hann_tap(2 * m + 1, N);
     }
 #pragma unroll
     for (int i = 0; i < K_ITERS; ++i)
@@ -1121,7 +1127,7 @@ __global__ __launch_bounds__(FFT_THREADS) void istft_frames_kernel(const pg_istf
     const float2* x = fft_lds(buf0, buf1, tw, N, -1.f);
     float* f = frames + ((long)sig * a.n_frames + t) * N;
     const float inv = 1.0f / (float)N;
-    for (int n = threadIdx.x; n < N; n += blockDim.x) f[n] = x[n].x * inv * hann(n, N);
+    for (int n = threadIdx.x; n < N; n += blockDim.x) f[n] = x[n].x * inv * hann_tap(n, N);
 }
 
 // Overlap-add, 4 consecutive samples per thread: the <= n_fft/hop frames covering them are read as 16 B pieces, the

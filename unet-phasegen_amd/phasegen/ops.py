@@ -1084,20 +1084,29 @@ def _istft_calls(a_t, b_t, audio, hop, mode, normalize, single_frame):
         yield a
 
 
-def istft(a_t, b_t, hop, mode=0, normalize=True, single_frame=None):
-    """(n, bins, frames) x2 -> (n, hop*(frames-1)).  mode 0: (logmag, phase) per demo.py:39; mode 1: (re, im).
-    utils.py:34-42: zero DC row, librosa.istft, peak normalisation."""
+def _istft_audio(a_t, hop, out):
     n, bins, nf = a_t.shape
-    audio = torch.empty(n, hop * (nf - 1), device=a_t.device, dtype=torch.float32)
+    if out is None:
+        return torch.empty(n, hop * (nf - 1), device=a_t.device, dtype=torch.float32)
+    if tuple(out.shape) != (n, hop * (nf - 1)):
+        raise ValueError(f"istft: out must be {(n, hop * (nf - 1))}, got {tuple(out.shape)}")
+    _dense(out, "out")
+    return out
+
+
+def istft(a_t, b_t, hop, mode=0, normalize=True, single_frame=None, out=None):
+    """(n, bins, frames) x2 -> (n, hop*(frames-1)).  mode 0: (logmag, phase) per demo.py:39; mode 1: (re, im).
+    utils.py:34-42: zero DC row, librosa.istft, peak normalisation.  ``out``: a dense (n, hop*(frames-1)) float32 tensor or view to
+    fill (a view that is not 16-byte aligned takes the three-kernel path at every size: pg_istft's selection rule)."""
+    audio = _istft_audio(a_t, hop, out)
     for a in _istft_calls(a_t, b_t, audio, hop, mode, normalize, single_frame):
         _lib.check(_lib.load().pg_istft(C.byref(a), _stream()), "istft")
     return audio
 
 
-def istft_describe(a_t, b_t, hop, mode=0, normalize=True, single_frame=None):
+def istft_describe(a_t, b_t, hop, mode=0, normalize=True, single_frame=None, out=None):
     """pg_istft_describe for the arguments of ``istft``: one string per call (64 signals each), its launches joined by '|'."""
-    n, bins, nf = a_t.shape
-    audio = torch.empty(n, hop * (nf - 1), device=a_t.device, dtype=torch.float32)
+    audio = _istft_audio(a_t, hop, out)
     return [_describe(_lib.load().pg_istft_describe, a, "istft_describe")
             for a in _istft_calls(a_t, b_t, audio, hop, mode, normalize, single_frame)]
 
