@@ -434,6 +434,51 @@ typedef struct pg_phase_join_args {
 } pg_phase_join_args;                            /* 72 bytes */
 int pg_phase_join(const pg_phase_join_args* a, void* stream);
 
+/* pg_phase_vocoder: the phase-vocoder phase of a time-stretched spectrogram (phasegen/track.py, phase="vocoder"): each bin's analysis
+ * phase is propagated along the OUTPUT frame grid by the frame-to-frame advance measured on the source grid (the recurrence of
+ * librosa.phase_vocoder), and a bin below a magnitude floor takes its analysis phase back.  One streaming kernel with a struct of its
+ * own; PG_VERSION is unchanged.  The reference has no counterpart; the arithmetic below is the contract.
+ *   A: the angle plane (n_ch, bins, F_src) fp32, frames fastest, channels a_stride >= bins F_src elements apart (pol[:, 1] of a
+ *   (n_ch, 2, bins, F) polar tensor by pointer and stride).  M: optional (may be NULL), the log-magnitude plane of the same shape with
+ *   its own channel stride m_stride (pol[:, 0]).  src_per_out = 1 / stretch, a double, finite and > 0.  reset_below: a float, finite
+ *   and >= 0, in the units of M.  F_out >= 1.  -> out (n_ch, bins, F_out), dense fp32.
+ *   Phase matters modulo 2 pi only and is kept as a 32-bit unsigned fraction of a turn; integer addition wraps and is associative, so
+ *   the scan along time is exact in any order.  Constants (each one double division): TWO_PI = 6.283185307179586,
+ *   K = 4294967296.0 / TWO_PI, R = TWO_PI / 4294967296.0.
+ *   Quantisation: q(x) = 0 if x is not finite or |x| > 2^20, otherwise q(x) = (uint32)(int64) rint((double)x * K): one double
+ *   multiply, round half to even, two's-complement wrap.
+ *   Positions (pg_spec_clips's), for output frame g: p = (double)g * src_per_out, i0 = min((int64)floor(p), F_src - 1),
+ *   i1 = min(i0 + 1, F_src - 1).
+ *   Scan, per (channel, bin) row:
+ *     delta[g] = q(A[i1(g)]) - q(A[i0(g)])   in uint32: the wrap is the principal value of the analysis phase advance.  The expected
+ *                advance 2 pi hop k / n_fft of librosa.phase_vocoder cancels modulo 2 pi, so no bin frequency, hop or n_fft enters.
+ *     reset[g] = (g == 0) || (M != NULL && M[i0(g)] < reset_below)          (a NaN in M does not reset)
+ *     acc[g]   = reset[g] ? q(A[i0(g)]) : acc[g-1] + delta[g-1]             in uint32
+ *     out[g]   = (float)((double)(int32)acc[g] * R)
+ *   so every value lies in [-pi, pi) before the one rounding to fp32 (which may deliver the fp32 next to -pi or pi).
+ *   Consequences.  With src_per_out == 1.0 the sum telescopes: acc[g] = q(A[g]) exactly for g < F_src, so a stretch of 1 returns the
+ *   analysis phase (modulo 2 pi) to within one quantisation step (2 pi / 2^33) plus one fp32 rounding.  A bin whose magnitude is below
+ *   the floor carries its analysis phase and resumes accumulating from that phase the moment it rises above the floor: the transient
+ *   and silence phase reset that restores coherence between neighbouring bins at onsets; reset_below == 0 or M == NULL never resets
+ *   after frame 0.  At the end of the source i1 == i0 and the advance is zero.  A row's result does not depend on n_ch, bins or the
+ *   row's position, bit for bit, nor on how the kernel splits the scan.
+ *   Kernel: one 256-thread workgroup per row, chunks of 1024 output frames, 4 per thread; a segmented scan in registers, across the
+ *   wave and across the waves through LDS; 16-byte stores where out and F_out allow, frame by frame otherwise (same bits); 64-bit
+ *   index arithmetic.  The library allocates nothing and keeps nothing.
+ *   Errors (host side, before any launch): NULL args / A / out PG_ERR_NULL; non-positive sizes, src_per_out not finite or <= 0,
+ *   reset_below not finite or < 0, a_stride (or, with M, m_stride) < bins F_src PG_ERR_SHAPE; A, M or out not 4-byte aligned
+ *   PG_ERR_ALIGN. */
+typedef struct pg_phase_vocoder_args {
+    int32_t n_ch, bins;
+    int64_t F_src, F_out;                        /* frames per row of A (and M), frames per row of out                  */
+    double  src_per_out;                         /* source frames per output frame = 1 / stretch; finite, > 0          */
+    float   reset_below; int32_t _pad0;          /* a frame whose M is below this takes its analysis phase; finite, >= 0 */
+    const float* A; int64_t a_stride;            /* (n_ch, bins, F_src), channels a_stride >= bins F_src elements apart */
+    const float* M; int64_t m_stride;            /* optional (NULL: no reset after frame 0), same shape, own stride    */
+    float* out;                                  /* (n_ch, bins, F_out), dense                                          */
+} pg_phase_vocoder_args;                         /* 80 bytes */
+int pg_phase_vocoder(const pg_phase_vocoder_args* a, void* stream);
+
 /* How far a reconstruction is from its source, reduced on the device: the sums from which SI-SDR / SNR (waveforms) and spectral
  * convergence / log-spectral distance (spectrograms) are formed on the host (phasegen/metrics.py).  The reference has no counterpart
  * (validate.py takes mean absolute waveform errors of three dataset clips on the host); the arithmetic below is the contract.

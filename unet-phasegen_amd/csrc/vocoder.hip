@@ -1,0 +1,181 @@
+// vocoder.hip -- pg_phase_vocoder: the phase-vocoder phase of a time-stretched spectrogram (phasegen/track.py, phase="vocoder"), the
+// standard comparator of every time-stretch method.  Each bin's analysis phase is propagated along the OUTPUT frame grid by the
+// frame-to-frame advance measured on the SOURCE grid at the output frame's position (librosa.phase_vocoder's recurrence); a bin that
+// falls below a magnitude floor takes its analysis phase back (the transient / silence reset).  The reference has no counterpart; the
+// arithmetic below is the contract (include/phasegen.h states it) and tests/_vocoder_ref.py restates it in numpy, bit for bit.
+//
+// Phase on a wrap-around grid.  Phase matters modulo 2 pi only, so it is kept as a 32-bit unsigned fraction of a turn:
+//   q(x) = 0 when x is not finite or |x| > 2^20, else (uint32)(int64) rint((double)x * K),  K = 2^32 / TWO_PI
+// Integer addition wraps and is associative, so the scan along time is EXACT in any order: the result cannot depend on the grid, the
+// chunking or the wave size.  For output frame g of a row: p = (double)g * src_per_out, i0 = min((int64)floor(p), F_src - 1),
+// i1 = min(i0 + 1, F_src - 1) (pg_spec_clips's positions), and
+//   delta[g] = q(A[i1]) - q(A[i0])                            (uint32: the wrap IS the principal value of the advance)
+//   reset[g] = g == 0 || (M != NULL && M[i0] < reset_below)
+//   acc[g]   = reset[g] ? q(A[i0]) : acc[g-1] + delta[g-1]    (uint32)
+//   out[g]   = (float)((double)(int32)acc[g] * R),            R = TWO_PI / 2^32
+//
+// Kernel.  One 256-thread workgroup per (channel, bin) row (rows are walked grid-stride), the row in chunks of 1024 output frames, 4
+// consecutive frames per thread.  Element g of the scan is the pair (reset[g], reset[g] ? q(A[i0(g)]) : delta[g-1]) and the operator
+// is the segmented sum (f1, v1) o (f2, v2) = (f1 | f2, f2 ? v2 : v1 + v2): in registers over a thread's 4 elements, across the 64
+// lanes of a wave (6 shuffle steps), across the 4 waves through LDS (two buffers alternate, so one barrier per chunk), and a carry
+// register into the next chunk.  Source reads are gathers at i0 / i1, monotone in g: they coalesce and hit cache.  Stores are 16-byte
+// when `out` and F_out allow and frame by frame otherwise; both paths give the same bits.  All index arithmetic is 64-bit; q() is one
+// double multiply (nothing to contract; the file is built with -ffp-contract=off like the rest).  Measurements: DESIGN.md section 4.11.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include "phasegen.h"
+#include "pg_common.h"
+
+namespace {
+
+constexpr int PV_THREADS = 256;
+constexpr int PV_PER_THREAD = 4;
+constexpr int PV_CHUNK = PV_THREADS * PV_PER_THREAD;      // 1024 output frames
+constexpr int PV_WAVES = PV_THREADS / 64;
+constexpr double PV_TWO_PI = 6.283185307179586;
+constexpr long PV_MAX_BLOCKS = 2048;                        // 256 CUs x 8 workgroups
+
+struct PvKernelArgs {
+    const float* A; const float* M; float* out;
+    double src_per_out;
+    long a_stride, m_stride, F_src, F_out, rows;
+    int bins;
+    float reset_below;
+};
+
+__device__ __forceinline__ uint32_t pv_q(float x) {
+    if (!(fabsf(x) <= 1048576.0f)) return 0u;               // NaN, +-inf and |x| > 2^20
+    const double K = 4294967296.0 / PV_TWO_PI;
+    return (uint32_t)(int64_t)rint((double)x * K);
+}
+
+// i0 of output frame g (>= 0)
+__device__ __forceinline__ long pv_i0(long g, double spo, long F_src) {
+    const double fl = floor((double)g * spo);
+    return fl < (double)F_src ? (long)fl : F_src - 1;        // (also for a position beyond the int64 range)
+}
+
+
+__device__ __forceinline__ float pv_angle(uint32_t acc) {
+    const double R = PV_TWO_PI / 4294967296.0;
+    return (float)((double)(int32_t)acc * R);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(PV_THREADS) void phase_vocoder_kernel(const PvKernelArgs a) {
+    __shared__ uint32_t wave_v[2][PV_WAVES];
+    __shared__ uint32_t wave_f[2][PV_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (long r = blockIdx.x; r < a.rows; r += gridDim.x) {
+        const long c = r / a.bins, b = r - c * a.bins;
+        const float* ar = a.A + c * a.a_stride + b * a.F_src;
+        const float* mr = a.M ? a.M + c * a.m_stride + b * a.F_src : nullptr;
+        float* orow = a.out + r * a.F_out;
+        uint32_t carry = 0u;                                  // acc of the last frame of the previous chunk (frame 0 always resets)
+        int buf = 0;
+        for (long c0 = 0; c0 < a.F_out; c0 += PV_CHUNK, buf ^= 1) {
+            const long g0 = c0 + (long)tid * PV_PER_THREAD;
+            // 1. the thread's 4 elements, scanned in registers; frames past the end are the identity (0, 0).  The five frames
+            // g0 - 1 .. g0 + 3 give the positions and quantised phases of all four elements: element g takes q(A[i0(g)]) when it
+            // resets and delta[g-1] = q(A[i1(g-1)]) - q(A[i0(g-1)]) otherwise, and i1(g-1) is very often i0(g).  (Frames outside
+            // 0 .. F_out - 1 are clamped into the row: what they read is valid and never used.)
+            long i0[PV_PER_THREAD + 1];
+            uint32_t q0[PV_PER_THREAD + 1];
+#pragma unroll
+            for (int j = 0; j <= PV_PER_THREAD; ++j) {
+                long g = g0 - 1 + j;
+                g = g < 0 ? 0 : (g < a.F_out ? g : a.F_out - 1);
+                i0[j] = pv_i0(g, a.src_per_out, a.F_src);
+                q0[j] = pv_q(ar[i0[j]]);
+            }
+            uint32_t v[PV_PER_THREAD];
+            bool f[PV_PER_THREAD];
+            uint32_t tv = 0u;
+            bool tf = false;
+#pragma unroll
+            for (int i = 0; i < PV_PER_THREAD; ++i) {
+                const long g = g0 + i;
+                uint32_t ev = 0u;
+                bool ef = false;
+                if (g < a.F_out) {
+                    ef = g == 0 || (mr != nullptr && mr[i0[i + 1]] < a.reset_below);
+                    if (ef) ev = q0[i + 1];
+                    else {
+                        const long j1 = i0[i] + 1 < a.F_src ? i0[i] + 1 : a.F_src - 1;
+                        ev = (j1 == i0[i + 1] ? q0[i + 1] : pv_q(ar[j1])) - q0[i];
+                    }
+                }
+                tv = ef ? ev : tv + ev;
+                tf = tf || ef;
+                v[i] = tv; f[i] = tf;
+            }
+            // 2. inclusive segmented scan of the threads' totals across the wave
+            uint32_t sv = tv, sf = tf ? 1u : 0u;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t pv = __shfl_up(sv, off, 64), pf = __shfl_up(sf, off, 64);
+                if (lane >= off) { sv = sf ? sv : pv + sv; sf |= pf; }
+            }
+            // the lanes before this one: (0, 0) for lane 0
+            uint32_t xv = __shfl_up(sv, 1, 64), xf = __shfl_up(sf, 1, 64);
+            if (lane == 0) { xv = 0u; xf = 0u; }
+            // 3. the waves' totals through LDS
+            if (lane == 63) { wave_v[buf][wave] = sv; wave_f[buf][wave] = sf; }
+            __syncthreads();
+            uint32_t pre = carry, tot = carry;                // carry o wave 0 o ... o wave (w - 1), and over all waves
+#pragma unroll
+            for (int w = 0; w < PV_WAVES; ++w) {
+                const uint32_t wv = wave_v[buf][w], wf = wave_f[buf][w];
+                tot = wf ? wv : tot + wv;
+                if (w + 1 == wave) pre = tot;
+            }
+            carry = tot;
+            pre = xf ? xv : pre + xv;                         // ... o the lanes before this one
+            // 4. the thread's frames
+            if (g0 < a.F_out) {
+                if (VEC) {                                    // F_out % 4 == 0: the unit is whole and 16-byte aligned
+                    f32x4 o;
+#pragma unroll
+                    for (int i = 0; i < PV_PER_THREAD; ++i) o[i] = pv_angle(f[i] ? v[i] : pre + v[i]);
+                    *(f32x4*)(orow + g0) = o;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < PV_PER_THREAD; ++i)
+                        if (g0 + i < a.F_out) orow[g0 + i] = pv_angle(f[i] ? v[i] : pre + v[i]);
+                }
+            }
+        }
+        // (the next row's first barrier orders its LDS writes after this row's last reads: the buffers alternate and every wave
+        // passes a chunk's barrier before any wave reaches the chunk after the next)
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+extern "C" int pg_phase_vocoder(const pg_phase_vocoder_args* a, void* stream) {
+    if (!a || !a->A || !a->out) return pg_fail(PG_ERR_NULL, "phase_vocoder: args, A and out required");
+    if (a->n_ch <= 0 || a->bins <= 0 || a->F_src <= 0 || a->F_out <= 0) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: non-positive dimension");
+    if (!(a->src_per_out > 0.0) || !(a->src_per_out <= 1.7976931348623157e308)) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: src_per_out must be finite and positive");
+    if (!(a->reset_below >= 0.0f) || !(a->reset_below <= 3.402823466e+38f)) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: reset_below must be finite and not negative");
+    if (a->F_src > INT64_MAX / 2 / a->bins) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: plane beyond 2^62 elements");
+    if (a->a_stride < (int64_t)a->bins * a->F_src) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: a_stride shorter than a plane");
+    if (a->M && a->m_stride < (int64_t)a->bins * a->F_src) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: m_stride shorter than a plane");
+    const int64_t rows = (int64_t)a->n_ch * a->bins;
+    if (rows > INT64_MAX / 2 / a->F_out) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: output beyond 2^62 elements");
+    if ((((uintptr_t)a->A) & 3) || (((uintptr_t)a->M) & 3) || (((uintptr_t)a->out) & 3)) return pg_fail(PG_ERR_ALIGN, "phase_vocoder: misaligned pointer");
+    const bool wide = (a->F_out & 3) == 0 && (((uintptr_t)a->out) & 15) == 0;
+    PvKernelArgs k;
+    k.A = a->A; k.M = a->M; k.out = a->out;
+    k.src_per_out = a->src_per_out;
+    k.a_stride = a->n_ch == 1 ? 0 : a->a_stride; k.m_stride = a->n_ch == 1 ? 0 : a->m_stride;
+    k.F_src = a->F_src; k.F_out = a->F_out; k.rows = rows;
+    k.bins = a->bins; k.reset_below = a->reset_below;
+    long cap = (long)pg_cu_count() * 8; if (cap > PV_MAX_BLOCKS) cap = PV_MAX_BLOCKS; if (cap < 1) cap = 1;
+    const unsigned grid = (unsigned)(rows > cap ? cap : rows);
+    hipStream_t st = (hipStream_t)stream;
+    if (wide) hipLaunchKernelGGL(phase_vocoder_kernel<true>, dim3(grid), dim3(PV_THREADS), 0, st, k);
+    else hipLaunchKernelGGL(phase_vocoder_kernel<false>, dim3(grid), dim3(PV_THREADS), 0, st, k);
+    return pg_launch_ok("phase_vocoder launch failed");
+}

@@ -176,6 +176,13 @@ class PhaseJoinArgs(C.Structure):
                 ("out", C.c_void_p), ("ramp", C.c_void_p)]
 
 
+class PhaseVocoderArgs(C.Structure):
+    """pg_phase_vocoder_args: the phase-vocoder phase of a time-stretched spectrogram (include/phasegen.h)."""
+    _fields_ = [("n_ch", C.c_int32), ("bins", C.c_int32), ("F_src", C.c_int64), ("F_out", C.c_int64),
+                ("src_per_out", C.c_double), ("reset_below", C.c_float), ("_pad0", C.c_int32),
+                ("A", C.c_void_p), ("a_stride", C.c_int64), ("M", C.c_void_p), ("m_stride", C.c_int64), ("out", C.c_void_p)]
+
+
 class WaveCompareArgs(C.Structure):
     """pg_wave_compare_args: six sums per signal of a reference / estimate pair of waveforms (include/phasegen.h)."""
     _fields_ = [("n_signals", C.c_int32), ("_pad0", C.c_int32), ("n", C.c_int64),
@@ -239,6 +246,7 @@ SYMBOLS = {
     "pg_stitch": (C.c_int, [C.POINTER(StitchArgs), C.c_void_p]),
     "pg_spec_clips": (C.c_int, [C.POINTER(SpecClipsArgs), C.c_void_p]),
     "pg_phase_join": (C.c_int, [C.POINTER(PhaseJoinArgs), C.c_void_p]),
+    "pg_phase_vocoder": (C.c_int, [C.POINTER(PhaseVocoderArgs), C.c_void_p]),
     "pg_workspace_bytes_wave_compare": (C.c_int64, [C.POINTER(WaveCompareArgs)]),
     "pg_wave_compare": (C.c_int, [C.POINTER(WaveCompareArgs), C.c_void_p]),
     "pg_workspace_bytes_spec_compare": (C.c_int64, [C.POINTER(SpecCompareArgs)]),

@@ -10,6 +10,9 @@ reduced on the device (pg_wave_compare, pg_spec_compare) -- a yardstick that can
                         which would scale the estimate away and pin the figure near 1 whatever the spectrum looks like
   lsd_db                log-spectral distance: mean over frames of the rms over bins of the difference of the levels
                         10 log10(max(m^2, floor)), with the estimate scaled by g_m; floor = 1e-10 is librosa.power_to_db's amin
+
+``consistency`` needs no reference signal (a time-stretched track has none): it compares the magnitudes that were imposed on an ISTFT
+with the spectrogram of what came out, by the same spectral convergence and log-spectral distance at gain 1.
 """
 import math
 
@@ -38,6 +41,43 @@ def _ratio(num, den):
 
 def _db(v):
     return math.inf if v == math.inf else (-math.inf if v <= 0 else 10.0 * math.log10(v))
+
+
+def consistency(logmag, audio, n_fft, hop_length, floor=1e-10):
+    """Spectrogram consistency, the reference-free measure of the phase-retrieval literature: how far |STFT(ISTFT(imposed
+    magnitudes, some phase))| lands from the imposed magnitudes.  ``logmag`` (n_ch, bins, F) float32 device tensor: the log1p
+    magnitude plane that was imposed (bins = n_fft / 2, the DC row dropped); ``audio`` (n_ch, hop_length * (F - 1)): the ISTFT output
+    BEFORE any trimming.  E = ops.stft(audio), R = [expm1(logmag); 0] in the same layout; both are cut to the frames [e, F - e),
+    e = ceil(n_fft / (2 hop_length)) -- those whose window does not reach the reflect padding -- and compared by ONE
+    ops.spec_compare with gain 1, summed over the channels.
+    -> {"spectral_convergence": sqrt(sum (mR - mE)^2 / sum mR^2), "lsd_db", "n_frames": F - 2 e, "channels"}, formed as
+    ``compare_audio`` forms them.  ValueError: F <= 2 e; "Audio buffer is not finite everywhere" when a cell of either is not finite."""
+    n_fft, hop_length = int(n_fft), int(hop_length)
+    if not (torch.is_tensor(logmag) and logmag.is_cuda and logmag.dtype == torch.float32 and logmag.dim() == 3):
+        raise ValueError("consistency: logmag must be a 3-D float32 device tensor (n_ch, bins, F)")
+    n_ch, bins, F = logmag.shape
+    if n_fft < 2 or hop_length < 1 or bins != n_fft // 2:
+        raise ValueError(f"consistency: logmag has {bins} bins, n_fft {n_fft} (hop {hop_length}) needs {n_fft // 2}")
+    if not (torch.is_tensor(audio) and audio.is_cuda and audio.dtype == torch.float32 and tuple(audio.shape) == (n_ch, hop_length * (F - 1))):
+        raise ValueError(f"consistency: audio must be the untrimmed ISTFT output, a float32 device tensor {(n_ch, hop_length * (F - 1))}")
+    e = -(-n_fft // (2 * hop_length))
+    if F <= 2 * e:
+        raise ValueError(f"consistency: {F} frames leave none whose window stays clear of the padding (need more than {2 * e})")
+    with torch.cuda.device(logmag.device), torch.no_grad():
+        E = ops.stft(audio.contiguous(), n_fft, hop_length)[:, :, :, e:F - e].contiguous()   # (n_ch, 2, bins, F - 2 e)
+        R = torch.zeros_like(E)
+        R[:, 0] = torch.expm1(logmag[:, :, e:F - e])
+        s = ops.spec_compare(R, E, floor=floor).sum(0)
+        smm, serr, lsd_sum, bad = s[[0, 3, 4, 5]].cpu().tolist()
+    if bad != 0:
+        raise ValueError("Audio buffer is not finite everywhere")
+    n_frames = F - 2 * e
+    return {
+        "spectral_convergence": math.sqrt(serr / smm) if smm > 0 else (0.0 if serr == 0 else math.inf),
+        "lsd_db": lsd_sum / (n_ch * n_frames),
+        "n_frames": int(n_frames),
+        "channels": int(n_ch),
+    }
 
 
 def compare_audio(ref, est, n_fft=2048, hop_length=512, floor=1e-10):

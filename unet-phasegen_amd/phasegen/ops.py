@@ -915,6 +915,57 @@ def phase_join(phi, sf, ramp=None, out=None):
     return out
 
 
+def _vocoder_plane(t, name, shape=None):
+    """(n_ch, bins, F_src) float32 on the device, frames contiguous, rows F_src apart, the channel stride free -> that stride."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
+        raise ValueError(f"phase_vocoder: {name} must be a 3-D float32 device tensor (n_ch, bins, F_src)")
+    _on_current_device(t, name)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"phase_vocoder: {name} must be shaped like angle, {tuple(shape)}, got {tuple(t.shape)}")
+    n_ch, bins, F_src = t.shape
+    if min(n_ch, bins, F_src) < 1:
+        raise ValueError(f"phase_vocoder: empty {name} {tuple(t.shape)}")
+    if (F_src > 1 and t.stride(2) != 1) or (bins > 1 and t.stride(1) != F_src):
+        raise ValueError(f"phase_vocoder: frames of {name} must be contiguous and rows F_src apart (strides {t.stride()})")
+    stride = t.stride(0) if n_ch > 1 else bins * F_src
+    if stride < bins * F_src:
+        raise ValueError(f"phase_vocoder: channels of {name} overlap in memory (strides {t.stride()})")
+    return stride
+
+
+def phase_vocoder(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=None):
+    """The phase-vocoder phase of a time-stretched spectrogram (pg_phase_vocoder): angle (n_ch, bins, F_src) float32 on the device,
+    frames contiguous, rows F_src apart, the channel stride free (``pol[:, 1]`` of a (n_ch, 2, bins, F) polar tensor is read in place)
+    -> (n_ch, bins, F_out), dense, in [-pi, pi].  Output frame g sits at source position g * src_per_out (src_per_out = 1 / stretch);
+    every bin's phase advances from frame to frame by the wrapped difference of the two analysis phases around that position, summed
+    exactly on a 2^32 grid of the turn.  ``logmag`` (same shape, ``pol[:, 0]``) and ``reset_below``: a frame whose log-magnitude is
+    below the floor takes the analysis phase itself (the transient / silence reset); without either nothing resets after frame 0.
+    src_per_out == 1.0 returns the analysis phase (to 2 pi / 2^33 and one rounding)."""
+    a_stride = _vocoder_plane(angle, "angle")
+    n_ch, bins, F_src = angle.shape
+    F_out, src_per_out, reset_below = int(F_out), float(src_per_out), float(reset_below)
+    if F_out < 1:
+        raise ValueError(f"phase_vocoder: F_out must be positive, got {F_out}")
+    if not 0.0 < src_per_out < float("inf"):
+        raise ValueError(f"phase_vocoder: src_per_out must be finite and positive, got {src_per_out}")
+    if not 0.0 <= reset_below < float("inf"):
+        raise ValueError(f"phase_vocoder: reset_below must be finite and not negative, got {reset_below}")
+    m_stride = _vocoder_plane(logmag, "logmag", angle.shape) if logmag is not None else 0
+    want = (n_ch, bins, F_out)
+    if out is None:
+        out = torch.empty(want, device=angle.device, dtype=torch.float32)
+    elif tuple(out.shape) != want:
+        raise ValueError(f"phase_vocoder: out must be {want}, got {tuple(out.shape)}")
+    a = _lib.PhaseVocoderArgs()
+    a.n_ch, a.bins, a.F_src, a.F_out, a.src_per_out, a.reset_below = n_ch, bins, F_src, F_out, src_per_out, reset_below
+    a.A, a.a_stride = angle.data_ptr(), a_stride
+    if logmag is not None:
+        a.M, a.m_stride = logmag.data_ptr(), m_stride
+    a.out = _dense(out, "out")
+    _lib.check(_lib.load().pg_phase_vocoder(C.byref(a), _stream()), "phase_vocoder")
+    return out
+
+
 _compare_ws = _StreamCache()
 _caches.append(_compare_ws)
 

@@ -23,6 +23,11 @@ times as long at the same pitch) and ``pitch_shift`` resamples that back (same l
 
 ``evaluate_track`` runs the analysis once, synthesises the track from several phase sources (the model's, none at all, the
 analysis' own, Griffin-Lim's) and reports ``metrics.compare_audio`` of each against the input.
+
+phase="vocoder" (spectral join) is the phase vocoder, the comparator of every time-stretch method: the analysis' own phase carried
+along the output frames by its measured advance (ops.phase_vocoder); it needs no model.  A stretched track has no reference
+waveform, so ``evaluate_stretch`` reports ``metrics.consistency`` instead: how far the spectrogram of each phase source's result
+lands from the magnitudes that were imposed.
 """
 import collections
 import fractions
@@ -189,35 +194,58 @@ def _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, o
     return an
 
 
-def _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize):
-    """One phase source -> the track (channels, a_out) through the spectral join: clip windows of the log-magnitude plane, forward,
-    ONE phase per global frame (ops.phase_join), ONE ISTFT with the plane's own magnitudes; raises when a sample is not finite."""
+# log1p|z| of the standardised spectrogram below which phase="vocoder" resets a bin: of {0, 0.01, 0.05, 0.2} the floor with the
+# smallest consistency on the synthetic melody at stretch 1.5 (tools/vocoder_bench.py; the four figures are in DESIGN.md section 4.11)
+VOCODER_RESET_BELOW = 0.2
+STRETCH_PHASES = ("unet", "vocoder", "zero")
+
+
+def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below=None):
+    """One phase source -> (mag, audio): the log-magnitude plane on the output grid (n_ch, bins, F_out) and the un-normalised,
+    untrimmed ISTFT of it under that phase (n_ch, hop * (F_out - 1)).  Called under the device and no_grad."""
     pl, n_ch, bins = an.plan, an.n_ch, an.bins
     spo = 1.0 / an.stretch
-    with torch.cuda.device(an.a2.device), torch.no_grad():
-        logmag = an.pol[:, 0]                                                                 # (n_ch, bins, F_src), read in place
-        if phase == "zero":
-            ph = torch.zeros(n_ch, bins, pl.F_out, device=logmag.device)                      # (the join of zeros is zero)
-        elif phase == "original":
-            ph = ops.phase_join(ops.spec_clips(an.pol[:, 1], pl.n_clips, frames, pl.sf, spo), pl.sf)
+    logmag = an.pol[:, 0]                                                                     # (n_ch, bins, F_src), read in place
+    if phase == "zero":
+        ph = torch.zeros(n_ch, bins, pl.F_out, device=logmag.device)                          # (the join of zeros is zero)
+    elif phase == "original":
+        ph = ops.phase_join(ops.spec_clips(an.pol[:, 1], pl.n_clips, frames, pl.sf, spo), pl.sf)
+    elif phase == "vocoder":
+        # the analysis' own phase, propagated along the output grid by its measured advance (no model, no clips)
+        ph = ops.phase_vocoder(an.pol[:, 1], pl.F_out, spo, logmag=logmag,
+                               reset_below=VOCODER_RESET_BELOW if reset_below is None else reset_below)
+    else:
+        x = ops.spec_clips(logmag, pl.n_clips, frames, pl.sf, spo).view(pl.n_clips * n_ch, bins, frames)   # (clip, channel) order
+        n_sig = x.shape[0]
+        if n_sig <= clip_batch:       # one forward: the phase half of its (n_sig, 2 bins, frames) output is joined in place
+            phi = model.forward(x, per_clip=True).view(pl.n_clips, n_ch, 2 * bins, frames)[:, :, :bins]
         else:
-            x = ops.spec_clips(logmag, pl.n_clips, frames, pl.sf, spo).view(pl.n_clips * n_ch, bins, frames)   # (clip, channel) order
-            n_sig = x.shape[0]
-            if n_sig <= clip_batch:       # one forward: the phase half of its (n_sig, 2 bins, frames) output is joined in place
-                phi = model.forward(x, per_clip=True).view(pl.n_clips, n_ch, 2 * bins, frames)[:, :, :bins]
-            else:
-                phi = torch.empty(pl.n_clips, n_ch, bins, frames, device=logmag.device)
-                flat = phi.view(n_sig, bins, frames)
-                for i in range(0, n_sig, clip_batch):
-                    flat[i:i + clip_batch] = model.forward(x[i:i + clip_batch], per_clip=True)[:, :bins]
-            ph = ops.phase_join(phi, pl.sf)
-        # the magnitudes on the output grid: the plane itself, cut (or time-resampled) to F_out frames by the same kernel
-        mag = ops.spec_clips(logmag, 1, pl.F_out, pl.F_out, spo)[0]
-        audio = ops.istft(mag, ph, hop_length, mode=0, normalize=False)                       # (n_ch, hop * (F_out - 1))
-        out, _, bad = ops.stitch(audio[:, None, :pl.a_out], pl.a_out, pl.a_out, normalize=normalize, return_status=True)
-        if int(bad.item()) != 0:
-            raise ValueError("Audio buffer is not finite everywhere")
+            phi = torch.empty(pl.n_clips, n_ch, bins, frames, device=logmag.device)
+            flat = phi.view(n_sig, bins, frames)
+            for i in range(0, n_sig, clip_batch):
+                flat[i:i + clip_batch] = model.forward(x[i:i + clip_batch], per_clip=True)[:, :bins]
+        ph = ops.phase_join(phi, pl.sf)
+    # the magnitudes on the output grid: the plane itself, cut (or time-resampled) to F_out frames by the same kernel
+    mag = ops.spec_clips(logmag, 1, pl.F_out, pl.F_out, spo)[0]
+    return mag, ops.istft(mag, ph, hop_length, mode=0, normalize=False)                       # (n_ch, hop * (F_out - 1))
+
+
+def _trim_spectral(an, audio, normalize):
+    """The first a_out samples of the whole-track ISTFT, finite-checked (and peak-normalised): (channels, a_out)."""
+    pl = an.plan
+    out, _, bad = ops.stitch(audio[:, None, :pl.a_out], pl.a_out, pl.a_out, normalize=normalize, return_status=True)
+    if int(bad.item()) != 0:
+        raise ValueError("Audio buffer is not finite everywhere")
     return out
+
+
+def _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize, reset_below=None):
+    """One phase source -> the track (channels, a_out) through the spectral join: clip windows of the log-magnitude plane, forward,
+    ONE phase per global frame (ops.phase_join; phase="vocoder": ops.phase_vocoder on the analysis' phase instead), ONE ISTFT with
+    the plane's own magnitudes; raises when a sample is not finite."""
+    with torch.cuda.device(an.a2.device), torch.no_grad():
+        _mag, audio = _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below)
+        return _trim_spectral(an, audio, normalize)
 
 
 def _check_join(who, join, stretch, phase_list):
@@ -229,8 +257,10 @@ def _check_join(who, join, stretch, phase_list):
     for p in phase_list:
         if join == "spectral" and p == "griffinlim":
             raise ValueError(f"{who}: phase 'griffinlim' is not available under join='spectral'")
-        if stretch != 1.0 and p not in ("unet", "zero"):
-            raise ValueError(f"{who}: stretch {stretch} needs phase 'unet' or 'zero', got {p!r} (the analysis' own phase does not fit a resampled spectrogram)")
+        if join != "spectral" and p == "vocoder":
+            raise ValueError(f"{who}: phase 'vocoder' needs join='spectral' (it propagates the phase on the track's frame grid)")
+        if stretch != 1.0 and p not in STRETCH_PHASES:
+            raise ValueError(f"{who}: stretch {stretch} needs phase 'unet', 'vocoder' or 'zero', got {p!r} (the analysis' own phase does not fit a resampled spectrogram)")
     return stretch
 
 
@@ -267,8 +297,8 @@ def _keyword_options(impl, **options):
 def _reconstruct_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phase, normalize,
                        join, stretch):
     """``reconstruct_track`` with its keyword-only options spelled out."""
-    if phase not in ("unet", "original", "zero"):
-        raise ValueError(f"reconstruct_track: phase must be 'unet', 'original' or 'zero', got {phase!r}")
+    if phase not in ("unet", "original", "zero", "vocoder"):
+        raise ValueError(f"reconstruct_track: phase must be 'unet', 'original', 'zero' or 'vocoder', got {phase!r}")
     if phase == "unet" and model is None:
         raise ValueError("reconstruct_track: phase='unet' needs a model")
     if clip_batch < 1:
@@ -295,8 +325,10 @@ def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, over
     Keyword-only options (``reconstruct_track.options``; the positional parameter list above is the waveform-only call's and stays):
     ``join="waveform"`` inverts every clip and crossfades the waveforms (ops.stitch); ``join="spectral"`` joins the clips' PHASES on
     the track's frame grid (ops.phase_join: one phase per frame, the circular mean where two clips overlap) and inverts the whole
-    track once with its exact magnitudes.  ``stretch=1.0`` (spectral join, phase "unet" or "zero"): the magnitudes are resampled
-    along time and the result has round(a_len * stretch) samples per channel at the same pitch."""
+    track once with its exact magnitudes.  ``stretch=1.0`` (spectral join, phase "unet", "vocoder" or "zero"): the magnitudes are
+    resampled along time and the result has round(a_len * stretch) samples per channel at the same pitch.  phase="vocoder" (spectral
+    join only, ``model`` may be None) is the phase vocoder: the analysis' own phase, propagated along the output frames by its
+    measured advance (ops.phase_vocoder, floor ``VOCODER_RESET_BELOW``) -- the standard comparator of a time stretch."""
 
 
 def _evaluate_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phases, gl_iters,
@@ -347,6 +379,47 @@ def evaluate_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap
     ``reconstruct_track`` ("griffinlim" is not available under "spectral")."""
 
 
+def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
+                     res_type="kaiser_best", clip_batch=64, phases=("unet", "vocoder", "zero"), reset_below=None, floor=1e-10,
+                     return_audio=False):
+    """The quality report of a STRETCHED track, which has no reference waveform to be compared with: ONE spectral analysis (as
+    ``reconstruct_track(join="spectral", stretch=stretch)``), then for every entry of ``phases`` -- "unet" (the model's phase),
+    "vocoder" (ops.phase_vocoder with the floor ``reset_below``; None: ``VOCODER_RESET_BELOW``), "zero" (none) -- one synthesis and
+    ``metrics.consistency`` of its untrimmed ISTFT output against the resampled log-magnitude plane it was made from: how far the
+    spectrogram of the result lands from the magnitudes that were imposed.
+    -> {"n_samples", "n_out", "sr", "stretch", "n_clips", "reset_below", "metrics": {phase: dict}} and, with ``return_audio``,
+    "audio": {phase: un-normalised device tensor of round(a_len * stretch) samples per channel}.  The "unet" and "zero" audio has the
+    bits of ``reconstruct_track(..., normalize=False, join="spectral", stretch=stretch)``.  ``model`` may be None when "unet" is not
+    asked for."""
+    phases = tuple(phases)
+    for p in phases:
+        if p not in STRETCH_PHASES:
+            raise ValueError(f"evaluate_stretch: unknown phase {p!r} (expected some of {STRETCH_PHASES})")
+    if len(set(phases)) != len(phases) or not phases:
+        raise ValueError("evaluate_stretch: phases must be a non-empty list without repetitions")
+    if "unet" in phases and model is None:
+        raise ValueError("evaluate_stretch: phase 'unet' needs a model")
+    if clip_batch < 1:
+        raise ValueError("evaluate_stretch: clip_batch must be positive")
+    reset_below = VOCODER_RESET_BELOW if reset_below is None else float(reset_below)
+    if not 0.0 <= reset_below < math.inf:
+        raise ValueError(f"evaluate_stretch: reset_below must be finite and not negative, got {reset_below}")
+    stretch = _check_join("evaluate_stretch", "spectral", stretch, phases)
+    an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch)
+    res = {"n_samples": int(an.a_len), "n_out": int(an.plan.a_out), "sr": int(sr), "stretch": stretch, "n_clips": int(an.n_clips),
+           "reset_below": reset_below, "metrics": {}}
+    if return_audio:
+        res["audio"] = {}
+    with torch.cuda.device(an.a2.device), torch.no_grad():
+        for p in phases:
+            mag, full = _invert_spectral(an, model, p, hop_length, frames, clip_batch, reset_below)
+            out = _trim_spectral(an, full, False)
+            res["metrics"][p] = metrics.consistency(mag, full, n_fft, hop_length, floor)
+            if return_audio:
+                res["audio"][p] = out[0] if an.mono else out
+    return res
+
+
 def pitch_ratio(semitones, max_denominator=1024):
     """(stretch, Fraction p / q): the stretch 2 ** (semitones / 12) and the rational p / q closest to it with q <= 1024, the most
     phases pg_resample takes (its taps stay below 2048 for every ratio up to 4).  Resampling by q / p shifts the pitch by p / q
@@ -363,7 +436,8 @@ def pitch_shift(model, audio, semitones, n_fft=2048, hop_length=512, frames=128,
     """Pitch shift by ``semitones`` (within two octaves) without a change of tempo: the track is stretched by 2 ** (semitones / 12)
     through the spectral join (``reconstruct_track(join="spectral", stretch=...)``: same pitch, longer or shorter) and played back
     faster or slower by the same ratio (``preproc.resample`` by q / p, see ``pitch_ratio`` for the error in cents), then trimmed or
-    zero-padded to the input's length at ``sr``.  -> float32 device tensor shaped like the input at ``sr``."""
+    zero-padded to the input's length at ``sr``.  ``phase``: "unet", "vocoder" or "zero", as in ``reconstruct_track``.
+    -> float32 device tensor shaped like the input at ``sr``."""
     stretch, ratio = pitch_ratio(semitones)
     a = preproc.resample(audio, osr, sr, res_type=res_type) if osr is not None else audio
     a_len = int(a.shape[-1])

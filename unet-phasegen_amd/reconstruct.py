@@ -16,6 +16,13 @@ same file, byte for byte.
 ``--join spectral`` joins the clips in the spectrogram domain (one phase per frame of the track, one ISTFT with the exact
 magnitudes) instead of crossfading their waveforms.  ``--stretch R`` plays the track R times as long at the same pitch and
 ``--pitch SEMITONES`` shifts its pitch at the same tempo; both imply the spectral join, and neither can be reported against the input.
+
+``--phase vocoder`` takes the phase from the phase vocoder instead of the model (the analysis' own phase, propagated along the output
+frames by its measured advance: the standard comparator of a time stretch) and ``--phase zero`` uses none; neither needs ``--weight``,
+and ``vocoder`` implies the spectral join.  ``--stretch_report PATH`` (with ``--stretch``) measures what a stretched track can be
+measured by, spectrogram consistency (``phasegen.track.evaluate_stretch``): spectral convergence and log-spectral distance between
+the magnitudes that were imposed and the spectrogram of the result, for ``--phase`` and the other phase sources that need no
+weights (and the model's when ``--weight`` is given), written as JSON.
 """
 import argparse
 import json
@@ -28,7 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     parser = argparse.ArgumentParser(description="Reconstruct the phase of a whole track.")
-    parser.add_argument("--weight", required=True, help="a UNetModel.save checkpoint")
+    parser.add_argument("--weight", default=None, help="a UNetModel.save checkpoint (required for --phase unet)")
     parser.add_argument("--input", required=True, help="wav in")
     parser.add_argument("--output", required=True, help="wav out")
     parser.add_argument("--stats", default=None, help="*_audio_stats.npy of the training set (default: this track's own moments)")
@@ -53,7 +60,13 @@ def main():
                         help="play R times as long at the same pitch, 0.25 <= R <= 4 (implies --join spectral)")
     parser.add_argument("--pitch", default=None, type=float, metavar="SEMITONES",
                         help="shift the pitch at the same tempo, within +-24 semitones (implies --join spectral)")
+    parser.add_argument("--phase", choices=["unet", "vocoder", "zero"], default="unet",
+                        help="where the phase comes from: the model (default), the phase vocoder (implies --join spectral), or none")
+    parser.add_argument("--stretch_report", default=None, metavar="PATH",
+                        help="with --stretch: write a JSON report of the spectrogram consistency of every phase source")
     args = parser.parse_args()
+    if args.phase == "unet" and args.weight is None:
+        parser.error("the following arguments are required: --weight")
     if args.stretch is not None and args.pitch is not None:
         parser.error("--stretch and --pitch exclude each other")
     modified = (args.stretch is not None and args.stretch != 1.0) or args.pitch is not None
@@ -61,7 +74,19 @@ def main():
         parser.error("--stretch and --pitch need --join spectral")
     if modified and args.report is not None:
         parser.error("--report compares against the input: it works with --join, not with --stretch or --pitch")
-    join = "spectral" if (modified or args.stretch is not None) and args.join is None else (args.join or "waveform")
+    if args.phase == "vocoder" and args.join == "waveform":
+        parser.error("--phase vocoder needs --join spectral")
+    if args.phase != "unet" and args.report is not None:
+        parser.error("--report measures the model's phase: it needs --phase unet")
+    if args.stretch_report is not None and args.stretch is None:
+        parser.error("--stretch_report needs --stretch")
+    if args.stretch_report is not None and args.pitch is not None:
+        parser.error("--stretch_report measures the stretched track on the analysed frame grid: it does not work with --pitch")
+    if args.stretch_report is not None and args.report is not None:
+        parser.error("--report and --stretch_report exclude each other")
+    join = "spectral" if (modified or args.stretch is not None or args.phase == "vocoder") and args.join is None else (args.join or "waveform")
+    if args.stretch_report is not None and join != "spectral":
+        parser.error("--stretch_report needs --join spectral")
     n_fft = 2 * args.channels if args.n_fft is None else args.n_fft
     hop = n_fft // 4 if args.hop is None else args.hop
     if n_fft != 2 * args.channels:
@@ -74,8 +99,10 @@ def main():
     from phasegen import preproc, track
 
     torch.cuda.set_device(args.gpu)
-    model = UNetModel(args.channels, args.channels * 2, gpu_ids=[args.gpu], precision=args.precision).cuda(args.gpu)
-    model.load(args.weight)
+    model = None
+    if args.weight is not None:
+        model = UNetModel(args.channels, args.channels * 2, gpu_ids=[args.gpu], precision=args.precision).cuda(args.gpu)
+        model.load(args.weight)
     stats = None
     if args.stats is not None:
         mean, std = (float(v) for v in np.load(args.stats))
@@ -95,10 +122,15 @@ def main():
     start = time.time()
     kw = dict(n_fft=n_fft, hop_length=hop, frames=args.frames, overlap_frames=args.overlap_frames, stats=stats, osr=file_sr, sr=args.sr)
     report = None
+    stretch_report = None
     if args.pitch is not None:
-        out = track.pitch_shift(model, audio, args.pitch, **kw)
+        out = track.pitch_shift(model, audio, args.pitch, phase=args.phase, **kw)
+    elif args.stretch_report is not None:
+        others = [p for p in track.STRETCH_PHASES if p != args.phase and (p != "unet" or model is not None)]
+        stretch_report = track.evaluate_stretch(model, audio, args.stretch, phases=[args.phase] + others, return_audio=True, **kw)
+        out = track.peak_normalize(stretch_report.pop("audio")[args.phase])
     elif args.report is None:
-        out = track.reconstruct_track(model, audio, join=join, stretch=1.0 if args.stretch is None else args.stretch, **kw)
+        out = track.reconstruct_track(model, audio, phase=args.phase, join=join, stretch=1.0 if args.stretch is None else args.stretch, **kw)
     else:
         report = track.evaluate_track(model, audio, phases=phases, gl_iters=args.gl_iters, return_audio=True, join=join, **kw)
         out = track.peak_normalize(report.pop("audio")["unet"])
@@ -114,6 +146,12 @@ def main():
             json.dump(report, f, indent=1)
         print("Report: " + "; ".join("{} SI-SDR {:.2f} dB, spectral convergence {:.4f}, LSD {:.2f} dB".format(
             p, m["si_sdr_db"], m["spectral_convergence"], m["lsd_db"]) for p, m in ((p, report["metrics"].get(p)) for p in ("unet", "zero")) if m))
+    if stretch_report is not None:
+        stretch_report.update(input=os.path.abspath(args.input), seconds=n / args.sr, flags=vars(args))
+        with open(args.stretch_report, "w") as f:
+            json.dump(stretch_report, f, indent=1)
+        print("Stretch report (consistency): " + "; ".join("{} spectral convergence {:.4f}, LSD {:.2f} dB".format(
+            p, m["spectral_convergence"], m["lsd_db"]) for p, m in stretch_report["metrics"].items()))
 
 
 if __name__ == "__main__":
