@@ -479,6 +479,49 @@ typedef struct pg_phase_vocoder_args {
 } pg_phase_vocoder_args;                         /* 80 bytes */
 int pg_phase_vocoder(const pg_phase_vocoder_args* a, void* stream);
 
+/* pg_phase_lock: the phase-vocoder phase with IDENTITY PHASE LOCKING (Laroche & Dolson 1999; phasegen/track.py,
+ * phase="vocoder_locked").  A plain vocoder moves every bin on its own and the bins of one sinusoid's main lobe drift apart; here only
+ * the spectral peaks of a frame advance, and every other bin takes its peak's rotation, so the analysis' phase relations inside a
+ * lobe survive.  Struct of its own, PG_VERSION unchanged; the reference has no counterpart; the arithmetic below is the contract.
+ *   A, M, src_per_out, reset_below, F_src, F_out, out, q(), K, R, i0(g), i1(g): those of pg_phase_vocoder, but M is REQUIRED.
+ *   Per channel, with m_g[b] = M[b][i0(g)] and a_g[b] = q(A[b][i0(g)]):
+ *   Peaks of frame g.  Bin b is a peak iff m_g[b] is not NaN and, for d = 1 .. PG_LOCK_REACH (= 2):
+ *     (b - d < 0 or m_g[b] > m_g[b-d]) and (b + d >= bins or m_g[b] >= m_g[b+d])         plain IEEE fp32 comparisons
+ *   so the first bin of a plateau is the peak and a NaN neighbour within reach disqualifies a bin.
+ *   Region.  P_g(b) = the peak nearest to b in |b - p|, a tie going to the lower peak; in a frame without any peak P_g(b) = b.
+ *   Rotation T (uint32, wrapping).  T_0[b] = 0.  For g >= 1, with p = P_g(b):
+ *     e_g[p]  = q(A[p][i1(g-1)]) - q(A[p][i0(g)])                    (zero whenever i1(g-1) == i0(g))
+ *     reset   = m_g[p] < reset_below                                 (a NaN does not reset)
+ *     T_g[b]  = reset ? 0 : T_{g-1}[p] + e_g[p]
+ *     out[b][g] = (float)((double)(int32)(T_g[b] + a_g[b]) * R)      (also for g = 0)
+ *   T is constant over a peak's region: that is identity locking.
+ *   Consequences.  Where every bin is its own region -- bins == 1, or an M that is NaN everywhere -- the result equals
+ *   pg_phase_vocoder's with that same M, bit for bit.  src_per_out == 1.0 returns q(A) exactly for g < F_src.  A channel's result
+ *   does not depend on n_ch or on the channel's position, nor on how the scan is split: frame g is the gather map T_g[b] =
+ *   T_{g-1}[P_g(b)] + c_g[b], c_g[b] = e_g[P_g(b)], a reset being the source index `bins` with T[bins] == 0; maps compose as
+ *   (P2, c2) o (P1, c1) = (P1[P2], c1[P2] + c2), associatively and in integers.
+ *   Kernels: time in chunks of 32 output frames; compose (one workgroup per channel and chunk folds the chunk's maps in LDS), carry
+ *   (one workgroup per channel walks the chunk maps), apply (one workgroup per channel and chunk replays its frames; the peak maps
+ *   are recomputed, not stored); both stage a window of source frames of all rows through LDS, read along the frames (at 4096
+ *   bins, where no window fits beside the maps, every thread walks its own rows).  16-byte stores where out and F_out allow, frame by frame otherwise (same bits); 64-bit index
+ *   arithmetic; no atomics.  workspace: pg_workspace_bytes_phase_lock() bytes = 12 n_ch bins ceil(F_out / 32), a function of n_ch,
+ *   bins and F_out alone.  The library allocates nothing and keeps nothing.
+ *   Errors (host side, before any launch): those of pg_phase_vocoder, and M NULL PG_ERR_NULL; bins > 4096 PG_ERR_SHAPE; workspace
+ *   NULL or smaller than the query's answer PG_ERR_WORKSPACE. */
+#define PG_LOCK_REACH 2
+typedef struct pg_phase_lock_args {
+    int32_t n_ch, bins;                          /* bins <= 4096                                                        */
+    int64_t F_src, F_out;                        /* frames per row of A and M, frames per row of out                    */
+    double  src_per_out;                         /* source frames per output frame = 1 / stretch; finite, > 0          */
+    float   reset_below; int32_t _pad0;          /* a peak whose M is below this resets its region; finite, >= 0        */
+    const float* A; int64_t a_stride;            /* (n_ch, bins, F_src), channels a_stride >= bins F_src elements apart */
+    const float* M; int64_t m_stride;            /* required, same shape, own stride                                    */
+    float* out;                                  /* (n_ch, bins, F_out), dense                                          */
+    void* workspace; int64_t workspace_bytes;
+} pg_phase_lock_args;                            /* 96 bytes */
+int64_t pg_workspace_bytes_phase_lock(const pg_phase_lock_args* a);   /* host function of n_ch, bins, F_out; negative = error code */
+int     pg_phase_lock(const pg_phase_lock_args* a, void* stream);
+
 /* How far a reconstruction is from its source, reduced on the device: the sums from which SI-SDR / SNR (waveforms) and spectral
  * convergence / log-spectral distance (spectrograms) are formed on the host (phasegen/metrics.py).  The reference has no counterpart
  * (validate.py takes mean absolute waveform errors of three dataset clips on the host); the arithmetic below is the contract.

@@ -183,6 +183,11 @@ class PhaseVocoderArgs(C.Structure):
                 ("A", C.c_void_p), ("a_stride", C.c_int64), ("M", C.c_void_p), ("m_stride", C.c_int64), ("out", C.c_void_p)]
 
 
+class PhaseLockArgs(C.Structure):
+    """pg_phase_lock_args: the phase-vocoder phase with identity phase locking (include/phasegen.h)."""
+    _fields_ = PhaseVocoderArgs._fields_ + [("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class WaveCompareArgs(C.Structure):
     """pg_wave_compare_args: six sums per signal of a reference / estimate pair of waveforms (include/phasegen.h)."""
     _fields_ = [("n_signals", C.c_int32), ("_pad0", C.c_int32), ("n", C.c_int64),
@@ -247,6 +252,8 @@ SYMBOLS = {
     "pg_spec_clips": (C.c_int, [C.POINTER(SpecClipsArgs), C.c_void_p]),
     "pg_phase_join": (C.c_int, [C.POINTER(PhaseJoinArgs), C.c_void_p]),
     "pg_phase_vocoder": (C.c_int, [C.POINTER(PhaseVocoderArgs), C.c_void_p]),
+    "pg_workspace_bytes_phase_lock": (C.c_int64, [C.POINTER(PhaseLockArgs)]),
+    "pg_phase_lock": (C.c_int, [C.POINTER(PhaseLockArgs), C.c_void_p]),
     "pg_workspace_bytes_wave_compare": (C.c_int64, [C.POINTER(WaveCompareArgs)]),
     "pg_wave_compare": (C.c_int, [C.POINTER(WaveCompareArgs), C.c_void_p]),
     "pg_workspace_bytes_spec_compare": (C.c_int64, [C.POINTER(SpecCompareArgs)]),

@@ -915,21 +915,22 @@ def phase_join(phi, sf, ramp=None, out=None):
     return out
 
 
-def _vocoder_plane(t, name, shape=None):
-    """(n_ch, bins, F_src) float32 on the device, frames contiguous, rows F_src apart, the channel stride free -> that stride."""
+def _vocoder_plane(t, name, shape=None, who="phase_vocoder"):
+    """(n_ch, bins, F_src) float32 on the device, frames contiguous, rows F_src apart, the channel stride free -> that stride.
+    ``who``: the caller the messages name."""
     if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
-        raise ValueError(f"phase_vocoder: {name} must be a 3-D float32 device tensor (n_ch, bins, F_src)")
+        raise ValueError(f"{who}: {name} must be a 3-D float32 device tensor (n_ch, bins, F_src)")
     _on_current_device(t, name)
     if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"phase_vocoder: {name} must be shaped like angle, {tuple(shape)}, got {tuple(t.shape)}")
+        raise ValueError(f"{who}: {name} must be shaped like angle, {tuple(shape)}, got {tuple(t.shape)}")
     n_ch, bins, F_src = t.shape
     if min(n_ch, bins, F_src) < 1:
-        raise ValueError(f"phase_vocoder: empty {name} {tuple(t.shape)}")
+        raise ValueError(f"{who}: empty {name} {tuple(t.shape)}")
     if (F_src > 1 and t.stride(2) != 1) or (bins > 1 and t.stride(1) != F_src):
-        raise ValueError(f"phase_vocoder: frames of {name} must be contiguous and rows F_src apart (strides {t.stride()})")
+        raise ValueError(f"{who}: frames of {name} must be contiguous and rows F_src apart (strides {t.stride()})")
     stride = t.stride(0) if n_ch > 1 else bins * F_src
     if stride < bins * F_src:
-        raise ValueError(f"phase_vocoder: channels of {name} overlap in memory (strides {t.stride()})")
+        raise ValueError(f"{who}: channels of {name} overlap in memory (strides {t.stride()})")
     return stride
 
 
@@ -963,6 +964,45 @@ def phase_vocoder(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, o
         a.M, a.m_stride = logmag.data_ptr(), m_stride
     a.out = _dense(out, "out")
     _lib.check(_lib.load().pg_phase_vocoder(C.byref(a), _stream()), "phase_vocoder")
+    return out
+
+
+PHASE_LOCK_CHUNK = 32          # output frames per chunk of pg_phase_lock's scan (csrc/lock.hip: LK_CHUNK)
+_lock_ws = _StreamCache()
+_caches.append(_lock_ws)
+
+
+def phase_lock(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=None):
+    """The phase-vocoder phase with identity phase locking (pg_phase_lock): ``angle`` and ``logmag`` (required) as in
+    ``phase_vocoder``, (n_ch, bins <= 4096, F_src) float32 on the device, read in place from a polar tensor -> (n_ch, bins, F_out),
+    dense, in [-pi, pi].  In every output frame the peaks of the log-magnitude (larger than the two bins below, not smaller than the
+    two above) advance by their own measured phase advance and every other bin takes the rotation of its nearest peak, so the
+    analysis' phase relations inside a sinusoid's lobe survive; a peak below ``reset_below`` resets its whole region to the analysis
+    phase.  Exact on a 2^32 grid of the turn, like ``phase_vocoder``; src_per_out == 1.0 returns the analysis phase."""
+    if logmag is None:
+        raise ValueError("phase_lock: logmag is required (the peaks are those of the log-magnitude)")
+    a_stride = _vocoder_plane(angle, "angle", who="phase_lock")
+    n_ch, bins, F_src = angle.shape
+    F_out, src_per_out, reset_below = int(F_out), float(src_per_out), float(reset_below)
+    if F_out < 1:
+        raise ValueError(f"phase_lock: F_out must be positive, got {F_out}")
+    if not 0.0 < src_per_out < float("inf"):
+        raise ValueError(f"phase_lock: src_per_out must be finite and positive, got {src_per_out}")
+    if not 0.0 <= reset_below < float("inf"):
+        raise ValueError(f"phase_lock: reset_below must be finite and not negative, got {reset_below}")
+    m_stride = _vocoder_plane(logmag, "logmag", angle.shape, who="phase_lock")
+    want = (n_ch, bins, F_out)
+    if out is None:
+        out = torch.empty(want, device=angle.device, dtype=torch.float32)
+    elif tuple(out.shape) != want:
+        raise ValueError(f"phase_lock: out must be {want}, got {tuple(out.shape)}")
+    a = _lib.PhaseLockArgs()
+    a.n_ch, a.bins, a.F_src, a.F_out, a.src_per_out, a.reset_below = n_ch, bins, F_src, F_out, src_per_out, reset_below
+    a.A, a.a_stride, a.M, a.m_stride = angle.data_ptr(), a_stride, logmag.data_ptr(), m_stride
+    a.out = _dense(out, "out")
+    lib = _lib.load()
+    a.workspace, a.workspace_bytes = _workspace(_lock_ws, angle.device, lib.pg_workspace_bytes_phase_lock(C.byref(a)), "workspace_bytes_phase_lock")
+    _lib.check(lib.pg_phase_lock(C.byref(a), _stream()), "phase_lock")
     return out
 
 

@@ -25,8 +25,9 @@ times as long at the same pitch) and ``pitch_shift`` resamples that back (same l
 analysis' own, Griffin-Lim's) and reports ``metrics.compare_audio`` of each against the input.
 
 phase="vocoder" (spectral join) is the phase vocoder, the comparator of every time-stretch method: the analysis' own phase carried
-along the output frames by its measured advance (ops.phase_vocoder); it needs no model.  A stretched track has no reference
-waveform, so ``evaluate_stretch`` reports ``metrics.consistency`` instead: how far the spectrogram of each phase source's result
+along the output frames by its measured advance (ops.phase_vocoder); it needs no model.  phase="vocoder_locked" is that vocoder with
+identity phase locking (ops.phase_lock: only the peaks of a frame advance, every other bin follows its peak).  A stretched track has
+no reference waveform, so ``evaluate_stretch`` reports ``metrics.consistency`` instead: how far the spectrogram of each phase source's result
 lands from the magnitudes that were imposed.
 """
 import collections
@@ -197,7 +198,8 @@ def _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, o
 # log1p|z| of the standardised spectrogram below which phase="vocoder" resets a bin: of {0, 0.01, 0.05, 0.2} the floor with the
 # smallest consistency on the synthetic melody at stretch 1.5 (tools/vocoder_bench.py; the four figures are in DESIGN.md section 4.11)
 VOCODER_RESET_BELOW = 0.2
-STRETCH_PHASES = ("unet", "vocoder", "zero")
+STRETCH_PHASES = ("unet", "vocoder", "zero", "vocoder_locked")
+VOCODER_PHASES = ("vocoder", "vocoder_locked")                    # the analysis' own phase, propagated: no model, spectral join only
 
 
 def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below=None):
@@ -214,6 +216,10 @@ def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_bel
         # the analysis' own phase, propagated along the output grid by its measured advance (no model, no clips)
         ph = ops.phase_vocoder(an.pol[:, 1], pl.F_out, spo, logmag=logmag,
                                reset_below=VOCODER_RESET_BELOW if reset_below is None else reset_below)
+    elif phase == "vocoder_locked":
+        # ... with identity phase locking: only the peaks of a frame advance, every other bin takes its peak's rotation
+        ph = ops.phase_lock(an.pol[:, 1], pl.F_out, spo, logmag=logmag,
+                            reset_below=VOCODER_RESET_BELOW if reset_below is None else reset_below)
     else:
         x = ops.spec_clips(logmag, pl.n_clips, frames, pl.sf, spo).view(pl.n_clips * n_ch, bins, frames)   # (clip, channel) order
         n_sig = x.shape[0]
@@ -257,10 +263,10 @@ def _check_join(who, join, stretch, phase_list):
     for p in phase_list:
         if join == "spectral" and p == "griffinlim":
             raise ValueError(f"{who}: phase 'griffinlim' is not available under join='spectral'")
-        if join != "spectral" and p == "vocoder":
-            raise ValueError(f"{who}: phase 'vocoder' needs join='spectral' (it propagates the phase on the track's frame grid)")
+        if join != "spectral" and p in VOCODER_PHASES:
+            raise ValueError(f"{who}: phase {p!r} needs join='spectral' (it propagates the phase on the track's frame grid)")
         if stretch != 1.0 and p not in STRETCH_PHASES:
-            raise ValueError(f"{who}: stretch {stretch} needs phase 'unet', 'vocoder' or 'zero', got {p!r} (the analysis' own phase does not fit a resampled spectrogram)")
+            raise ValueError(f"{who}: stretch {stretch} needs phase 'unet', 'vocoder', 'vocoder_locked' or 'zero', got {p!r} (the analysis' own phase does not fit a resampled spectrogram)")
     return stretch
 
 
@@ -297,8 +303,8 @@ def _keyword_options(impl, **options):
 def _reconstruct_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phase, normalize,
                        join, stretch):
     """``reconstruct_track`` with its keyword-only options spelled out."""
-    if phase not in ("unet", "original", "zero", "vocoder"):
-        raise ValueError(f"reconstruct_track: phase must be 'unet', 'original', 'zero' or 'vocoder', got {phase!r}")
+    if phase not in ("unet", "original", "zero") + VOCODER_PHASES:
+        raise ValueError(f"reconstruct_track: phase must be 'unet', 'original', 'zero', 'vocoder' or 'vocoder_locked', got {phase!r}")
     if phase == "unet" and model is None:
         raise ValueError("reconstruct_track: phase='unet' needs a model")
     if clip_batch < 1:
@@ -328,7 +334,9 @@ def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, over
     track once with its exact magnitudes.  ``stretch=1.0`` (spectral join, phase "unet", "vocoder" or "zero"): the magnitudes are
     resampled along time and the result has round(a_len * stretch) samples per channel at the same pitch.  phase="vocoder" (spectral
     join only, ``model`` may be None) is the phase vocoder: the analysis' own phase, propagated along the output frames by its
-    measured advance (ops.phase_vocoder, floor ``VOCODER_RESET_BELOW``) -- the standard comparator of a time stretch."""
+    measured advance (ops.phase_vocoder, floor ``VOCODER_RESET_BELOW``) -- the standard comparator of a time stretch.
+    phase="vocoder_locked" (the same conditions) is that vocoder with identity phase locking (ops.phase_lock): only the spectral peaks
+    of a frame advance and every other bin keeps its analysis phase relation to its peak -- the stretch to use without weights."""
 
 
 def _evaluate_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phases, gl_iters,
@@ -384,7 +392,8 @@ def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=1
                      return_audio=False):
     """The quality report of a STRETCHED track, which has no reference waveform to be compared with: ONE spectral analysis (as
     ``reconstruct_track(join="spectral", stretch=stretch)``), then for every entry of ``phases`` -- "unet" (the model's phase),
-    "vocoder" (ops.phase_vocoder with the floor ``reset_below``; None: ``VOCODER_RESET_BELOW``), "zero" (none) -- one synthesis and
+    "vocoder" (ops.phase_vocoder with the floor ``reset_below``; None: ``VOCODER_RESET_BELOW``), "zero" (none), "vocoder_locked"
+    (ops.phase_lock with the same floor) -- one synthesis and
     ``metrics.consistency`` of its untrimmed ISTFT output against the resampled log-magnitude plane it was made from: how far the
     spectrogram of the result lands from the magnitudes that were imposed.
     -> {"n_samples", "n_out", "sr", "stretch", "n_clips", "reset_below", "metrics": {phase: dict}} and, with ``return_audio``,
@@ -436,7 +445,8 @@ def pitch_shift(model, audio, semitones, n_fft=2048, hop_length=512, frames=128,
     """Pitch shift by ``semitones`` (within two octaves) without a change of tempo: the track is stretched by 2 ** (semitones / 12)
     through the spectral join (``reconstruct_track(join="spectral", stretch=...)``: same pitch, longer or shorter) and played back
     faster or slower by the same ratio (``preproc.resample`` by q / p, see ``pitch_ratio`` for the error in cents), then trimmed or
-    zero-padded to the input's length at ``sr``.  ``phase``: "unet", "vocoder" or "zero", as in ``reconstruct_track``.
+    zero-padded to the input's length at ``sr``.  ``phase``: "unet", "vocoder", "vocoder_locked" or "zero", as in
+    ``reconstruct_track``.
     -> float32 device tensor shaped like the input at ``sr``."""
     stretch, ratio = pitch_ratio(semitones)
     a = preproc.resample(audio, osr, sr, res_type=res_type) if osr is not None else audio

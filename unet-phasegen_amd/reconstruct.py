@@ -19,7 +19,9 @@ magnitudes) instead of crossfading their waveforms.  ``--stretch R`` plays the t
 
 ``--phase vocoder`` takes the phase from the phase vocoder instead of the model (the analysis' own phase, propagated along the output
 frames by its measured advance: the standard comparator of a time stretch) and ``--phase zero`` uses none; neither needs ``--weight``,
-and ``vocoder`` implies the spectral join.  ``--stretch_report PATH`` (with ``--stretch``) measures what a stretched track can be
+and ``vocoder`` implies the spectral join.  ``--phase vocoder_locked`` is that vocoder with identity phase locking (only the spectral
+peaks advance, every other bin follows its peak): the time stretch to use without weights; it implies the spectral join too.
+``--stretch_report PATH`` (with ``--stretch``) measures what a stretched track can be
 measured by, spectrogram consistency (``phasegen.track.evaluate_stretch``): spectral convergence and log-spectral distance between
 the magnitudes that were imposed and the spectrogram of the result, for ``--phase`` and the other phase sources that need no
 weights (and the model's when ``--weight`` is given), written as JSON.
@@ -60,8 +62,9 @@ def main():
                         help="play R times as long at the same pitch, 0.25 <= R <= 4 (implies --join spectral)")
     parser.add_argument("--pitch", default=None, type=float, metavar="SEMITONES",
                         help="shift the pitch at the same tempo, within +-24 semitones (implies --join spectral)")
-    parser.add_argument("--phase", choices=["unet", "vocoder", "zero"], default="unet",
-                        help="where the phase comes from: the model (default), the phase vocoder (implies --join spectral), or none")
+    parser.add_argument("--phase", choices=["unet", "vocoder", "vocoder_locked", "zero"], default="unet",
+                        help="where the phase comes from: the model (default), the phase vocoder, plain or with identity phase locking "
+                             "(both imply --join spectral), or none")
     parser.add_argument("--stretch_report", default=None, metavar="PATH",
                         help="with --stretch: write a JSON report of the spectrogram consistency of every phase source")
     args = parser.parse_args()
@@ -74,8 +77,8 @@ def main():
         parser.error("--stretch and --pitch need --join spectral")
     if modified and args.report is not None:
         parser.error("--report compares against the input: it works with --join, not with --stretch or --pitch")
-    if args.phase == "vocoder" and args.join == "waveform":
-        parser.error("--phase vocoder needs --join spectral")
+    if args.phase in ("vocoder", "vocoder_locked") and args.join == "waveform":
+        parser.error("--phase {} needs --join spectral".format(args.phase))
     if args.phase != "unet" and args.report is not None:
         parser.error("--report measures the model's phase: it needs --phase unet")
     if args.stretch_report is not None and args.stretch is None:
@@ -84,7 +87,7 @@ def main():
         parser.error("--stretch_report measures the stretched track on the analysed frame grid: it does not work with --pitch")
     if args.stretch_report is not None and args.report is not None:
         parser.error("--report and --stretch_report exclude each other")
-    join = "spectral" if (modified or args.stretch is not None or args.phase == "vocoder") and args.join is None else (args.join or "waveform")
+    join = "spectral" if (modified or args.stretch is not None or args.phase in ("vocoder", "vocoder_locked")) and args.join is None else (args.join or "waveform")
     if args.stretch_report is not None and join != "spectral":
         parser.error("--stretch_report needs --join spectral")
     n_fft = 2 * args.channels if args.n_fft is None else args.n_fft
@@ -126,7 +129,8 @@ def main():
     if args.pitch is not None:
         out = track.pitch_shift(model, audio, args.pitch, phase=args.phase, **kw)
     elif args.stretch_report is not None:
-        others = [p for p in track.STRETCH_PHASES if p != args.phase and (p != "unet" or model is not None)]
+        # (the locked vocoder is reported when it is asked for; the other modes' reports stay as they were)
+        others = [p for p in track.STRETCH_PHASES if p not in (args.phase, "vocoder_locked") and (p != "unet" or model is not None)]
         stretch_report = track.evaluate_stretch(model, audio, args.stretch, phases=[args.phase] + others, return_audio=True, **kw)
         out = track.peak_normalize(stretch_report.pop("audio")[args.phase])
     elif args.report is None:
