@@ -292,7 +292,7 @@ typedef struct pg_istft_args {
     float* audio;
     void* workspace; int64_t workspace_bytes;
 } pg_istft_args;
-int64_t pg_workspace_bytes_istft(const pg_istft_args* a);
+int64_t pg_workspace_bytes_istft(const pg_istft_args* a);   /* host function of n_signals, bins, n_frames, hop (pointers are not read); negative = error code */
 int pg_istft(const pg_istft_args* a, void* stream);
 int pg_istft_describe(const pg_istft_args* a, char* buf, int32_t buflen);   /* launch plan without launching, as pg_stft_describe */
 

@@ -1354,11 +1354,17 @@ IstftPlan plan_istft(const pg_istft_args& a) {
     return pl;
 }
 
-int plan_istft(const pg_istft_args* a, IstftPlan& pl) {
-    if (!a || !a->a || !a->b || !a->audio || !a->workspace) return pg_fail(PG_ERR_NULL, "istft: a, b, audio, workspace required");
+// the shape checks of a call, shared with the workspace query (which needs no pointers)
+int check_istft_shape(const pg_istft_args* a) {
     const int N = 2 * a->bins;
     if (!pow2(N) || N < 32 || N > 4096) return pg_fail(PG_ERR_UNSUPPORTED, "istft: 2*bins must be a power of two in [32, 4096]");
     if (a->n_signals <= 0 || a->n_signals > 64 || a->n_frames < 2 || a->hop <= 0 || a->hop > N) return pg_fail(PG_ERR_SHAPE, "istft: bad sizes (1..64 signals per call)");
+    return PG_OK;
+}
+
+int plan_istft(const pg_istft_args* a, IstftPlan& pl) {
+    if (!a || !a->a || !a->b || !a->audio || !a->workspace) return pg_fail(PG_ERR_NULL, "istft: a, b, audio, workspace required");
+    if (int e = check_istft_shape(a)) return e;
     pl = plan_istft(*a);
     if (a->workspace_bytes < pl.data_off + pl.data_bytes) return pg_fail(PG_ERR_WORKSPACE, "istft: workspace too small");
     return PG_OK;
@@ -1456,7 +1462,8 @@ extern "C" int pg_stft_frame_index(int32_t n_samples, int32_t n_fft, int32_t hop
 }
 
 extern "C" int64_t pg_workspace_bytes_istft(const pg_istft_args* a) {
-    if (!a) return 0;
+    if (!a) return pg_fail(PG_ERR_NULL, "workspace_bytes_istft: args required");
+    if (int e = check_istft_shape(a)) return e;
     const IstftPlan pl = plan_istft(*a);
     return pl.data_off + pl.data_bytes;
 }
