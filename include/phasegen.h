@@ -94,10 +94,15 @@ enum { PG_PREC_FP32 = 0, PG_PREC_BF16 = 1, PG_PREC_BF16X3 = 2 };
  * bits 15-16: their tile order (1: row-major, 2 / 3: super-rows of 2 / 4 tile rows; 0: automatic) -- measurements only.
  * PG_SCHED_NO_COLSPLIT (bit 17): the conv_raw3 launches keep a short column tail (<= 128 columns past the last full 256-wide tile)
  * instead of handing it to a second launch of the tall-tile kernel (pg_conv_describe shows the second launch as |tail=...);
- * PG_SCHED_COLSPLIT (bit 18): the tail launch wherever the geometry allows, whatever the cost model says (tests). */
+ * PG_SCHED_COLSPLIT (bit 18): the tail launch wherever the geometry allows, whatever the cost model says (tests).
+ * PG_SCHED_SLOTS(n) (bits 19-23, n = 1..31; 0 = the device's own count; additive, PG_VERSION unchanged): plan this call as if the device had n compute
+ * units.  Host side only: the grid, the whole / split classes of workgroups and the pricing of the column tail follow n, the kernels
+ * are the ones every call runs.  Tests use it to put a small problem through the work splits a full-size layer takes on 256 CUs
+ * (several whole tiles per workgroup, ranges that hold whole tiles between two partial ones, the hybrid split). */
 enum { PG_SCHED_AUTO = 0, PG_SCHED_TILE_PER_WG = 1, PG_SCHED_FORCE_STREAMK = 2, PG_SCHED_NO_RAW = 4, PG_SCHED_NO_TALL = 8,
        PG_SCHED_CONTENDED = 16, PG_SCHED_NO_PS = 128, PG_SCHED_NO_RAW3 = 0x2000, PG_SCHED_ALL_RAW3 = 0x4000, PG_SCHED_NO_COLSPLIT = 0x20000, PG_SCHED_COLSPLIT = 0x40000 };
 #define PG_SCHED_OVERSUB(f) (((f) & 15) << 8)
+#define PG_SCHED_SLOTS(n) (((n) & 31) << 19)
 
 /* nn.Conv1d forward / backward (model.py:77-78; autograd of train.py:61) */
 int pg_conv1d_fwd(const pg_conv_args* a, void* stream);
@@ -129,7 +134,7 @@ int pg_conv_describe(const pg_conv_args* a, int32_t op, char* buf, int32_t bufle
 typedef struct pg_convh_args {
     int32_t B, Cin, Cout, Lin, Lout, k, stride, pad;
     int32_t transposed;              /* 0: nn.Conv1d forward (model.py:77-78), 1: nn.ConvTranspose1d forward (model.py:88-102) */
-    int32_t schedule;                /* work-split bits of pg_conv_args.schedule (0-1, 4, 8-11).  One tile family since 0.4 (256 x 256 on 4
+    int32_t schedule;                /* work-split bits of pg_conv_args.schedule (0-1, 4, 8-11, 19-23).  One tile family since 0.4 (256 x 256 on 4
                                       * waves, one per SIMD); bits 5-6, which selected the removed ones, return PG_ERR_UNSUPPORTED */
     const uint16_t* x; int64_t x_bs; /* bf16 (B, Cin, x_pitch), batch stride in elements */
     int32_t x_pitch; int32_t _pad0;

@@ -301,6 +301,19 @@ def test_the_low_grade_rows_are_invisible_to_a_max_abs_bound():
 FP32_ROWS = list(dict.fromkeys((c[0], c[1]) for c in gpu.CASES))
 
 
+def assert_fp32_bound_rejects_the_split(row):
+    geom, op = row
+    for kind in gpu.KINDS:
+        t = gpu.inputs(geom, kind)
+        for x_act in ((ref.NONE, ref.LEAKY) if op == "fwd" else (x_act_of(op),)):           # the operands of the GPU module's calls
+            value, mag = ref.conv64(op, geom, t["x"], t["w"], t["dy"], x_act)
+            A, Bm, shape = ref.gemm(op, geom, t["x"], t["w"], t["dy"], x_act)
+            b = ref.errors(ref.seq32(A, Bm).reshape(shape), value, mag)
+            c = ref.errors(ref.x3(A, Bm).reshape(shape), value, mag)
+            assert c["r_rms"] >= 10.0 * b["r_rms"], (row, kind, x_act, b, c)
+            assert not ref.accept(c, b)
+
+
 def test_precision_rows_separate_fp32_from_the_split_by_10():
     skipped = []
     for row in FP32_ROWS:
@@ -308,19 +321,20 @@ def test_precision_rows_separate_fp32_from_the_split_by_10():
         if not gpu.precision_row(geom, op):
             skipped.append(f"{row_id(row)} (K = {ref.gemm_k(geom, op)})")
             continue
-        for kind in gpu.KINDS:
-            t = gpu.inputs(geom, kind)
-            for x_act in ((ref.NONE, ref.LEAKY) if op == "fwd" else (x_act_of(op),)):           # the operands of the GPU module's calls
-                value, mag = ref.conv64(op, geom, t["x"], t["w"], t["dy"], x_act)
-                A, Bm, shape = ref.gemm(op, geom, t["x"], t["w"], t["dy"], x_act)
-                b = ref.errors(ref.seq32(A, Bm).reshape(shape), value, mag)
-                c = ref.errors(ref.x3(A, Bm).reshape(shape), value, mag)
-                assert c["r_rms"] >= 10.0 * b["r_rms"], (row, kind, x_act, b, c)
-                assert not ref.accept(c, b)
+        assert_fp32_bound_rejects_the_split(row)
     print("\nrows without the precision check (GEMM K above 512; every other check is kept):")
     for s in skipped:
         print("  " + s)
     assert skipped == ["C136-130-k8s2p1-L62-B2-fwd (K = 1088)", "C160-136-k8s1p2-L65-B3-dgrad (K = 1088)", "T250-96-k8s2p6-L129-B2-dgrad (K = 768)"], skipped
+
+
+def test_split_rows_all_keep_the_precision_mark():
+    """the rows of tests/test_z_fixup_splits_gpu.py (SPLIT_CASES: the multi-tile work splits) have GEMM K <= 512, every one: the fp32
+    bound of their value tests rejects the bf16x3 split"""
+    from test_kernel_families import SPLIT_CASES
+    for row in dict.fromkeys((c[0], c[1]) for c in SPLIT_CASES):
+        assert gpu.precision_row(*row), row
+        assert_fp32_bound_rejects_the_split(row)
 
 
 # ---- (5) ---------------------------------------------------------------------------------------------------------------------------

@@ -47,8 +47,10 @@ def oracle_state(pn):
     return pp, ost, stats
 
 
-@pytest.mark.parametrize("C,L,B", [(1024, 256, 2), (512, 256, 1)], ids=["C1024-L256-B2", "C512-L256-B1"])
-def test_train_step_full_width_vs_oracle(C, L, B):
+def check_train_step_vs_oracle(C, L, B, label="full-width"):
+    """One Trainer.step at (C, L, B) under the calling thread's conv schedule against the oracle's step run with the device's sign
+    masks: every comparison and tolerance of the module docstring.  (tests/test_z_fixup_splits_gpu.py runs it at a small width under
+    PG_SCHED_SLOTS.)"""
     from oracle import unet_ref
     from phasegen.model import UNetModel
     from phasegen.trainer import Trainer
@@ -99,12 +101,17 @@ def test_train_step_full_width_vs_oracle(C, L, B):
         err["rv/" + k] = relmax(eng.arena.buffers[k + ".running_var"], stats[k + ".running_var"])
         assert int(eng.arena.buffers[k + ".num_batches_tracked"]) == int(stats[k + ".num_batches_tracked"]) == 1
     worst = {g: max((v, k) for k, v in err.items() if k.startswith(g)) for g in ("loss", "out", "act/", "grad/", "m/", "v/", "dp/", "rm/", "rv/")}
-    print(f"\nfull-width parity C={C} L={L} B={B}: " + ", ".join(f"{g}{v[0]:.2e}" for g, v in worst.items())
+    print(f"\n{label} parity C={C} L={L} B={B}: " + ", ".join(f"{g}{v[0]:.2e}" for g, v in worst.items())
           + f"; sign disagreements with the oracle's own forward: {flips} of {n_act} (largest |pre-activation| among them {flipped_mag:.1e} of max)")
     assert flips <= 1e-5 * n_act and flipped_mag < 1e-4
     tol = {"loss": 1e-5, "out": 1e-4, "act/": 1e-4, "grad/": 1e-4, "m/": 1e-4, "v/": 2e-4, "dp/": 2e-2, "rm/": 1e-4, "rv/": 1e-4}
     bad = {k: v for k, v in err.items() if v > next(t for g, t in tol.items() if k.startswith(g))}
     assert not bad, (bad, worst)
+
+
+@pytest.mark.parametrize("C,L,B", [(1024, 256, 2), (512, 256, 1)], ids=["C1024-L256-B2", "C512-L256-B1"])
+def test_train_step_full_width_vs_oracle(C, L, B):
+    check_train_step_vs_oracle(C, L, B)
 
 
 def test_forward_batch32_full_width_vs_oracle():

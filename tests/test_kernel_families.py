@@ -329,7 +329,7 @@ def test_view_cases_plan_is_the_declared_one_and_independent_of_strides():
     operand modes keep it (and their epilogue and form) at those precisions."""
     from phasegen import _lib, ops
     assert VIEW_CASES[:len(FIXUP_CASES)] == FIXUP_CASES and len(set(VIEW_CASES)) == len(VIEW_CASES)
-    for case in VIEW_CASES:
+    for case in VIEW_CASES + SPLIT_CASES:                    # (SPLIT_CASES: the multi-tile work splits, below)
         geom, op, sched, fam, epi, form = case
         opc = _opcode(_lib, case)
         for prec in (0, 1, 2) if fam in BF16_FAMILIES else (0,):
@@ -355,3 +355,235 @@ def test_view_cases_plan_is_the_declared_one_and_independent_of_strides():
     # what the table holds: every fixup instantiation of the fp32 entry points, every family's own epilogue, three kinds of tail
     assert {(c[3], c[4]) for c in VIEW_CASES if c[5] == "none"} >= {(c[3], c[4]) for c in FIXUP_CASES}
     assert {c[4] for c in VIEW_CASES if c[5] == "tail"} == {"F", "T", "Tpm"}
+
+
+# ---- the multi-tile work splits on small problems (tests/test_z_fixup_splits_gpu.py runs every row) ----------------------------------
+# Every row above has at most a handful of tiles, so a workgroup owns one whole tile or a fragment of one.  PG_SCHED_SLOTS(n) plans a
+# call as if the device had n compute units (host side only): the rows below put small problems through the work splits a full-size
+# layer takes on 256 CUs.  A plain restatement of make_split / split_lo (csrc/conv_common.h) names the regimes a row's plan is in; it
+# is used to CLASSIFY a row, never as an expected value -- the plan itself is pinned field by field from pg_conv_describe.
+def SLOTS(n):
+    return n << 19
+
+
+def split_ranges(tiles, nslab, grid, whole):
+    """[lo, hi) of every logical workgroup over the (tile, slab) space: the first `whole` own one whole tile each, the others share the
+    rest evenly, the first (rest mod workgroups) of them one slab longer"""
+    total, wn, gr = tiles * nslab, whole * nslab, grid - whole
+    q, r = divmod(total - wn, gr) if gr > 0 else (0, 0)
+
+    def lo(g):
+        if g < whole:
+            return g * nslab
+        g -= whole
+        return wn + (g * (q + 1) if g < r else r * (q + 1) + (g - r) * q)
+
+    return [(lo(g), lo(g + 1)) for g in range(grid)]
+
+
+def regimes(f, sched=0, auto=None, one_wave=False):
+    """the regimes of a described plan (f: its fields; sched: the row's schedule word; auto: the fields of the same call without
+    PG_SCHED_CONTENDED, for the contended regime; one_wave: conv_raw3 / conv_h3, one workgroup slot per CU instead of two)"""
+    tiles, nslab, grid, whole = int(f["tiles"]), int(f["slabs"]), int(f["grid"]), int(f["whole"])
+    out = set()
+    if tiles % grid == 0 and tiles // grid >= 2 and f["fixup"] == "none":
+        out.add("multi-whole")
+    if whole >= 2 and grid - whole >= 2 and f["fixup"] != "none":
+        out.add("hybrid")
+    if f["fixup"] != "none":
+        for lo, hi in split_ranges(tiles, nslab, grid, whole)[whole:]:
+            head, tail = lo % nslab != 0, hi % nslab != 0
+            if hi // nslab - -(-lo // nslab) >= 1:              # a whole tile inside the range
+                if head and tail:
+                    out.add("head-whole-tail")
+                elif tail:
+                    out.add("whole-then-partial")
+                elif head:
+                    out.add("partial-then-whole")
+    if sched & 16 and auto is not None and (auto["fixup"] == "none" or int(auto["whole"]) > 0) and f["fixup"] != "none" and whole == 0 and tiles > grid:
+        out.add("contended")
+    over, slots = ((sched >> 8) & 15) or 4, (sched >> 19) & 31          # (no factor given: the default, 4)
+    if slots and tiles > grid and grid == over * slots * (1 if one_wave else 2):
+        out.add("oversub")
+    return out
+
+
+IM2COL, STREAMK, NO_TALL, CONTENDED, NO_RAW3, ALL_RAW3, SR2, COLSPLIT = 4, 2, 8, 16, 0x2000, 0x4000, 0x10000, 0x40000
+
+
+def OVERSUB(f):
+    return f << 8
+
+
+# (row in FIXUP_CASES' format with the slot field inside the schedule word, the regimes the row is here for, its plan after the kernel name)
+SPLIT_TABLE = [
+    # conv_raw3 (256 x 256 tiles, one workgroup per CU): 2 tile rows (the second partial) x 3 tile columns (the last partial), 7 slabs
+    (((F_, 14, 390, 8, 2, 1, 260, 5), "fwd", ALL_RAW3 | SLOTS(1), "conv_raw3", "F", "none"), ("multi-whole",), "grid=3|tiles=6|slabs=7|split=0|whole=0|fixup=none"),
+    (((F_, 14, 390, 8, 2, 1, 260, 5), "fwd", ALL_RAW3 | STREAMK | SLOTS(4), "conv_raw3", "F", "plain"), ("head-whole-tail",), "grid=4|tiles=6|slabs=7|split=1|whole=0|fixup=plain"),
+    (((T_, 14, 390, 8, 1, 2, 130, 5), "fwd", ALL_RAW3 | SLOTS(1), "conv_raw3", "T", "none"), ("multi-whole",), "grid=3|tiles=6|slabs=7|split=0|whole=0|fixup=none"),
+    (((T_, 14, 390, 8, 1, 2, 130, 5), "fwd", ALL_RAW3 | STREAMK | SLOTS(4), "conv_raw3", "T", "plain"), ("head-whole-tail",), "grid=4|tiles=6|slabs=7|split=1|whole=0|fixup=plain"),
+    (((F_, 195, 28, 8, 2, 1, 260, 5), "dgrad", ALL_RAW3 | SLOTS(1), "conv_raw3", "Tpm", "none"), ("multi-whole",), "grid=3|tiles=6|slabs=7|split=0|whole=0|fixup=none"),
+    (((F_, 195, 28, 8, 2, 1, 260, 5), "dgrad", ALL_RAW3 | STREAMK | SLOTS(4), "conv_raw3", "Tpm", "plain"), ("head-whole-tail",), "grid=4|tiles=6|slabs=7|split=1|whole=0|fixup=plain"),
+    # ... in super-rows of 2 over 3 tile rows x 2 tile columns: the last super-row is short
+    (((F_, 14, 760, 8, 2, 1, 130, 5), "fwd", SR2 | ALL_RAW3 | SLOTS(1), "conv_raw3", "F", "none"), ("multi-whole",), "grid=3|tiles=6|slabs=7|split=0|whole=0|fixup=none"),
+    (((F_, 14, 760, 8, 2, 1, 130, 5), "fwd", SR2 | ALL_RAW3 | STREAMK | SLOTS(4), "conv_raw3", "F", "plain"), ("head-whole-tail",), "grid=4|tiles=6|slabs=7|split=1|whole=0|fixup=plain"),
+    (((F_, 380, 28, 8, 2, 1, 130, 5), "dgrad", SR2 | ALL_RAW3 | SLOTS(1), "conv_raw3", "Tpm", "none"), ("multi-whole",), "grid=3|tiles=6|slabs=7|split=0|whole=0|fixup=none"),
+    (((F_, 380, 28, 8, 2, 1, 130, 5), "dgrad", SR2 | ALL_RAW3 | STREAMK | SLOTS(4), "conv_raw3", "Tpm", "plain"), ("head-whole-tail",), "grid=4|tiles=6|slabs=7|split=1|whole=0|fixup=plain"),
+    # ... 2 x 4 tiles: the default oversubscription factor's grid of 4 x slots through the whole-tile branch (U0.dgrad's bench plan in miniature)
+    (((F_, 14, 390, 8, 2, 1, 390, 5), "fwd", ALL_RAW3 | SLOTS(1), "conv_raw3", "F", "none"), ("multi-whole", "oversub"), "grid=4|tiles=8|slabs=7|split=0|whole=0|fixup=none"),
+    # ... two whole tiles per workgroup over the full tile columns and the tall tile over the 47 columns behind them: D0.fwd at the bench shape in miniature
+    (((F_, 14, 390, 8, 2, 1, 326, 5), "fwd", COLSPLIT | ALL_RAW3 | SLOTS(1), "conv_raw3", "F", "tail"), ("multi-whole",), "grid=3|tiles=6|slabs=7|split=0|whole=0|fixup=none|tail=conv_raw_kernel<8, 2, false, 0, 1>,grid=2"),
+    # ... 16 slabs: hybrid (4 whole-tile workgroups, 2 tiles over 4 more), the even split PG_SCHED_CONTENDED takes instead, 3 and 6 tiles per workgroup
+    (((F_, 32, 390, 8, 2, 1, 260, 5), "fwd", ALL_RAW3 | SLOTS(4), "conv_raw3", "F", "plain"), ("hybrid",), "grid=8|tiles=6|slabs=16|split=1|whole=4|fixup=plain"),
+    (((F_, 32, 390, 8, 2, 1, 260, 5), "fwd", ALL_RAW3 | CONTENDED | SLOTS(4), "conv_raw3", "F", "plain"), ("contended",), "grid=4|tiles=6|slabs=16|split=1|whole=0|fixup=plain"),
+    (((F_, 32, 390, 8, 2, 1, 260, 5), "fwd", ALL_RAW3 | OVERSUB(2) | SLOTS(1), "conv_raw3", "F", "none"), ("multi-whole", "oversub"), "grid=2|tiles=6|slabs=16|split=0|whole=0|fixup=none"),
+    (((F_, 32, 390, 8, 2, 1, 260, 5), "fwd", ALL_RAW3 | OVERSUB(1) | SLOTS(1), "conv_raw3", "F", "none"), ("multi-whole", "oversub"), "grid=1|tiles=6|slabs=16|split=0|whole=0|fixup=none"),
+    (((F_, 390, 32, 8, 1, 2, 130, 5), "dgrad", ALL_RAW3 | SLOTS(4), "conv_raw3", "T", "plain"), ("hybrid",), "grid=8|tiles=6|slabs=16|split=1|whole=4|fixup=plain"),
+    # raw 128 x 256 (two workgroups per CU): 2 x 5 tiles, 3 slabs
+    (((F_, 12, 136, 4, 2, 1, 380, 6), "fwd", NO_RAW3 | NO_TALL | SLOTS(1), "conv_raw(128x256)", "F", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=3|split=0|whole=0|fixup=none"),
+    (((F_, 12, 136, 4, 2, 1, 380, 6), "fwd", NO_RAW3 | NO_TALL | STREAMK | SLOTS(2), "conv_raw(128x256)", "F", "plain"), ("head-whole-tail",), "grid=4|tiles=10|slabs=3|split=1|whole=0|fixup=plain"),
+    (((T_, 6, 136, 8, 1, 2, 190, 6), "fwd", NO_RAW3 | NO_TALL | SLOTS(1), "conv_raw(128x256)", "T", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=3|split=0|whole=0|fixup=none"),
+    (((T_, 6, 136, 8, 1, 2, 190, 6), "fwd", NO_RAW3 | NO_TALL | STREAMK | SLOTS(2), "conv_raw(128x256)", "T", "plain"), ("head-whole-tail",), "grid=4|tiles=10|slabs=3|split=1|whole=0|fixup=plain"),
+    (((F_, 68, 12, 8, 2, 1, 380, 6), "dgrad", NO_RAW3 | NO_TALL | SLOTS(1), "conv_raw(128x256)", "Tpm", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=3|split=0|whole=0|fixup=none"),
+    (((F_, 68, 12, 8, 2, 1, 380, 6), "dgrad", NO_RAW3 | NO_TALL | STREAMK | SLOTS(2), "conv_raw(128x256)", "Tpm", "plain"), ("head-whole-tail",), "grid=4|tiles=10|slabs=3|split=1|whole=0|fixup=plain"),
+    # ... 32 slabs: hybrid with the plain and with the wide fixup (2 split tiles over 4 / 8 workgroups), contended; 3 x 4 tiles: 3 and 6 per workgroup
+    (((F_, 128, 136, 4, 2, 1, 380, 6), "fwd", NO_RAW3 | NO_TALL | SLOTS(2), "conv_raw(128x256)", "F", "plain"), ("hybrid",), "grid=12|tiles=10|slabs=32|split=1|whole=8|fixup=plain"),
+    (((F_, 128, 136, 4, 2, 1, 380, 6), "fwd", NO_RAW3 | NO_TALL | SLOTS(4), "conv_raw(128x256)", "F", "wide"), ("hybrid",), "grid=16|tiles=10|slabs=32|split=1|whole=8|fixup=wide"),
+    (((F_, 128, 136, 4, 2, 1, 380, 6), "fwd", NO_RAW3 | NO_TALL | CONTENDED | SLOTS(2), "conv_raw(128x256)", "F", "plain"), ("contended",), "grid=4|tiles=10|slabs=32|split=1|whole=0|fixup=plain"),
+    (((F_, 32, 264, 4, 2, 1, 300, 6), "fwd", NO_RAW3 | NO_TALL | OVERSUB(2) | SLOTS(1), "conv_raw(128x256)", "F", "none"), ("multi-whole", "oversub"), "grid=4|tiles=12|slabs=8|split=0|whole=0|fixup=none"),
+    (((F_, 32, 264, 4, 2, 1, 300, 6), "fwd", NO_RAW3 | NO_TALL | OVERSUB(1) | SLOTS(1), "conv_raw(128x256)", "F", "none"), ("multi-whole", "oversub"), "grid=2|tiles=12|slabs=8|split=0|whole=0|fixup=none"),
+    # raw tall 256 x 128: 2 x 5 tiles, 3 slabs
+    (((F_, 12, 300, 4, 2, 1, 240, 5), "fwd", NO_RAW3 | SLOTS(1), "conv_raw(tall 256x128)", "F", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=3|split=0|whole=0|fixup=none"),
+    (((F_, 12, 300, 4, 2, 1, 240, 5), "fwd", NO_RAW3 | STREAMK | SLOTS(2), "conv_raw(tall 256x128)", "F", "plain"), ("head-whole-tail",), "grid=4|tiles=10|slabs=3|split=1|whole=0|fixup=plain"),
+    (((F_, 300, 6, 8, 1, 2, 120, 5), "dgrad", NO_RAW3 | SLOTS(1), "conv_raw(tall 256x128)", "T", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=3|split=0|whole=0|fixup=none"),
+    (((F_, 300, 6, 8, 1, 2, 120, 5), "dgrad", NO_RAW3 | STREAMK | SLOTS(2), "conv_raw(tall 256x128)", "T", "plain"), ("head-whole-tail",), "grid=4|tiles=10|slabs=3|split=1|whole=0|fixup=plain"),
+    (((T_, 12, 150, 8, 2, 1, 120, 5), "fwd", NO_RAW3 | SLOTS(1), "conv_raw(tall 256x128)", "Tpm", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=3|split=0|whole=0|fixup=none"),
+    (((T_, 12, 150, 8, 2, 1, 120, 5), "fwd", NO_RAW3 | STREAMK | SLOTS(2), "conv_raw(tall 256x128)", "Tpm", "plain"), ("head-whole-tail",), "grid=4|tiles=10|slabs=3|split=1|whole=0|fixup=plain"),
+    # im2col 256 x 128: 2 x 5 tiles
+    (((T_, 300, 12, 4, 2, 1, 120, 5), "dgrad", IM2COL | SLOTS(1), "conv_f", "F", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=3|split=0|whole=0|fixup=none"),
+    (((T_, 300, 12, 4, 2, 1, 120, 5), "dgrad", IM2COL | STREAMK | SLOTS(2), "conv_f", "F", "plain"), ("head-whole-tail",), "grid=4|tiles=10|slabs=3|split=1|whole=0|fixup=plain"),
+    (((F_, 300, 6, 8, 1, 2, 120, 5), "dgrad", IM2COL | SLOTS(1), "conv_t", "T", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=3|split=0|whole=0|fixup=none"),
+    (((F_, 300, 6, 8, 1, 2, 120, 5), "dgrad", IM2COL | STREAMK | SLOTS(2), "conv_t", "T", "plain"), ("head-whole-tail",), "grid=4|tiles=10|slabs=3|split=1|whole=0|fixup=plain"),
+    (((F_, 75, 300, 8, 2, 1, 40, 4), "wgrad", IM2COL | SLOTS(1), "conv_g", "G", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=5|split=0|whole=0|fixup=none"),
+    (((F_, 75, 300, 8, 2, 1, 40, 4), "wgrad", IM2COL | STREAMK | SLOTS(2), "conv_g", "G", "plain"), ("head-whole-tail",), "grid=4|tiles=10|slabs=5|split=1|whole=0|fixup=plain"),
+    # raw-window wgrads (128 x 256; k = 5: 255-column tiles): flat K, per-sample slabs; hybrid over 2 x 5 tiles x 16 slabs (plain fixup:
+    # 8 whole-tile workgroups, 2 tiles over 4 more) and over 2 x 7 (wide: 12 whole, 2 tiles over 4); K = 256 keeps the fp32 bound 10 x from the split
+    (((F_, 138, 136, 8, 2, 1, 40, 4), "wgrad", SLOTS(1), "conv_g_raw", "G", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=5|split=0|whole=0|fixup=none"),
+    (((F_, 138, 136, 8, 2, 1, 40, 4), "wgrad", STREAMK | SLOTS(2), "conv_g_raw", "G", "plain"), ("head-whole-tail",), "grid=4|tiles=10|slabs=5|split=1|whole=0|fixup=plain"),
+    (((F_, 35, 136, 32, 2, 16, 254, 2), "wgrad", SLOTS(2), "conv_g_raw", "G", "plain"), ("hybrid",), "grid=12|tiles=10|slabs=16|split=1|whole=8|fixup=plain"),
+    (((F_, 53, 136, 32, 2, 16, 254, 2), "wgrad", SLOTS(2), "conv_g_raw", "G", "wide"), ("hybrid",), "grid=16|tiles=14|slabs=16|split=1|whole=12|fixup=wide"),
+    (((F_, 35, 136, 32, 2, 16, 254, 2), "wgrad", CONTENDED | SLOTS(2), "conv_g_raw", "G", "plain"), ("contended",), "grid=4|tiles=10|slabs=16|split=1|whole=0|fixup=plain"),
+    (((F_, 112, 264, 8, 2, 1, 40, 4), "wgrad", OVERSUB(2) | SLOTS(1), "conv_g_raw", "G", "none"), ("multi-whole", "oversub"), "grid=4|tiles=12|slabs=5|split=0|whole=0|fixup=none"),
+    (((F_, 112, 264, 8, 2, 1, 40, 4), "wgrad", OVERSUB(1) | SLOTS(1), "conv_g_raw", "G", "none"), ("multi-whole", "oversub"), "grid=2|tiles=12|slabs=5|split=0|whole=0|fixup=none"),
+    (((F_, 138, 136, 8, 2, 1, 36, 5), "wgrad", SLOTS(1), "conv_g_ps", "G", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=5|split=0|whole=0|fixup=none"),
+    (((F_, 138, 136, 8, 2, 1, 36, 5), "wgrad", STREAMK | SLOTS(2), "conv_g_ps", "G", "plain"), ("head-whole-tail",), "grid=4|tiles=10|slabs=5|split=1|whole=0|fixup=plain"),
+    (((T_, 136, 220, 5, 2, 1, 30, 3), "wgrad", SLOTS(1), "conv_g_ps", "G", "none"), ("multi-whole",), "grid=2|tiles=10|slabs=6|split=0|whole=0|fixup=none"),
+    (((T_, 136, 220, 5, 2, 1, 30, 3), "wgrad", STREAMK | SLOTS(3), "conv_g_ps", "G", "plain"), ("head-whole-tail",), "grid=6|tiles=10|slabs=6|split=1|whole=0|fixup=plain"),
+    (((F_, 138, 136, 8, 2, 1, 252, 2), "wgrad", SLOTS(2), "conv_g_ps", "G", "plain"), ("hybrid",), "grid=12|tiles=10|slabs=16|split=1|whole=8|fixup=plain"),
+    (((F_, 212, 136, 8, 2, 1, 252, 2), "wgrad", SLOTS(2), "conv_g_ps", "G", "wide"), ("hybrid",), "grid=16|tiles=14|slabs=16|split=1|whole=12|fixup=wide"),
+]
+# pg_conv_fwd_h (conv_h3: 256 x 256 tiles, one workgroup per CU; 2 x 3 tiles): FIXUP_CASES_H's format and the schedule word
+SPLIT_TABLE_H = [
+    (((F_, 28, 390, 8, 1, 2, 130, 5), "F", "none", SLOTS(1)), ("multi-whole",), "grid=3|tiles=6|slabs=7|split=0|whole=0|fixup=none"),
+    (((F_, 28, 390, 8, 1, 2, 130, 5), "F", "plain", STREAMK | SLOTS(4)), ("head-whole-tail",), "grid=4|tiles=6|slabs=7|split=1|whole=0|fixup=plain"),
+    (((F_, 64, 390, 8, 1, 2, 130, 5), "F", "plain", SLOTS(4)), ("hybrid",), "grid=8|tiles=6|slabs=16|split=1|whole=4|fixup=plain"),
+    (((T_, 56, 195, 8, 2, 1, 130, 5), "T", "none", SLOTS(1)), ("multi-whole",), "grid=3|tiles=6|slabs=7|split=0|whole=0|fixup=none"),
+    (((T_, 56, 195, 8, 2, 1, 130, 5), "T", "plain", STREAMK | SLOTS(4)), ("head-whole-tail",), "grid=4|tiles=6|slabs=7|split=1|whole=0|fixup=plain"),
+    (((T_, 128, 195, 8, 2, 1, 130, 5), "T", "plain", SLOTS(4)), ("hybrid",), "grid=8|tiles=6|slabs=16|split=1|whole=4|fixup=plain"),
+]
+SPLIT_CASES = [row for row, _, _ in SPLIT_TABLE]
+SPLIT_CASES_H = [row for row, _, _ in SPLIT_TABLE_H]
+# What the tables leave out, by name:
+NOT_REACHED = {
+    "head-whole-tail with the wide fixup": "the wide form needs grid >= 8 x split tiles, a range that holds a whole tile needs grid < tiles",
+    "conv_raw3 with the wide fixup": "conv_raw3 takes the plain form however many segments a tile has (set_grid)",
+    "a mult x slots grid through the uneven split (mult = total slabs / (256 slots) >= 2)": "needs 512 slabs per slot -- 16 tiles per slot at "
+    "K = 512, where the value rows lose their [precision] mark; the oversub rows reach mult = 4, 2 and 1 through the whole-tile branch of pick_grid",
+}
+
+
+def _h_args(_lib, ops, geom, sched):
+    tr, Cin, Cout, k, s, p, Lin, B = geom
+    a = _lib.ConvhArgs()
+    a.B, a.Cin, a.Cout, a.Lin, a.k, a.stride, a.pad, a.transposed = B, Cin, Cout, Lin, k, s, p, int(tr)
+    a.Lout = (Lin - 1) * s - 2 * p + k if tr else (Lin + 2 * p - k) // s + 1
+    a.x_pitch = ops.h_pitch(Lin)
+    a.x_bs = Cin * a.x_pitch
+    a.x = a.w = a.y = 4096
+    a.y_bs = Cout * a.Lout
+    a.workspace, a.workspace_bytes = 4096, _lib.load().pg_workspace_bytes_conv()
+    a.schedule = sched
+    return a
+
+
+def _gemm_k(geom, op):
+    tr, Cin, Cout, k, s, p, Lin, B = geom
+    if op == "wgrad":
+        return B * (Lin if tr else (Lin + 2 * p - k) // s + 1)
+    return (Cin if op == "fwd" else Cout) * (-(-k // s) if tr == (op == "fwd") else k)
+
+
+def test_split_cases_plans_are_pinned_and_in_their_regime():
+    """Every SPLIT_CASES / SPLIT_CASES_H row: family, epilogue, grid, tiles, slabs, split, whole, fixup form and tail launch as the table
+    states them, at every precision the family has; the restated ranges put the plan into the regimes the row is there for; the same
+    call without the slot field is in none of them (a grid of at least as many workgroups as tiles, as in FIXUP_CASES); and the GEMM K
+    stays within 48 .. 512, where the value tests' fp32 bound still rejects the bf16x3 split."""
+    from phasegen import _lib, ops
+    assert len(set(SPLIT_CASES)) == len(SPLIT_CASES) and not set(SPLIT_CASES) & set(VIEW_CASES)
+    assert len({fixup_case_id(c) for c in SPLIT_CASES}) == len(SPLIT_CASES)
+    for case, declared, plan in SPLIT_TABLE:
+        geom, op, sched, fam, epi, form = case
+        assert (sched >> 19) & 31 and 48 <= _gemm_k(geom, op) <= 512, case
+        opc = _opcode(_lib, case)
+        for prec in (0, 1, 2) if fam in BF16_FAMILIES else (0,):
+            d = ops.conv_describe(_view_args(_lib, case, None, prec), opc)
+            f = _fields(d)
+            assert (family(d), _epilogue(d), d.split("|", 1)[1]) == (fam, epi, plan), (case, prec, d)
+            assert ("tail" in f) == (form == "tail") and (form == "tail" or f["fixup"] == form), (case, d)
+        auto = _fields(ops.conv_describe(_view_args(_lib, (geom, op, sched & ~CONTENDED) + case[3:], None), opc))
+        assert set(declared) <= regimes(f, sched, auto, fam == "conv_raw3"), (case, declared, regimes(f, sched, auto, fam == "conv_raw3"))
+        bare = _fields(ops.conv_describe(_view_args(_lib, (geom, op, sched & ~SLOTS(31)) + case[3:], None), opc))
+        assert regimes(bare, sched & ~SLOTS(31)) == set() and int(bare["grid"]) >= int(bare["tiles"]), (case, bare)
+    for (geom, epi, form, sched), declared, plan in SPLIT_TABLE_H:
+        assert (sched >> 19) & 31 and 48 <= _gemm_k(geom, "fwd") <= 512, geom
+        d = ops.conv_fwd_h_describe(_h_args(_lib, ops, geom, sched))
+        f = _fields(d)
+        assert (family(d), _epilogue(d), f["fixup"], d.split("|", 1)[1]) == ("conv_h3", epi, form, plan), (geom, sched, d)
+        assert set(declared) <= regimes(f, sched, None, True), (geom, sched, declared)
+        assert regimes(_fields(ops.conv_fwd_h_describe(_h_args(_lib, ops, geom, sched & ~SLOTS(31))))) == set()
+    # bits above the slot field stay refused; the Python constant is the header's macro
+    buf = ctypes.create_string_buffer(256)
+    assert _lib.load().pg_conv_describe(ctypes.byref(_args(_lib, 5, 14, 390, 260, 8, 2, 1, False, schedule=1 << 24)), _lib.OP_CONV1D_FWD, buf, 256) == _lib.ERR_SHAPE
+    assert _lib.SCHED_SLOTS(31) == SLOTS(31) == 31 << 19 and ops.SCHED_SLOTS(1) == SLOTS(1)
+    with pytest.raises(ValueError):
+        _lib.SCHED_SLOTS(32)
+
+
+def test_split_cases_hold_every_regime_for_every_family():
+    """Coverage of the tables, as test_every_fixup_instantiation_is_reached_by_a_small_case asserts it for FIXUP_CASES."""
+    by = {}
+    for (geom, op, sched, fam, epi, form), declared, _ in SPLIT_TABLE:
+        for r in declared:
+            by.setdefault(r, set()).add((fam, epi, form, sched))
+    pairs = {(c[3], c[4]) for c in FIXUP_CASES}
+    assert len(pairs) == 14
+    # several whole tiles per workgroup, and a range with a whole tile between a partial head and a partial tail: every (family, epilogue)
+    assert {(f, e) for f, e, _, _ in by["multi-whole"]} == pairs and {(f, e) for f, e, _, _ in by["head-whole-tail"]} == pairs
+    assert {form for _, _, form, _ in by["head-whole-tail"]} == {"plain"}                       # (NOT_REACHED: never wide)
+    # conv_raw3: super-rows of 2 over a short last super-row in both regimes, and whole tiles beside the column-tail launch
+    for regime in ("multi-whole", "head-whole-tail"):
+        assert {e for f, e, _, s in by[regime] if f == "conv_raw3" and s & SR2} == {"F", "Tpm"}
+    assert ("conv_raw3", "F", "tail") in {r[:3] for r in by["multi-whole"]}
+    # hybrid: conv_raw3 F and T; the 128 x 256 F kernel and both raw-window wgrads under the plain and under the wide fixup
+    assert {r[:3] for r in by["hybrid"]} == {("conv_raw3", "F", "plain"), ("conv_raw3", "T", "plain")} | {
+        (f, e, form) for f, e in (("conv_raw(128x256)", "F"), ("conv_g_raw", "G"), ("conv_g_ps", "G")) for form in ("plain", "wide")}
+    # contended, and oversubscription factors 2 and 1 over more tiles than slots
+    three = {"conv_raw3", "conv_raw(128x256)", "conv_g_raw"}
+    assert {f for f, _, _, _ in by["contended"]} == three
+    assert {(f, (s >> 8) & 15) for f, _, _, s in by["oversub"]} == {(f, o) for f in three for o in (1, 2)} | {("conv_raw3", 0)}      # (0: the default, 4)
+    # both fixup forms wherever a family of the table has both (the wide one under the hybrid split)
+    for fam in ("conv_raw(128x256)", "conv_g_raw", "conv_g_ps"):
+        assert {c[5] for c in SPLIT_CASES if c[3] == fam} >= {"none", "plain", "wide"}
+    assert {(epi, r) for (_, epi, _, _), declared, _ in SPLIT_TABLE_H for r in declared} == {
+        (e, r) for e in ("F", "T") for r in ("multi-whole", "head-whole-tail", "hybrid")}
+    assert len(NOT_REACHED) == 3

@@ -249,11 +249,9 @@ def _h_call(geom, sched, x, w, x_act):
     return y, yh[:, :, :Lout], yh2[:, :, :Lout]
 
 
-@pytest.mark.parametrize("row", H_ROWS, ids=_h_id)
-def test_values_conv_h3(row):
+def run_values_h3(geom, sched):
     """the resident forward at the bf16 criterion: float64 of the bf16 operands, 4 x sequential fp32 accumulation of the same; the bf16
     copies are the kernel's own fp32 result activated and rounded once"""
-    geom, epi, sched = row
     for kind in KINDS:
         t = inputs(geom, kind)
         for x_act, name in ((ref.NONE, "y"), (ref.LEAKY, "y(leaky x)")):
@@ -265,9 +263,7 @@ def test_values_conv_h3(row):
             assert np.array_equal(yh2.float().cpu().numpy(), ref.bf16(ref.act32(yc, ref.RELU)))
 
 
-@pytest.mark.parametrize("row", H_ROWS, ids=_h_id)
-def test_impulse_conv_h3(row):
-    geom, epi, sched = row
+def run_impulse_h3(geom, sched):
     tr, Cin, Cout, k, s, p, Lin, B = geom
     t = inputs(geom, "white")
     for v in range(ref.impulse_variants(B)):
@@ -278,5 +274,15 @@ def test_impulse_conv_h3(row):
         got = y.cpu().numpy()
         wrong = int(np.sum(got != want32))
         print(f"CONVIMPULSE bf16-resident conv_h3 fwd variant {v}: {int(np.sum(terms > 0))} selected elements, {wrong} differ")
-        assert wrong == 0, (row, v, np.argwhere(got != want32)[:8].tolist())
+        assert wrong == 0, (geom, sched, v, np.argwhere(got != want32)[:8].tolist())
         assert np.array_equal(yh.float().cpu().numpy(), ref.bf16(ref.act32(want32, ref.LEAKY)))
+
+
+@pytest.mark.parametrize("row", H_ROWS, ids=_h_id)
+def test_values_conv_h3(row):
+    run_values_h3(row[0], row[2])
+
+
+@pytest.mark.parametrize("row", H_ROWS, ids=_h_id)
+def test_impulse_conv_h3(row):
+    run_impulse_h3(row[0], row[2])

@@ -209,13 +209,12 @@ def test_views_bf16x3(case):
     _run(case, "bf16x3")
 
 
-@pytest.mark.parametrize("case", FIXUP_CASES_H, ids=lambda c: f"{'T' if c[0][0] else 'C'}{c[0][1]}-{c[0][2]}-k{c[0][3]}s{c[0][4]}-{c[1]}-{c[2]}")
-def test_views_conv_h3(case):
-    """pg_conv_fwd_h under the forced stream-K split: yh / yh2 as channel slices of wider ops.h_alloc buffers (as the resident forward
+def run_views_h3(geom, sched):
+    """pg_conv_fwd_h under schedule word `sched`: yh / yh2 as channel slices of wider ops.h_alloc buffers (as the resident forward
     writes the concat halves), stored as LeakyReLU / ReLU, bit-identical to the call on dense outputs; the row tails [Lout, pitch) inside
     the views stay zero, the sibling channels untouched."""
     from phasegen import ops
-    tr, Cin, Cout, k, s, p, Lin, B = case[0]
+    tr, Cin, Cout, k, s, p, Lin, B = geom
     dev = _dev()
     x = rnd(51, B, Cin, Lin)
     w = rnd(52, *((Cin, Cout, k) if tr else (Cout, Cin, k))) * 0.1
@@ -223,7 +222,7 @@ def test_views_conv_h3(case):
     xh = ops.h_alloc(B, Cin, Lin, dev)
     ops.cast_rows_bf16(x.to(dev), xh)
     wh = ops.shadow_weights(w.to(dev), tr, s)
-    kw = dict(transposed=tr, yh_act=ops.ACT_LEAKY, yh2_act=ops.ACT_RELU, schedule=2)
+    kw = dict(transposed=tr, yh_act=ops.ACT_LEAKY, yh2_act=ops.ACT_RELU, schedule=sched)
     d1, d2 = ops.h_alloc(B, Cout, Lout, dev), ops.h_alloc(B, Cout, Lout, dev)
     ops.conv_fwd_h(xh, Lin, wh, tuple(w.shape), s, p, yh=d1, yh2=d2, **kw)
     assert float(d1[:, :, :Lout].float().abs().max()) > 0.0
@@ -242,3 +241,9 @@ def test_views_conv_h3(case):
         for buf, v in zip(bufs, views):
             assert float(v[:, :, Lout:].float().abs().max()) == 0.0
             assert bool((buf[:, :off] == SENTINEL).all()) and bool((buf[:, off + Cout:] == SENTINEL).all())
+
+
+@pytest.mark.parametrize("case", FIXUP_CASES_H, ids=lambda c: f"{'T' if c[0][0] else 'C'}{c[0][1]}-{c[0][2]}-k{c[0][3]}s{c[0][4]}-{c[1]}-{c[2]}")
+def test_views_conv_h3(case):
+    """the forced stream-K split over every fixup instantiation of conv_h3"""
+    run_views_h3(case[0], 2)

@@ -70,11 +70,13 @@ struct Knobs {
     int sr;           // conv_raw3 tile order: super-row height forced by schedule bits 15-16 (0 = default)
     int force_colsplit;   // 1 = split wherever the geometry allows, whatever the cost model says (bit 18: tests reach the tail launch on small problems)
     int no_colsplit;  // 1 = never split the columns past the last full 256-wide tile off into a tail launch (bit 17: A/B, tests)
+    int slots;        // PG_SCHED_SLOTS (bits 19-23): plan as if the device had this many compute units (0 = pg_cu_count(): tests reach the
+                      // multi-tile work splits of the bench shape on small problems)
 };
 int decode_knobs(const pg_conv_args* a, Knobs& k) {
     if (a->precision < 0 || a->precision > 2) return pg_fail(PG_ERR_UNSUPPORTED, "conv: precision must be PG_PREC_FP32, PG_PREC_BF16 or PG_PREC_BF16X3");
     const int sc = a->schedule;
-    if (sc < 0 || (sc & ~0x7ffff) || ((sc >> 17) & 3) == 3 || (sc & 3) == 3 || ((sc >> 8) & 15) > 8) return pg_fail(PG_ERR_SHAPE, "conv: bad schedule bits");
+    if (sc < 0 || (sc & ~0xffffff) || ((sc >> 17) & 3) == 3 || (sc & 3) == 3 || ((sc >> 8) & 15) > 8) return pg_fail(PG_ERR_SHAPE, "conv: bad schedule bits");
     k.prec = a->precision;
     k.force_mode = sc & 3; k.no_raw = (sc >> 2) & 1; k.no_tall = (sc >> 3) & 1;
     k.oversub = (sc >> 8) & 15; if (!k.oversub) k.oversub = 4;
@@ -88,6 +90,7 @@ int decode_knobs(const pg_conv_args* a, Knobs& k) {
     k.sr = ((sc >> 15) & 3) ? 1 << (((sc >> 15) & 3) - 1) : 0;      // bits 15-16: 1 -> R = 1 (row-major), 2 -> 2, 3 -> 4; 0 = default
     k.no_colsplit = (sc >> 17) & 1;
     k.force_colsplit = (sc >> 18) & 1;
+    k.slots = (sc >> 19) & 31;
     if (k.no_raw3 && k.all_raw3) return pg_fail(PG_ERR_SHAPE, "conv: schedule bits 13 and 14 exclude each other");
     return PG_OK;
 }
@@ -102,10 +105,11 @@ bool fixup_wide(int grid, long split_tiles) { return split_tiles > 0 && grid >= 
 // degrades gracefully when slots are taken (16 of 512 slots held: 1x split 33 -> 58 ms, one-tile-per-workgroup 32 -> 43 ms,
 // 4x split 33 -> 37 ms).  Small problems (less than 8 slabs per resident slot, or no workspace) run one tile per
 // workgroup.  kn.force_mode: 0 auto, 1 force one tile per workgroup, 2 force stream-K (tests).  one_wave: the one-wave-per-SIMD
-// kernels (one workgroup per CU, partial tiles of 256 x 256).
+// kernels (one workgroup per CU, partial tiles of 256 x 256).  kn.slots: the compute units to plan for instead of the device's
+// (PG_SCHED_SLOTS); the only place the conv launch plan reads the CU count, so split_columns' pricing follows it too.
 int pick_grid(long tiles, int nslab, IgemmParams& p, long ws_bytes, const Knobs& kn, bool one_wave) {
     const long total = tiles * (long)nslab;
-    const long slots = (long)pg_cu_count() * (one_wave ? 1 : WG_PER_CU), ws_per_wg = one_wave ? 2 * WS_PER_WG : WS_PER_WG;
+    const long slots = (long)(kn.slots ? kn.slots : pg_cu_count()) * (one_wave ? 1 : WG_PER_CU), ws_per_wg = one_wave ? 2 * WS_PER_WG : WS_PER_WG;
     // the schedule is a function of the stream-K region only: a workspace that also holds packed wgrad operands splits the same way
     ws_bytes = std::min(ws_bytes, WS_STREAMK);
     p.whole = 0;

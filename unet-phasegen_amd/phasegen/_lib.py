@@ -21,7 +21,16 @@ SCHED_NO_RAW3 = 0x2000  # fp32 F / T: never the one-wave-per-SIMD kernels (conv_
 SCHED_ALL_RAW3 = 0x4000  # ... those kernels wherever they cover the problem (also the F form of k = 32, which auto leaves on the older ones)
 SCHED_NO_COLSPLIT = 0x20000  # fp32 F / T on conv_raw3: keep the columns past the last full 256-wide tile in the same launch (no tail launch)
 SCHED_COLSPLIT = 0x40000     # ... or always hand them to the tail launch where the geometry allows (tests; the automatic choice prices the tail)
-RS_KAISER_BEST, RS_KAISER_FAST = 0, 1      # pg_resample_args.quality (PG_RS_*)
+
+
+def SCHED_SLOTS(n):
+    """PG_SCHED_SLOTS(n), schedule bits 19-23: plan the call as if the device had n = 1..31 compute units (0: the device's own count)"""
+    if not 0 <= n <= 31:
+        raise ValueError("SCHED_SLOTS: n must be 0..31")
+    return n << 19
+
+
+RS_KAISER_BEST, RS_KAISER_FAST = 0, 1     # pg_resample_args.quality (PG_RS_*)
 # (pg_convh_args.schedule bits 5-6 selected tile families that ABI 0.4 removed; bit 12, the surviving conv_h3 family, is a no-op)
 
 c_float_p = C.c_void_p  # device pointers travel as integers

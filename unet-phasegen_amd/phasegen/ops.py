@@ -12,7 +12,7 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, SCHED_CONTENDED, SCHED_TILE_PER_WG  # noqa: F401  (re-exported)
+from ._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, SCHED_CONTENDED, SCHED_SLOTS, SCHED_TILE_PER_WG  # noqa: F401  (re-exported)
 
 
 def _stream():
@@ -220,8 +220,10 @@ def set_conv_schedule(mode):
     never the one-wave-per-SIMD fp32 kernels (conv_raw3.hip), i.e. the two-waves-per-SIMD raw kernels everywhere; bit 14 (0x4000):
     those kernels wherever they cover the problem, also where the automatic choice keeps the older ones (F form of k = 32); bits 15-16:
     their tile order (1 << 15: row-major, 2 << 15 / 3 << 15: super-rows of 2 / 4 tile rows); bit 17 (0x20000): never split the columns past the
-    last full 256-wide tile off into a tail launch, bit 18 (0x40000): always, where the geometry allows (the automatic choice prices it)."""
-    if mode < 0 or (mode & ~0x7e0ff) or (mode & 0x60000) == 0x60000 or (mode & 3) == 3 or (mode & 0x70) or (mode & 0x6000) == 0x6000:
+    last full 256-wide tile off into a tail launch, bit 18 (0x40000): always, where the geometry allows (the automatic choice prices it);
+    bits 19-23 (``SCHED_SLOTS(n)``): plan as if the device had n = 1..31 compute units, so that a small problem takes the work splits of
+    a full-size layer (several whole tiles per workgroup, whole tiles between two partial ones, the hybrid split)."""
+    if mode < 0 or (mode & ~0xffe0ff) or (mode & 0x60000) == 0x60000 or (mode & 3) == 3 or (mode & 0x70) or (mode & 0x6000) == 0x6000:
         raise ValueError("conv schedule: bad mode")
     _tls.schedule = (_tls.schedule & 0xf00) | mode
 
