@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import _lock_ref as lref
+import _stretch_args as shared
 import _vocoder_ref as ref
 
 
@@ -47,53 +48,27 @@ def test_struct_layout():
 
 def _args(_lib):
     """2 channels of 5 bins, 19 source frames -> 25 output frames; pointers are fake and never dereferenced."""
-    a = _lib.PhaseLockArgs()
-    a.n_ch, a.bins, a.F_src, a.F_out, a.src_per_out, a.reset_below = 2, 5, 19, 25, 0.75, 0.05
-    a.A = a.M = a.out = a.workspace = 4096
-    a.a_stride = a.m_stride = 5 * 19
-    a.workspace_bytes = 1 << 20
-    return a
+    return shared.args(_lib, "pg_phase_lock")
 
 
 def test_argument_errors_are_reported_before_any_launch():
+    """The table pg_phase_lock shares with pg_phase_vocoder (tests/_stretch_args.py), run through both: same codes, same words;
+    then what is pg_phase_lock's own."""
     from phasegen import _lib
     lib = _lib.load()
     f = lib.pg_phase_lock
-    assert f(None, None) == _lib.ERR_NULL
-    for field in ("A", "M", "out"):                                                 # M is required here
-        a = _args(_lib)
-        setattr(a, field, None)
-        assert f(ctypes.byref(a), None) == _lib.ERR_NULL and b"required" in lib.pg_last_error_string(), field
-    for field in ("n_ch", "bins", "F_src", "F_out"):
-        for bad in (0, -3):
-            a = _args(_lib)
-            setattr(a, field, bad)
-            assert f(ctypes.byref(a), None) == _lib.ERR_SHAPE and b"non-positive" in lib.pg_last_error_string(), (field, bad)
-    for bad in (0.0, -0.5, float("inf"), float("-inf"), float("nan")):
-        a = _args(_lib)
-        a.src_per_out = bad
-        assert f(ctypes.byref(a), None) == _lib.ERR_SHAPE and b"src_per_out" in lib.pg_last_error_string(), bad
-    for bad in (-1e-30, -1.0, float("inf"), float("-inf"), float("nan")):
-        a = _args(_lib)
-        a.reset_below = bad
-        assert f(ctypes.byref(a), None) == _lib.ERR_SHAPE and b"reset_below" in lib.pg_last_error_string(), bad
-    for field in ("a_stride", "m_stride"):
-        a = _args(_lib)
-        setattr(a, field, 5 * 19 - 1)
-        assert f(ctypes.byref(a), None) == _lib.ERR_SHAPE and field.encode() in lib.pg_last_error_string(), field
-    for field in ("A", "M", "out"):
-        for off in (1, 2, 3):
-            a = _args(_lib)
-            setattr(a, field, 4096 + off)
-            assert f(ctypes.byref(a), None) == _lib.ERR_ALIGN and b"misaligned" in lib.pg_last_error_string(), (field, off)
-    a = _args(_lib)
-    a.n_ch, a.bins, a.F_out = 1 << 30, 4096, 1 << 62
-    a.a_stride = a.m_stride = 4096 * 19
-    assert f(ctypes.byref(a), None) == _lib.ERR_SHAPE and b"2^62" in lib.pg_last_error_string()
+    shared.run_both(_lib)
+    a = _args(_lib)                                                                 # M is required here: the one documented difference
+    a.M = None
+    assert f(ctypes.byref(a), None) == _lib.ERR_NULL and b"required" in lib.pg_last_error_string()
     # the additions: the widest plane, and the workspace
     a = _args(_lib)
     a.bins, a.a_stride, a.m_stride = 4097, 4097 * 19, 4097 * 19
     assert f(ctypes.byref(a), None) == _lib.ERR_SHAPE and b"4096 bins" in lib.pg_last_error_string()
+    for off in (1, 2, 3):
+        a = _args(_lib)
+        a.workspace = 4096 + off
+        assert f(ctypes.byref(a), None) == _lib.ERR_ALIGN and b"misaligned" in lib.pg_last_error_string(), off
     need = lib.pg_workspace_bytes_phase_lock(ctypes.byref(_args(_lib)))
     for ws, nbytes in ((None, 1 << 20), (4096, need - 1), (4096, 0), (4096, -1)):
         a = _args(_lib)

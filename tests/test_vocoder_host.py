@@ -21,6 +21,7 @@ import inspect
 import numpy as np
 import pytest
 
+import _stretch_args as shared
 import _vocoder_ref as ref
 
 
@@ -47,48 +48,19 @@ def test_struct_layout():
 
 def _args(_lib):
     """2 channels of 5 bins, 19 source frames -> 25 output frames; pointers are fake and never dereferenced."""
-    a = _lib.PhaseVocoderArgs()
-    a.n_ch, a.bins, a.F_src, a.F_out, a.src_per_out, a.reset_below = 2, 5, 19, 25, 0.75, 0.05
-    a.A = a.M = a.out = 4096
-    a.a_stride = a.m_stride = 5 * 19
-    return a
+    return shared.args(_lib, "pg_phase_vocoder")
 
 
 def test_argument_errors_are_reported_before_any_launch():
+    """The table pg_phase_vocoder shares with pg_phase_lock (tests/_stretch_args.py: null fields, non-positive sizes, the bad
+    src_per_out and reset_below, short strides, misaligned pointers, the 2^62 overflow), run through both: same codes, same words."""
     from phasegen import _lib
     lib = _lib.load()
-    f = lib.pg_phase_vocoder
-    assert f(None, None) == _lib.ERR_NULL
-    for field in ("A", "out"):
-        a = _args(_lib)
-        setattr(a, field, None)
-        assert f(ctypes.byref(a), None) == _lib.ERR_NULL and b"required" in lib.pg_last_error_string(), field
-    for field in ("n_ch", "bins", "F_src", "F_out"):
-        for bad in (0, -3):
-            a = _args(_lib)
-            setattr(a, field, bad)
-            assert f(ctypes.byref(a), None) == _lib.ERR_SHAPE and b"non-positive" in lib.pg_last_error_string(), (field, bad)
-    for bad in (0.0, -0.5, float("inf"), float("-inf"), float("nan")):
-        a = _args(_lib)
-        a.src_per_out = bad
-        assert f(ctypes.byref(a), None) == _lib.ERR_SHAPE and b"src_per_out" in lib.pg_last_error_string(), bad
-    for bad in (-1e-30, -1.0, float("inf"), float("-inf"), float("nan")):
-        a = _args(_lib)
-        a.reset_below = bad
-        assert f(ctypes.byref(a), None) == _lib.ERR_SHAPE and b"reset_below" in lib.pg_last_error_string(), bad
-    for field in ("a_stride", "m_stride"):
-        a = _args(_lib)
-        setattr(a, field, 5 * 19 - 1)
-        assert f(ctypes.byref(a), None) == _lib.ERR_SHAPE and field.encode() in lib.pg_last_error_string(), field
-    for field in ("A", "M", "out"):
-        for off in (1, 2, 3):
-            a = _args(_lib)
-            setattr(a, field, 4096 + off)
-            assert f(ctypes.byref(a), None) == _lib.ERR_ALIGN and b"misaligned" in lib.pg_last_error_string(), (field, off)
+    shared.run_both(_lib)
     a = _args(_lib)                                                                 # without M its stride is not looked at
     a.M, a.m_stride, a.n_ch, a.bins, a.F_out = None, 0, 1 << 30, 1 << 30, 1 << 62
     a.a_stride = (1 << 30) * 19
-    assert f(ctypes.byref(a), None) == _lib.ERR_SHAPE and b"2^62" in lib.pg_last_error_string()
+    assert lib.pg_phase_vocoder(ctypes.byref(a), None) == _lib.ERR_SHAPE and b"2^62" in lib.pg_last_error_string()
 
 
 # ---- the Python surface --------------------------------------------------------------------------------------------------

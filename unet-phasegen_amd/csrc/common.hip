@@ -1,5 +1,6 @@
 // common.hip -- error string, version, fill.
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include "phasegen.h"
@@ -21,6 +22,15 @@ int pg_cu_count() {
 int pg_fail(int code, const char* msg) {
     snprintf(g_err, sizeof(g_err), "%s (code %d)", msg ? msg : "error", code);
     return code;
+}
+
+int pg_failf(int code, const char* fmt, ...) {
+    char msg[sizeof(g_err)];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof(msg), fmt, ap);
+    va_end(ap);
+    return pg_fail(code, msg);
 }
 
 extern "C" const char* pg_last_error_string(void) { return g_err; }

@@ -32,6 +32,7 @@
 #include <stdint.h>
 #include "phasegen.h"
 #include "pg_common.h"
+#include "pg_track.h"
 
 namespace {
 
@@ -40,8 +41,6 @@ constexpr int WC_CHUNK = 8192;             // samples per workgroup of pg_wave_c
 constexpr int SC_FRAMES = 256;             // frames per workgroup of pg_spec_compare: 64 lanes x 4
 constexpr int SC_WBINS = 16;               // bins per wave
 constexpr int SC_BINS = 4 * SC_WBINS;      // bins per workgroup
-
-__device__ __forceinline__ bool cmp_finite(float v) { return fabsf(v) <= FLT_MAX; }      // (false for NaN and inf)
 
 // Block-wide fold of six values; with MAX4 slot 4 is a maximum, else a sum.  Thread 0's copy is the result (every thread gets it).
 template <bool MAX4>
@@ -101,7 +100,7 @@ __global__ __launch_bounds__(CMP_THREADS) void wave_compare_kernel(const WcKerne
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float xf = xv[j], yf = yv[j];
-                if (!(cmp_finite(xf) && cmp_finite(yf))) { ++bad; xf = 0.f; yf = 0.f; }
+                if (!(pg_finite(xf) && pg_finite(yf))) { ++bad; xf = 0.f; yf = 0.f; }
                 const double xd = (double)xf, yd = (double)yf;
                 v[0] += xd * xd;
                 v[1] += yd * yd;
@@ -193,7 +192,7 @@ __global__ __launch_bounds__(CMP_THREADS) void spec_compare_kernel(const ScKerne
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if (!(cmp_finite(rr[j]) && cmp_finite(ri[j]) && cmp_finite(er[j]) && cmp_finite(ei[j]))) {
+                if (!(pg_finite(rr[j]) && pg_finite(ri[j]) && pg_finite(er[j]) && pg_finite(ei[j]))) {
                     ++bad;
                     rr[j] = ri[j] = er[j] = ei[j] = 0.f;
                 }
@@ -265,7 +264,7 @@ struct ScPlan { int64_t ntiles, nblocks, cell_elems, tile_elems, frame_elems; };
 int sc_check(const pg_spec_compare_args* a, ScPlan* p) {
     if (!a) return pg_fail(PG_ERR_NULL, "spec_compare: null args");
     if (a->n_signals <= 0 || a->bins <= 0 || a->frames <= 0) return pg_fail(PG_ERR_SHAPE, "spec_compare: non-positive dimension");
-    if (!(a->floor_power > 0.f) || !(a->floor_power <= FLT_MAX)) return pg_fail(PG_ERR_SHAPE, "spec_compare: floor_power must be positive and finite");
+    if (!(a->floor_power > 0.f) || !pg_finite(a->floor_power)) return pg_fail(PG_ERR_SHAPE, "spec_compare: floor_power must be positive and finite");
     p->ntiles = ((int64_t)a->frames + SC_FRAMES - 1) / SC_FRAMES;
     p->nblocks = ((int64_t)a->bins + SC_BINS - 1) / SC_BINS;
     if (p->ntiles * p->nblocks > INT32_MAX / a->n_signals) return pg_fail(PG_ERR_SHAPE, "spec_compare: more than 2^31 workgroups");
@@ -274,8 +273,6 @@ int sc_check(const pg_spec_compare_args* a, ScPlan* p) {
     p->frame_elems = (int64_t)a->n_signals * p->nblocks * a->frames;
     return PG_OK;
 }
-
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 }  // namespace
 
@@ -297,7 +294,7 @@ extern "C" int pg_wave_compare(const pg_wave_compare_args* a, void* stream) {
         return pg_fail(PG_ERR_WORKSPACE, "wave_compare: needs a workspace of pg_workspace_bytes_wave_compare() bytes");
     if ((uintptr_t)a->workspace & 7) return pg_fail(PG_ERR_ALIGN, "wave_compare: workspace must be 8-byte aligned");
     // (a stride that is never applied -- one signal -- does not decide)
-    const bool wide = al16(a->x) && al16(a->y) && (a->n_signals == 1 || ((a->x_stride & 3) == 0 && (a->y_stride & 3) == 0));
+    const bool wide = pg_al16(a->x) && pg_al16(a->y) && (a->n_signals == 1 || ((a->x_stride & 3) == 0 && (a->y_stride & 3) == 0));
     WcKernelArgs k;
     k.x = a->x; k.y = a->y; k.gain = a->gain; k.partial = (double*)a->workspace;
     k.n = a->n; k.x_stride = a->n_signals == 1 ? 0 : a->x_stride; k.y_stride = a->n_signals == 1 ? 0 : a->y_stride;
@@ -332,7 +329,7 @@ extern "C" int pg_spec_compare(const pg_spec_compare_args* a, void* stream) {
     if (!a->workspace || a->workspace_bytes < pg_workspace_bytes_spec_compare(a))
         return pg_fail(PG_ERR_WORKSPACE, "spec_compare: needs a workspace of pg_workspace_bytes_spec_compare() bytes");
     if ((uintptr_t)a->workspace & 7) return pg_fail(PG_ERR_ALIGN, "spec_compare: workspace must be 8-byte aligned");
-    const bool wide = (a->frames & 3) == 0 && al16(a->R) && al16(a->E)
+    const bool wide = (a->frames & 3) == 0 && pg_al16(a->R) && pg_al16(a->E)
                       && (a->n_signals == 1 || ((a->r_stride & 3) == 0 && (a->e_stride & 3) == 0));
     ScKernelArgs k;
     k.R = a->R; k.E = a->E; k.gain = a->gain;

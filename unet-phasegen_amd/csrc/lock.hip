@@ -4,7 +4,8 @@
 // phase relations inside a lobe survive the stretch.  The reference has no counterpart; the arithmetic is the contract
 // (include/phasegen.h states it) and tests/_lock_ref.py restates it in numpy, bit for bit.
 //
-// The recurrence.  Per channel, T_g[b] (uint32, a fraction of a turn) is the rotation of bin b at output frame g against its analysis
+// The recurrence (q(), angle(), i0(g), i1(g) and the advance into frame g are pg_track.h's, shared with vocoder.hip).  Per channel,
+// T_g[b] (uint32, a fraction of a turn) is the rotation of bin b at output frame g against its analysis
 // phase: T_0 = 0 and T_g[b] = reset ? 0 : T_{g-1}[p] + e_g[p] with p = P_g(b) the peak bin b belongs to, e_g[p] = q(A[p][i1(g-1)]) -
 // q(A[p][i0(g)]) and reset = M[p][i0(g)] < reset_below; out[b][g] = angle(T_g[b] + q(A[b][i0(g)])).  Frame g is therefore a GATHER MAP
 // (src_g, c_g): T_g[b] = T_{g-1}[src_g[b]] + c_g[b], where a reset is the source index `bins`, the zero source (T[bins] == 0).  Maps
@@ -41,15 +42,16 @@
 #include <stdint.h>
 #include "phasegen.h"
 #include "pg_common.h"
+#include "pg_track.h"
 
 namespace {
 
+namespace tk = pg_track;
 constexpr int LK_CHUNK = 32;                                // L: output frames per chunk (a multiple of 4: chunks begin on a 16-byte unit)
 constexpr int LK_MAX_BINS = 4096;
 constexpr int LK_MAX_THREADS = 1024;
 constexpr int LK_WORDS = LK_MAX_BINS / 64;                  // words of the peak bitmask
 constexpr int LK_RING = 8;                                  // map words per thread in flight in the carry: 8 / BPT chunk maps
-constexpr double LK_TWO_PI = 6.283185307179586;
 static_assert(PG_LOCK_REACH == 2, "the peak test below is written for a reach of 2");
 static_assert(LK_CHUNK % 4 == 0, "16-byte stores need chunks of whole units");
 
@@ -63,34 +65,14 @@ struct LkArgs {
     float reset_below;
 };
 
-__device__ __forceinline__ uint32_t lk_q(float x) {
-    if (!(fabsf(x) <= 1048576.0f)) return 0u;               // NaN, +-inf and |x| > 2^20
-    const double K = 4294967296.0 / LK_TWO_PI;
-    return (uint32_t)(int64_t)rint((double)x * K);
-}
-
-__device__ __forceinline__ long lk_i0(long g, double spo, long F_src) {
-    const double fl = floor((double)g * spo);
-    return fl < (double)F_src ? (long)fl : F_src - 1;        // (also for a position beyond the int64 range)
-}
-
-__device__ __forceinline__ float lk_angle(uint32_t acc) {
-    const double R = LK_TWO_PI / 4294967296.0;
-    return (float)((double)(int32_t)acc * R);
-}
-
 // what a thread reads of frame g for its bins: the magnitude, the quantised analysis phase and the advance e_g
 template <int BPT>
 struct LkFrame { float m[BPT]; uint32_t qa[BPT]; uint32_t e[BPT]; };
 
 template <int BPT>
 __device__ __forceinline__ void lk_load(const LkArgs& a, const float* Ac, const float* Mc, long g, LkFrame<BPT>& f) {
-    const long i0 = lk_i0(g, a.src_per_out, a.F_src);
-    long i1p = i0;                                          // i1(g - 1); frame 0 has no advance
-    if (g > 0) {
-        const long j0 = lk_i0(g - 1, a.src_per_out, a.F_src);
-        i1p = j0 + 1 < a.F_src ? j0 + 1 : a.F_src - 1;
-    }
+    const tk::Advance adv = tk::advance(g, a.src_per_out, a.F_src);
+    const long i0 = adv.i0, i1p = adv.i1p;
 #pragma unroll
     for (int j = 0; j < BPT; ++j) {
         const int b = (int)threadIdx.x + j * (int)blockDim.x;
@@ -99,8 +81,8 @@ __device__ __forceinline__ void lk_load(const LkArgs& a, const float* Ac, const 
         if (b < a.bins) {
             const long row = (long)b * a.F_src;
             f.m[j] = Mc[row + i0];
-            f.qa[j] = lk_q(Ac[row + i0]);
-            f.e[j] = (i1p == i0 ? f.qa[j] : lk_q(Ac[row + i1p])) - f.qa[j];
+            f.qa[j] = tk::q(Ac[row + i0]);
+            f.e[j] = (i1p == i0 ? f.qa[j] : tk::q(Ac[row + i1p])) - f.qa[j];
         }
     }
 }
@@ -113,12 +95,8 @@ __device__ __forceinline__ void lk_load(const LkArgs& a, const float* Ac, const 
 template <int BPT>
 __device__ __forceinline__ void lk_fetch(const LkArgs& a, const float* Ac, const float* Mc, long g, uint32_t* win, int wt, long& ws0,
                                          LkFrame<BPT>& f) {
-    const long i0 = lk_i0(g, a.src_per_out, a.F_src);
-    long i1p = i0;
-    if (g > 0) {
-        const long j0 = lk_i0(g - 1, a.src_per_out, a.F_src);
-        i1p = j0 + 1 < a.F_src ? j0 + 1 : a.F_src - 1;
-    }
+    const tk::Advance adv = tk::advance(g, a.src_per_out, a.F_src);
+    const long i0 = adv.i0, i1p = adv.i1p;
     const long lo = i0 < i1p ? i0 : i1p, hi = i0 < i1p ? i1p : i0;
     if (wt == 0 || hi - lo >= wt) { lk_load<BPT>(a, Ac, Mc, g, f); return; }
     const int pitch = wt + 1, tid = threadIdx.x, nt = blockDim.x;
@@ -133,7 +111,7 @@ __device__ __forceinline__ void lk_fetch(const LkArgs& a, const float* Ac, const
             if (ws0 + k < a.F_src) {
                 const long at = (long)r * a.F_src + ws0 + k;
                 winM[r * pitch + k] = __float_as_uint(Mc[at]);
-                winA[r * pitch + k] = lk_q(Ac[at]);
+                winA[r * pitch + k] = tk::q(Ac[at]);
             }
         }
         __syncthreads();
@@ -369,7 +347,7 @@ __global__ __launch_bounds__(LK_MAX_THREADS) void lock_apply_kernel(const LkArgs
                         const bool reset = g == 0 || __uint_as_float(msf[pj]) < a.reset_below;
                         const uint32_t t = reset ? 0u : Tc[pj] + esf[pj];
                         Tn[b] = t;
-                        const float v = lk_angle(t + f.qa[j]);
+                        const float v = tk::angle(t + f.qa[j]);
                         if (VEC) {
                             o[j][0] = u == 0 ? v : o[j][0]; o[j][1] = u == 1 ? v : o[j][1];
                             o[j][2] = u == 2 ? v : o[j][2]; o[j][3] = u == 3 ? v : o[j][3];
@@ -448,29 +426,17 @@ int64_t lk_workspace_bytes(const pg_phase_lock_args* a) {
 extern "C" int64_t pg_workspace_bytes_phase_lock(const pg_phase_lock_args* a) { return lk_workspace_bytes(a); }
 
 extern "C" int pg_phase_lock(const pg_phase_lock_args* a, void* stream) {
-    if (!a || !a->A || !a->M || !a->out) return pg_fail(PG_ERR_NULL, "phase_lock: args, A, M and out required");
-    if (a->n_ch <= 0 || a->bins <= 0 || a->F_src <= 0 || a->F_out <= 0) return pg_fail(PG_ERR_SHAPE, "phase_lock: non-positive dimension");
-    if (a->bins > LK_MAX_BINS) return pg_fail(PG_ERR_SHAPE, "phase_lock: more than 4096 bins");
-    if (!(a->src_per_out > 0.0) || !(a->src_per_out <= 1.7976931348623157e308)) return pg_fail(PG_ERR_SHAPE, "phase_lock: src_per_out must be finite and positive");
-    if (!(a->reset_below >= 0.0f) || !(a->reset_below <= 3.402823466e+38f)) return pg_fail(PG_ERR_SHAPE, "phase_lock: reset_below must be finite and not negative");
-    if (a->F_src > INT64_MAX / 2 / a->bins) return pg_fail(PG_ERR_SHAPE, "phase_lock: plane beyond 2^62 elements");
-    if (a->a_stride < (int64_t)a->bins * a->F_src) return pg_fail(PG_ERR_SHAPE, "phase_lock: a_stride shorter than a plane");
-    if (a->m_stride < (int64_t)a->bins * a->F_src) return pg_fail(PG_ERR_SHAPE, "phase_lock: m_stride shorter than a plane");
-    const int64_t rows = (int64_t)a->n_ch * a->bins;
-    if (rows > INT64_MAX / 2 / a->F_out) return pg_fail(PG_ERR_SHAPE, "phase_lock: output beyond 2^62 elements");
-    if ((((uintptr_t)a->A) & 3) || (((uintptr_t)a->M) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->workspace) & 3))
-        return pg_fail(PG_ERR_ALIGN, "phase_lock: misaligned pointer");
+    LkArgs k;
+    bool wide;
+    if (int e = pg_stretch_check("phase_lock", true, LK_MAX_BINS, a, k, wide)) return e;
+    if (((uintptr_t)a->workspace) & 3) return pg_fail(PG_ERR_ALIGN, "phase_lock: misaligned pointer");
     const int64_t need = lk_workspace_bytes(a);
     if (need < 0) return (int)need;
     if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_lock: workspace missing or smaller than pg_workspace_bytes_phase_lock()");
-    const bool wide = (a->F_out & 3) == 0 && (((uintptr_t)a->out) & 15) == 0;
     const int bpt = lk_bpt(a->bins), threads = lk_threads(a->bins);
-    LkArgs k;
-    k.A = a->A; k.M = a->M; k.out = a->out; k.ws = (uint32_t*)a->workspace;
-    k.src_per_out = a->src_per_out;
-    k.a_stride = a->n_ch == 1 ? 0 : a->a_stride; k.m_stride = a->n_ch == 1 ? 0 : a->m_stride;
-    k.F_src = a->F_src; k.F_out = a->F_out; k.n_chunks = (a->F_out - 1) / LK_CHUNK + 1;
-    k.bins = a->bins; k.nb = bpt * threads; k.reset_below = a->reset_below;
+    k.ws = (uint32_t*)a->workspace;
+    k.n_chunks = (a->F_out - 1) / LK_CHUNK + 1;
+    k.nb = bpt * threads;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
     switch (bpt) {

@@ -5,6 +5,8 @@
 
 // Records `msg` as the calling thread's last error and returns `code` (see pg_last_error_string()).
 int pg_fail(int code, const char* msg);
+// The same with a printf-style message.
+int pg_failf(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 // Number of CUs of the current device (immutable per device; cached).
 int pg_cu_count();
 // taps per output phase in a transposed conv's bf16 weight shadow (pointwise.hip)

@@ -1,0 +1,124 @@
+// pg_track.h -- the rules the track kernels share (stitch.hip, spectral.hip, vocoder.hip, lock.hip, compare.hip; not part of the
+// ABI).  include/phasegen.h states each of them once and promises bit-for-bit equalities between entry points that rest on them --
+// pg_phase_lock with one bin equals pg_phase_vocoder, a stretch of 1 returns q(A), both joins cut a track at the same places -- so
+// each is ONE piece of code here.  Everything on the device side is __forceinline__: the kernels compile to what they would with
+// the text written out in place.
+#pragma once
+#include <float.h>
+#include <math.h>
+#include <stdint.h>
+#include "pg_common.h"
+
+// false for NaN and +-inf
+__host__ __device__ __forceinline__ bool pg_finite(float v) { return fabsf(v) <= FLT_MAX; }
+
+namespace pg_track {
+
+// ---- The phase grid: a phase is a 32-bit unsigned fraction of a turn, so sums wrap and are exact in any order.  Each constant is
+// the one double division the contract names.
+constexpr double TWO_PI = 6.283185307179586;
+constexpr double K = 4294967296.0 / TWO_PI;
+constexpr double R = TWO_PI / 4294967296.0;
+
+__device__ __forceinline__ uint32_t q(float x) {
+    if (!(fabsf(x) <= 1048576.0f)) return 0u;               // NaN, +-inf and |x| > 2^20
+    return (uint32_t)(int64_t)rint((double)x * K);
+}
+
+__device__ __forceinline__ float angle(uint32_t acc) { return (float)((double)(int32_t)acc * R); }
+
+// ---- The stretched time grid: output frame g (>= 0) sits at p = (double)g * src_per_out of the source, between the source frames
+// i0 = min((int64)floor(p), F_src - 1) and i1 = min(i0 + 1, F_src - 1).
+__device__ __forceinline__ long i0(long g, double spo, long F_src) {
+    const double fl = floor((double)g * spo);
+    return fl < (double)F_src ? (long)fl : F_src - 1;        // (also for a position beyond the int64 range)
+}
+
+__device__ __forceinline__ long i1(long i0, long F_src) { return i0 + 1 < F_src ? i0 + 1 : F_src - 1; }
+
+// the advance into frame g is measured between i1(g - 1) and i0(g); frame 0 has none (i1p == i0)
+struct Advance { long i0, i1p; };
+__device__ __forceinline__ Advance advance(long g, double spo, long F_src) {
+    Advance s;
+    s.i0 = i0(g, spo, F_src);
+    s.i1p = g > 0 ? i1(i0(g - 1, spo, F_src), F_src) : s.i0;
+    return s;
+}
+
+// ---- The two-clip crossfade join.  Clip k begins at element k step of the output row and shares its first V elements with the
+// tail of clip k - 1 (2 V <= clip length: at most two clips cover an element).  Element t: k = min(t div step, n_clips - 1),
+// j = t - k step; shared iff k >= 1 and j < V, and then blend(ramp[V-1-j], ramp[j], lo, hi) with hi = clip[k][j] and
+// lo = clip[k-1][j + step], the lower clip's term first; every other element is clip[k][j] bit for bit.
+struct Join { const float* ramp; long step, clip_stride; int n_clips, V; };
+struct JoinAt { long k, j; const float* hp; };               // hp: clip[k] + j of the row whose clip 0 begins at `base`
+
+__device__ __forceinline__ JoinAt join_locate(const Join& jn, const float* base, long t) {
+    JoinAt at;
+    at.k = t / jn.step;
+    if (at.k > jn.n_clips - 1) at.k = jn.n_clips - 1;
+    at.j = t - at.k * jn.step;
+    at.hp = base + at.k * jn.clip_stride + at.j;
+    return at;
+}
+
+template <typename Blend>
+__device__ __forceinline__ float join_one(const Join& jn, const float* base, long t, Blend blend) {
+    const JoinAt at = join_locate(jn, base, t);
+    const float hi = *at.hp;
+    if (at.k >= 1 && at.j < jn.V) return blend(jn.ramp[jn.V - 1 - at.j], jn.ramp[at.j], at.hp[jn.step - jn.clip_stride], hi);
+    return hi;
+}
+
+// Elements t .. t + 3 as 16-byte accesses: step and V are multiples of 4 there, so the four never straddle a clip boundary or the
+// end of a shared region, and the reversed ramp ramp[V-1-j-i] is the 16-byte load at V-4-j read backwards.
+template <typename Blend>
+__device__ __forceinline__ f32x4 join_four(const Join& jn, const float* base, long t, Blend blend) {
+    const JoinAt at = join_locate(jn, base, t);
+    f32x4 v = *(const f32x4*)at.hp;
+    if (at.k >= 1 && at.j < jn.V) {
+        const f32x4 lo = *(const f32x4*)(at.hp + (jn.step - jn.clip_stride));
+        const f32x4 rb = *(const f32x4*)(jn.ramp + at.j), ra = *(const f32x4*)(jn.ramp + (jn.V - 4 - at.j));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = blend(ra[3 - i], rb[i], lo[i], v[i]);
+    }
+    return v;
+}
+
+}  // namespace pg_track
+
+// ---- Host side of a streaming launch
+inline bool pg_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// Units are walked grid-stride by at most 8 workgroups per CU, and never by more than PG_STREAM_MAX_BLOCKS (256 CUs x 8), which
+// also sizes pg_stitch's workspace on the host without asking a device.
+constexpr int PG_STREAM_MAX_BLOCKS = 2048;
+inline unsigned pg_stream_grid(long units, int threads) {
+    long cap = (long)pg_cu_count() * 8; if (cap > PG_STREAM_MAX_BLOCKS) cap = PG_STREAM_MAX_BLOCKS; if (cap < 1) cap = 1;
+    const long grid = (units + threads - 1) / threads;
+    return (unsigned)(grid > cap ? cap : grid);
+}
+
+// The host checks of a stretched-plane call (pg_phase_vocoder_args, or pg_phase_lock_args, which begins with the same fields), in
+// the order that decides which error a doubly-bad call reports, and the kernel arguments both take: k.A .. k.reset_below, with the
+// stride of a single channel 0.  `op` prefixes every message; need_M: M may not be NULL; max_bins: the op's own limit.  wide: `out`
+// takes 16-byte stores.
+template <typename Args, typename KernelArgs>
+int pg_stretch_check(const char* op, bool need_M, int max_bins, const Args* a, KernelArgs& k, bool& wide) {
+    if (!a || !a->A || (need_M && !a->M) || !a->out) return pg_failf(PG_ERR_NULL, "%s: args, A%s and out required", op, need_M ? ", M" : "");
+    if (a->n_ch <= 0 || a->bins <= 0 || a->F_src <= 0 || a->F_out <= 0) return pg_failf(PG_ERR_SHAPE, "%s: non-positive dimension", op);
+    if (a->bins > max_bins) return pg_failf(PG_ERR_SHAPE, "%s: more than %d bins", op, max_bins);
+    if (!(a->src_per_out > 0.0) || !(a->src_per_out <= DBL_MAX)) return pg_failf(PG_ERR_SHAPE, "%s: src_per_out must be finite and positive", op);
+    if (!(a->reset_below >= 0.0f) || !pg_finite(a->reset_below)) return pg_failf(PG_ERR_SHAPE, "%s: reset_below must be finite and not negative", op);
+    if (a->F_src > INT64_MAX / 2 / a->bins) return pg_failf(PG_ERR_SHAPE, "%s: plane beyond 2^62 elements", op);
+    if (a->a_stride < (int64_t)a->bins * a->F_src) return pg_failf(PG_ERR_SHAPE, "%s: a_stride shorter than a plane", op);
+    if (a->M && a->m_stride < (int64_t)a->bins * a->F_src) return pg_failf(PG_ERR_SHAPE, "%s: m_stride shorter than a plane", op);
+    if ((int64_t)a->n_ch * a->bins > INT64_MAX / 2 / a->F_out) return pg_failf(PG_ERR_SHAPE, "%s: output beyond 2^62 elements", op);
+    if ((((uintptr_t)a->A) & 3) || (((uintptr_t)a->M) & 3) || (((uintptr_t)a->out) & 3)) return pg_failf(PG_ERR_ALIGN, "%s: misaligned pointer", op);
+    wide = (a->F_out & 3) == 0 && pg_al16(a->out);
+    k.A = a->A; k.M = a->M; k.out = a->out;
+    k.src_per_out = a->src_per_out;
+    k.a_stride = a->n_ch == 1 ? 0 : a->a_stride; k.m_stride = a->n_ch == 1 ? 0 : a->m_stride;
+    k.F_src = a->F_src; k.F_out = a->F_out;
+    k.bins = a->bins; k.reset_below = a->reset_below;
+    return PG_OK;
+}

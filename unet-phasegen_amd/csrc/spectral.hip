@@ -6,34 +6,37 @@
 // Geometry of both.  Clip k covers the global frames k sf .. k sf + frames - 1 of the track's frame grid, sf the frame stride between
 // clips; Vf = frames - sf frames are shared with the next clip.
 //
-// pg_spec_clips.  Output frame f of clip k is global frame g = k sf + f; p = (double)g * src_per_out is its position in the source
-// plane, i0 = min((int64)floor(p), F_src - 1), i1 = min(i0 + 1, F_src - 1), w = (float)(p - floor(p)); out = P[i0] bit for bit when
-// w == 0, else fl(a + fl(w fl(b1 - a))) with a = P[i0], b1 = P[i1] in fp32, nothing contracted (-ffp-contract=off).
-// src_per_out == 1.0 is therefore a copy (clamped at the last source frame), and n_clips = 1 resamples a whole plane.
+// pg_spec_clips.  Output frame f of clip k is global frame g = k sf + f; its source position p = (double)g * src_per_out and the two
+// source frames i0, i1 around it are pg_track.h's time grid (the one pg_phase_vocoder and pg_phase_lock read A and M on);
+// w = (float)(p - floor(p)); out = P[i0] bit for bit when w == 0, else fl(a + fl(w fl(b1 - a))) with a = P[i0], b1 = P[i1] in
+// fp32, nothing contracted (-ffp-contract=off).  src_per_out == 1.0 is therefore a copy (clamped at the last source frame), and
+// n_clips = 1 resamples a whole plane.
 //
-// pg_phase_join.  Global frame g: k = min(g div sf, n_clips - 1), j = g - k sf.  k >= 1 and j < Vf: the frame is shared; with
-// a = ramp[Vf-1-j], b = ramp[j], lo = phi[k-1][j + sf], hi = phi[k][j]: zr = fl(fl(a cos lo) + fl(b cos hi)), zi likewise with sin,
-// out = atan2(zi, zr); zr == zi == 0 or either not finite: out = (b >= a ? hi : lo).  Every other frame is phi[k][j] bit for bit.
-// sin / cos / atan2 are pg_fastmath.h's (pg_sincos, pg_atan2): the unit vectors blended here are the ones pg_istft mode 0 forms
-// from the same angles, and ~85 VALU instructions per SHARED frame keep the kernel under its memory time (libm's: ~300).
+// pg_phase_join.  Which clips cover a global frame and where the crossfade reads them is pg_track.h's join, the code pg_stitch cuts
+// its samples by; only the blend differs.  A shared frame, with a = ramp[Vf-1-j], b = ramp[j], lo = phi[k-1][j + sf], hi = phi[k][j]:
+// zr = fl(fl(a cos lo) + fl(b cos hi)), zi likewise with sin, out = atan2(zi, zr); zr == zi == 0 or either not finite: out =
+// (b >= a ? hi : lo).  sin / cos / atan2 are pg_fastmath.h's (pg_sincos, pg_atan2): the unit vectors blended here are the ones
+// pg_istft mode 0 forms from the same angles, and ~85 VALU instructions per SHARED frame keep the kernel under its memory time
+// (libm's: ~300).
 //
 // Kernels.  Element-wise and memory-bound, no LDS.  A unit is 4 consecutive frames of one (clip or channel, bin) row, one thread per
-// unit; units are walked grid-stride by at most 8 workgroups per CU.  Where sf, frames, the row lengths, the strides and the pointers
-// allow (and, for pg_spec_clips, src_per_out == 1.0) a unit moves as 16-byte accesses: sf and Vf are then multiples of 4, so a unit
-// never straddles a clip boundary, the end of a shared region or the end of the source plane, and the reversed ramp
-// a = ramp[Vf-1-j-i] is the 16-byte load at Vf-4-j read backwards.  Otherwise the same unit is done frame by frame with the same
-// per-frame arithmetic: both paths give the same bits.  All index arithmetic is 64-bit.  Measurements: DESIGN.md section 4.10.
+// unit; units are walked grid-stride (pg_stream_grid).  Where sf, frames, the row lengths, the strides and the pointers allow (and,
+// for pg_spec_clips, src_per_out == 1.0) a unit moves as 16-byte accesses: sf and Vf are then multiples of 4, so a unit never
+// straddles a clip boundary, the end of a shared region or the end of the source plane.  Otherwise the same unit is done frame by
+// frame with the same per-frame arithmetic: both paths give the same bits.  All index arithmetic is 64-bit.  Measurements:
+// DESIGN.md section 4.10.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "phasegen.h"
 #include "pg_common.h"
+#include "pg_track.h"
 #include "pg_fastmath.h"
 
 namespace {
 
+namespace tk = pg_track;
 constexpr int SP_THREADS = 256;
-constexpr long SP_MAX_BLOCKS = 2048;       // 256 CUs x 8 workgroups
 
 struct ScKernelArgs {
     const float* P; float* out;
@@ -44,10 +47,9 @@ struct ScKernelArgs {
 
 // one output frame: global frame g of the source row `row`
 __device__ __forceinline__ float sc_one(const float* row, long g, double spo, long F_src) {
-    const double p = (double)g * spo, fl = floor(p);
-    const long i0 = fl < (double)F_src ? (long)fl : F_src - 1;        // (also for a p beyond the int64 range)
-    long i1 = i0 + 1;   if (i1 > F_src - 1) i1 = F_src - 1;
-    const float w = (float)(p - fl);
+    const double p = (double)g * spo;
+    const long i0 = tk::i0(g, spo, F_src), i1 = tk::i1(i0, F_src);
+    const float w = (float)(p - floor(p));
     const float a = row[i0];
     if (w == 0.0f) return a;
     const float d = row[i1] - a;
@@ -82,29 +84,21 @@ struct PjKernelArgs {
     int n_clips, bins, Vf;
 };
 
-__device__ __forceinline__ float pj_blend(float a, float b, float lo, float hi) {
-    float sl, cl, sh, ch;
-    pg_sincos(lo, sl, cl);
-    pg_sincos(hi, sh, ch);
-    const float zr = a * cl + b * ch, zi = a * sl + b * sh;
-    const bool finite = fabsf(zr) <= 3.402823466e+38f && fabsf(zi) <= 3.402823466e+38f;       // (false for NaN and inf)
-    if (!finite || (zr == 0.0f && zi == 0.0f)) return b >= a ? hi : lo;
-    return pg_atan2(zi, zr);
-}
-
-// one global frame g of the row whose clip 0 begins at `rp`
-__device__ __forceinline__ float pj_one(const PjKernelArgs& a, const float* rp, long g) {
-    long k = g / a.sf;
-    if (k > a.n_clips - 1) k = a.n_clips - 1;
-    const long j = g - k * a.sf;
-    const float* hp = rp + k * a.clip_stride + j;
-    const float hi = *hp;
-    if (k >= 1 && j < a.Vf) return pj_blend(a.ramp[a.Vf - 1 - j], a.ramp[j], hp[a.sf - a.clip_stride], hi);
-    return hi;
-}
+// the blend of a shared frame: the weighted circular mean of its two phases, the lower clip's term first
+struct pj_blend {
+    __device__ __forceinline__ float operator()(float a, float b, float lo, float hi) const {
+        float sl, cl, sh, ch;
+        pg_sincos(lo, sl, cl);
+        pg_sincos(hi, sh, ch);
+        const float zr = a * cl + b * ch, zi = a * sl + b * sh;
+        if (!(pg_finite(zr) && pg_finite(zi)) || (zr == 0.0f && zi == 0.0f)) return b >= a ? hi : lo;
+        return pg_atan2(zi, zr);
+    }
+};
 
 template <bool VEC>
 __global__ __launch_bounds__(SP_THREADS) void phase_join_kernel(const PjKernelArgs a) {
+    const tk::Join jn{a.ramp, a.sf, a.clip_stride, a.n_clips, a.Vf};
     const long stride = (long)gridDim.x * SP_THREADS;
     for (long u = (long)blockIdx.x * SP_THREADS + threadIdx.x; u < a.units; u += stride) {
         const long r = u / a.units_per_row, g = (u - r * a.units_per_row) * 4;          // r = c bins + b
@@ -112,31 +106,12 @@ __global__ __launch_bounds__(SP_THREADS) void phase_join_kernel(const PjKernelAr
         const float* rp = a.phi + c * a.ch_stride + b * a.row_pitch;
         float* op = a.out + r * a.F_out + g;
         if (VEC) {                                                // sf, Vf, F_out are multiples of 4
-            long k = g / a.sf;
-            if (k > a.n_clips - 1) k = a.n_clips - 1;
-            const long j = g - k * a.sf;
-            const float* hp = rp + k * a.clip_stride + j;
-            f32x4 v = *(const f32x4*)hp;
-            if (k >= 1 && j < a.Vf) {
-                const f32x4 lo = *(const f32x4*)(hp + (a.sf - a.clip_stride));
-                const f32x4 rb = *(const f32x4*)(a.ramp + j), ra = *(const f32x4*)(a.ramp + (a.Vf - 4 - j));
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = pj_blend(ra[3 - i], rb[i], lo[i], v[i]);
-            }
-            *(f32x4*)op = v;
+            *(f32x4*)op = tk::join_four(jn, rp, g, pj_blend());
         } else {
             const int n = a.F_out - g < 4 ? (int)(a.F_out - g) : 4;
-            for (int i = 0; i < n; ++i) op[i] = pj_one(a, rp, g + i);
+            for (int i = 0; i < n; ++i) op[i] = tk::join_one(jn, rp, g + i, pj_blend());
         }
     }
-}
-
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
-unsigned sp_grid(long units) {
-    long cap = (long)pg_cu_count() * 8; if (cap > SP_MAX_BLOCKS) cap = SP_MAX_BLOCKS; if (cap < 1) cap = 1;
-    long grid = (units + SP_THREADS - 1) / SP_THREADS;
-    return (unsigned)(grid > cap ? cap : grid);
 }
 
 }  // namespace
@@ -152,13 +127,13 @@ extern "C" int pg_spec_clips(const pg_spec_clips_args* a, void* stream) {
     if ((((uintptr_t)a->P) & 3) || (((uintptr_t)a->out) & 3)) return pg_fail(PG_ERR_ALIGN, "spec_clips: misaligned pointer");
     // (a stride that is never applied -- one channel -- does not decide)
     const bool wide = a->src_per_out == 1.0 && (a->sf & 3) == 0 && (a->frames & 3) == 0 && (a->F_src & 3) == 0
-                      && (a->n_ch == 1 || (a->p_stride & 3) == 0) && al16(a->P) && al16(a->out);
+                      && (a->n_ch == 1 || (a->p_stride & 3) == 0) && pg_al16(a->P) && pg_al16(a->out);
     ScKernelArgs k;
     k.P = a->P; k.out = a->out; k.src_per_out = a->src_per_out;
     k.p_stride = a->n_ch == 1 ? 0 : a->p_stride; k.F_src = a->F_src; k.sf = a->sf;
     k.units_per_row = ((long)a->frames + 3) / 4; k.units = k.units_per_row * rows;
     k.n_ch = a->n_ch; k.bins = a->bins; k.frames = a->frames;
-    const unsigned grid = sp_grid(k.units);
+    const unsigned grid = pg_stream_grid(k.units, SP_THREADS);
     hipStream_t st = (hipStream_t)stream;
     if (wide) hipLaunchKernelGGL(spec_clips_kernel<true>, dim3(grid), dim3(SP_THREADS), 0, st, k);
     else hipLaunchKernelGGL(spec_clips_kernel<false>, dim3(grid), dim3(SP_THREADS), 0, st, k);
@@ -181,14 +156,14 @@ extern "C" int pg_phase_join(const pg_phase_join_args* a, void* stream) {
     if ((((uintptr_t)a->phi) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->ramp) & 3)) return pg_fail(PG_ERR_ALIGN, "phase_join: misaligned pointer");
     const bool wide = (a->sf & 3) == 0 && (a->frames & 3) == 0 && (a->n_clips == 1 || (a->clip_stride & 3) == 0)
                       && (a->n_ch == 1 || (a->ch_stride & 3) == 0) && (a->bins == 1 || (a->row_pitch & 3) == 0)
-                      && al16(a->phi) && al16(a->out) && al16(a->ramp);
+                      && pg_al16(a->phi) && pg_al16(a->out) && pg_al16(a->ramp);
     PjKernelArgs k;
     k.phi = a->phi; k.out = a->out; k.ramp = a->ramp;
     k.clip_stride = a->clip_stride; k.ch_stride = a->n_ch == 1 ? 0 : a->ch_stride; k.row_pitch = a->bins == 1 ? 0 : a->row_pitch;
     k.F_out = F_out; k.sf = a->sf;
     k.units_per_row = (F_out + 3) / 4; k.units = k.units_per_row * rows;
     k.n_clips = a->n_clips; k.bins = a->bins; k.Vf = Vf;
-    const unsigned grid = sp_grid(k.units);
+    const unsigned grid = pg_stream_grid(k.units, SP_THREADS);
     hipStream_t st = (hipStream_t)stream;
     if (wide) hipLaunchKernelGGL(phase_join_kernel<true>, dim3(grid), dim3(SP_THREADS), 0, st, k);
     else hipLaunchKernelGGL(phase_join_kernel<false>, dim3(grid), dim3(SP_THREADS), 0, st, k);

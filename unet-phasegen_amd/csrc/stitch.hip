@@ -2,16 +2,14 @@
 // normalisation of utils.py:41-42 taken over the whole track instead of one clip.  Nothing in the reference does this (its demo.py
 // stops at clips of `frames` columns); the arithmetic below is the contract and the tests restate it in float64.
 //
-// Geometry.  Clip k of a track (T = clip_len samples) begins at output sample k step; V = T - step samples are shared with the
-// next clip, 0 <= 2 V <= T, so at most two clips cover a sample.  The output has n_out samples, (n_clips-1) step < n_out <=
-// (n_clips-1) step + T: the last clip may be cut short, the others are used whole.
+// Geometry and value.  Clip k of a track (T = clip_len samples) begins at output sample k step and shares V = T - step samples with
+// the next clip, 0 <= 2 V <= T; which clips cover a sample and where the crossfade reads them is pg_track.h's join (pg_phase_join
+// cuts its frames by the same code), and a sample covered twice is st_blend of the two under the ramp
+//     raw = (fl(a lo) + fl(b hi)) / fl(a + b)          fp32, no contraction (-ffp-contract=off), the lower clip's term first.
+// step == T therefore concatenates, and all-ones clips give all ones: (a + b) / (a + b).  The output has n_out samples,
+// (n_clips-1) step < n_out <= (n_clips-1) step + T: the last clip may be cut short, the others are used whole.
 // Ramp.  ramp[j] = float32(sin^2(pi (j + 0.5) / (2 V))), 0 <= j < V, evaluated in double on the HOST (pg_stitch_ramp) and handed
 // over as a device copy: strictly positive (2.3e-9 at V = 16384, a normal float), ramp[j] + ramp[V-1-j] within 2^-23 of 1.
-// Value.  For output sample t: k = min(t div step, n_clips-1), j = t - k step.  If k >= 1 and j < V the sample is covered twice;
-// with a = ramp[V-1-j], b = ramp[j], lo = clip[k-1][j + step], hi = clip[k][j]
-//     raw = (fl(a lo) + fl(b hi)) / fl(a + b)          fp32, no contraction (-ffp-contract=off), the lower clip's term first;
-// otherwise raw = clip[k][j] copied bit for bit (the head of clip 0 and the tail of the last clip are never faded).  step == T
-// therefore concatenates, and all-ones clips give all ones: (a + b) / (a + b).
 // Peak / finiteness.  n_nonfinite = number of NaN / +-inf output samples of all tracks, peak = max |raw| over the FINITE samples of
 // all tracks jointly (librosa.util.normalize(axis=None)); with normalize and peak > FLT_MIN, out = raw / peak.  A maximum and an
 // integer count are exact in any order, so the two-stage reduction (per-workgroup partials in `workspace`, then a second launch
@@ -19,22 +17,21 @@
 //
 // Kernel.  Element-wise and memory-bound: each clip sample is read once, each output written once (twice with normalize: the
 // second launch scales in place).  A unit is 4 consecutive samples of one track where step, T, the three strides and the four
-// pointers allow 16-byte accesses -- step and V are then multiples of 4, so a unit never straddles a clip boundary or the end of a
-// crossfade, and the reversed ramp a = ramp[V-1-j-i] is the 16-byte load at V-4-j read backwards -- and 1 sample otherwise; the
-// arithmetic per sample is the same, so both paths give the same bits.  The last unit of a row with n_out % 4 != 0 is done sample
-// by sample.  Units are walked grid-stride by at most 8 workgroups per CU (and never more than ST_MAX_BLOCKS, which sizes the
-// workspace on the host without asking a device).  All index arithmetic is 64-bit.  Measurements in DESIGN.md section 4.7.
+// pointers allow 16-byte accesses (join_four) and 1 sample otherwise (join_one); the arithmetic per sample is the same, so both
+// paths give the same bits.  The last unit of a row with n_out % 4 != 0 is done sample by sample.  Units are walked grid-stride
+// (pg_stream_grid, whose cap sizes the workspace on the host without asking a device).  All index arithmetic is 64-bit.
+// Measurements in DESIGN.md section 4.7.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include "phasegen.h"
 #include "pg_common.h"
+#include "pg_track.h"
 
 namespace {
 
 constexpr int ST_THREADS = 256;
-constexpr int ST_MAX_BLOCKS = 2048;        // 256 CUs x 8 workgroups: the most partials a call leaves in the workspace
 
 struct StPartial { float peak; int32_t bad; };
 
@@ -45,23 +42,14 @@ struct StKernelArgs {
     int n_clips, T, V, nparts, normalize;
 };
 
-__device__ __forceinline__ float st_blend(float a, float b, float lo, float hi) { return (a * lo + b * hi) / (a + b); }
+// the blend of a sample covered twice: fp32, nothing contracted, the lower clip's term first
+struct st_blend {
+    __device__ __forceinline__ float operator()(float a, float b, float lo, float hi) const { return (a * lo + b * hi) / (a + b); }
+};
 
 __device__ __forceinline__ void st_note(float v, float& peak, int& bad) {
-    const float m = fabsf(v);
-    if (m <= FLT_MAX) peak = fmaxf(peak, m);                      // (false for NaN and inf)
+    if (pg_finite(v)) peak = fmaxf(peak, fabsf(v));
     else ++bad;
-}
-
-// one output sample t of the track whose clips begin at `tr`
-__device__ __forceinline__ float st_one(const StKernelArgs& a, const float* tr, long t) {
-    long k = t / a.step;
-    if (k > a.n_clips - 1) k = a.n_clips - 1;
-    const long j = t - k * a.step;
-    const float* hp = tr + k * a.clip_stride + j;
-    const float hi = *hp;
-    if (k >= 1 && j < a.V) return st_blend(a.ramp[a.V - 1 - j], a.ramp[j], hp[a.step - a.clip_stride], hi);
-    return hi;
 }
 
 // block-wide maximum / sum through wave shuffles and 4 LDS slots; every thread gets the result
@@ -86,30 +74,21 @@ template <int VEC>
 __global__ __launch_bounds__(ST_THREADS) void stitch_kernel(const StKernelArgs a) {
     float peak = 0.f;
     int bad = 0;
+    const pg_track::Join jn{a.ramp, a.step, a.clip_stride, a.n_clips, a.V};
     const long stride = (long)gridDim.x * ST_THREADS;
     for (long u = (long)blockIdx.x * ST_THREADS + threadIdx.x; u < a.units; u += stride) {
         const long r = u / a.units_per_track, t = (u - r * a.units_per_track) * VEC;
         const float* tr = a.clips + r * a.track_stride;
         float* op = a.out + r * a.out_stride + t;
         if (VEC == 4 && t + 4 <= a.n_out) {
-            long k = t / a.step;
-            if (k > a.n_clips - 1) k = a.n_clips - 1;
-            const long j = t - k * a.step;
-            const float* hp = tr + k * a.clip_stride + j;
-            f32x4 v = *(const f32x4*)hp;
-            if (k >= 1 && j < a.V) {
-                const f32x4 lo = *(const f32x4*)(hp + (a.step - a.clip_stride));
-                const f32x4 b = *(const f32x4*)(a.ramp + j), ar = *(const f32x4*)(a.ramp + (a.V - 4 - j));
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = st_blend(ar[3 - i], b[i], lo[i], v[i]);
-            }
+            const f32x4 v = pg_track::join_four(jn, tr, t, st_blend());
             *(f32x4*)op = v;
 #pragma unroll
             for (int i = 0; i < 4; ++i) st_note(v[i], peak, bad);
         } else {
             const long n = VEC == 1 ? 1 : a.n_out - t;            // (a 16-byte row's last, short unit)
             for (long i = 0; i < n; ++i) {
-                const float v = st_one(a, tr, t + i);
+                const float v = pg_track::join_one(jn, tr, t + i, st_blend());
                 op[i] = v;
                 st_note(v, peak, bad);
             }
@@ -176,7 +155,7 @@ extern "C" int pg_stitch_ramp(float* ramp_host, int32_t overlap) {
 
 extern "C" int64_t pg_workspace_bytes_stitch(const pg_stitch_args* a) {
     if (int e = st_check(a)) return e;
-    return (int64_t)ST_MAX_BLOCKS * (int64_t)sizeof(StPartial);
+    return (int64_t)PG_STREAM_MAX_BLOCKS * (int64_t)sizeof(StPartial);      // the most partials a call leaves
 }
 
 extern "C" int pg_stitch(const pg_stitch_args* a, void* stream) {
@@ -192,11 +171,10 @@ extern "C" int pg_stitch(const pg_stitch_args* a, void* stream) {
     if (reduce && ((uintptr_t)a->workspace & 7)) return pg_fail(PG_ERR_ALIGN, "stitch: workspace must be 8-byte aligned");
     if (((uintptr_t)a->clips & 3) || ((uintptr_t)a->out & 3) || ((uintptr_t)a->ramp & 3) || ((uintptr_t)a->peak & 3) || ((uintptr_t)a->n_nonfinite & 3))
         return pg_fail(PG_ERR_ALIGN, "stitch: misaligned pointer");
-    auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
     // (a stride that is never applied -- one clip, one track -- does not decide)
     const bool wide = (a->step & 3) == 0 && (a->clip_len & 3) == 0 && (a->n_clips == 1 || (a->clip_stride & 3) == 0)
                       && (a->n_tracks == 1 || ((a->track_stride & 3) == 0 && (a->out_stride & 3) == 0))
-                      && al16(a->clips) && al16(a->out) && (V == 0 || al16(a->ramp));
+                      && pg_al16(a->clips) && pg_al16(a->out) && (V == 0 || pg_al16(a->ramp));
     StKernelArgs k;
     k.clips = a->clips; k.out = a->out; k.ramp = a->ramp; k.partial = reduce ? (StPartial*)a->workspace : nullptr;
     k.peak = a->peak; k.n_nonfinite = a->n_nonfinite;
@@ -205,16 +183,15 @@ extern "C" int pg_stitch(const pg_stitch_args* a, void* stream) {
     k.units_per_track = wide ? (a->n_out + 3) / 4 : a->n_out;
     k.units = k.units_per_track * a->n_tracks;
     k.n_clips = a->n_clips; k.T = a->clip_len; k.V = V; k.normalize = a->normalize ? 1 : 0;
-    long cap = (long)pg_cu_count() * 8; if (cap > ST_MAX_BLOCKS) cap = ST_MAX_BLOCKS;
-    long grid = (k.units + ST_THREADS - 1) / ST_THREADS; if (grid > cap) grid = cap;
+    const unsigned grid = pg_stream_grid(k.units, ST_THREADS);
     k.nparts = (int)grid;
     hipStream_t st = (hipStream_t)stream;
-    if (wide) hipLaunchKernelGGL(stitch_kernel<4>, dim3((unsigned)grid), dim3(ST_THREADS), 0, st, k);
-    else hipLaunchKernelGGL(stitch_kernel<1>, dim3((unsigned)grid), dim3(ST_THREADS), 0, st, k);
+    if (wide) hipLaunchKernelGGL(stitch_kernel<4>, dim3(grid), dim3(ST_THREADS), 0, st, k);
+    else hipLaunchKernelGGL(stitch_kernel<1>, dim3(grid), dim3(ST_THREADS), 0, st, k);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return pg_fail((int)e, "stitch launch failed");
     if (reduce) {
-        const unsigned g2 = k.normalize ? (unsigned)grid : 1u;
+        const unsigned g2 = k.normalize ? grid : 1u;
         if (wide) hipLaunchKernelGGL(stitch_finish_kernel<4>, dim3(g2), dim3(ST_THREADS), 0, st, k);
         else hipLaunchKernelGGL(stitch_finish_kernel<1>, dim3(g2), dim3(ST_THREADS), 0, st, k);
         e = hipGetLastError();

@@ -2,17 +2,15 @@
 // standard comparator of every time-stretch method.  Each bin's analysis phase is propagated along the OUTPUT frame grid by the
 // frame-to-frame advance measured on the SOURCE grid at the output frame's position (librosa.phase_vocoder's recurrence); a bin that
 // falls below a magnitude floor takes its analysis phase back (the transient / silence reset).  The reference has no counterpart; the
-// arithmetic below is the contract (include/phasegen.h states it) and tests/_vocoder_ref.py restates it in numpy, bit for bit.
+// arithmetic is the contract (include/phasegen.h states it) and tests/_vocoder_ref.py restates it in numpy, bit for bit.
 //
-// Phase on a wrap-around grid.  Phase matters modulo 2 pi only, so it is kept as a 32-bit unsigned fraction of a turn:
-//   q(x) = 0 when x is not finite or |x| > 2^20, else (uint32)(int64) rint((double)x * K),  K = 2^32 / TWO_PI
-// Integer addition wraps and is associative, so the scan along time is EXACT in any order: the result cannot depend on the grid, the
-// chunking or the wave size.  For output frame g of a row: p = (double)g * src_per_out, i0 = min((int64)floor(p), F_src - 1),
-// i1 = min(i0 + 1, F_src - 1) (pg_spec_clips's positions), and
+// The phase grid q() / angle() and the positions i0(g), i1(g) are pg_track.h's.  Phase matters modulo 2 pi only and is kept as a
+// 32-bit unsigned fraction of a turn: integer addition wraps and is associative, so the scan along time is EXACT in any order and
+// the result cannot depend on the grid, the chunking or the wave size.
 //   delta[g] = q(A[i1]) - q(A[i0])                            (uint32: the wrap IS the principal value of the advance)
 //   reset[g] = g == 0 || (M != NULL && M[i0] < reset_below)
 //   acc[g]   = reset[g] ? q(A[i0]) : acc[g-1] + delta[g-1]    (uint32)
-//   out[g]   = (float)((double)(int32)acc[g] * R),            R = TWO_PI / 2^32
+//   out[g]   = angle(acc[g])
 //
 // Kernel.  One 256-thread workgroup per (channel, bin) row (rows are walked grid-stride), the row in chunks of 1024 output frames, 4
 // consecutive frames per thread.  Element g of the scan is the pair (reset[g], reset[g] ? q(A[i0(g)]) : delta[g-1]) and the operator
@@ -26,15 +24,15 @@
 #include <stdint.h>
 #include "phasegen.h"
 #include "pg_common.h"
+#include "pg_track.h"
 
 namespace {
 
+namespace tk = pg_track;
 constexpr int PV_THREADS = 256;
 constexpr int PV_PER_THREAD = 4;
 constexpr int PV_CHUNK = PV_THREADS * PV_PER_THREAD;      // 1024 output frames
 constexpr int PV_WAVES = PV_THREADS / 64;
-constexpr double PV_TWO_PI = 6.283185307179586;
-constexpr long PV_MAX_BLOCKS = 2048;                        // 256 CUs x 8 workgroups
 
 struct PvKernelArgs {
     const float* A; const float* M; float* out;
@@ -43,24 +41,6 @@ struct PvKernelArgs {
     int bins;
     float reset_below;
 };
-
-__device__ __forceinline__ uint32_t pv_q(float x) {
-    if (!(fabsf(x) <= 1048576.0f)) return 0u;               // NaN, +-inf and |x| > 2^20
-    const double K = 4294967296.0 / PV_TWO_PI;
-    return (uint32_t)(int64_t)rint((double)x * K);
-}
-
-// i0 of output frame g (>= 0)
-__device__ __forceinline__ long pv_i0(long g, double spo, long F_src) {
-    const double fl = floor((double)g * spo);
-    return fl < (double)F_src ? (long)fl : F_src - 1;        // (also for a position beyond the int64 range)
-}
-
-
-__device__ __forceinline__ float pv_angle(uint32_t acc) {
-    const double R = PV_TWO_PI / 4294967296.0;
-    return (float)((double)(int32_t)acc * R);
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(PV_THREADS) void phase_vocoder_kernel(const PvKernelArgs a) {
@@ -86,8 +66,8 @@ __global__ __launch_bounds__(PV_THREADS) void phase_vocoder_kernel(const PvKerne
             for (int j = 0; j <= PV_PER_THREAD; ++j) {
                 long g = g0 - 1 + j;
                 g = g < 0 ? 0 : (g < a.F_out ? g : a.F_out - 1);
-                i0[j] = pv_i0(g, a.src_per_out, a.F_src);
-                q0[j] = pv_q(ar[i0[j]]);
+                i0[j] = tk::i0(g, a.src_per_out, a.F_src);
+                q0[j] = tk::q(ar[i0[j]]);
             }
             uint32_t v[PV_PER_THREAD];
             bool f[PV_PER_THREAD];
@@ -102,8 +82,8 @@ __global__ __launch_bounds__(PV_THREADS) void phase_vocoder_kernel(const PvKerne
                     ef = g == 0 || (mr != nullptr && mr[i0[i + 1]] < a.reset_below);
                     if (ef) ev = q0[i + 1];
                     else {
-                        const long j1 = i0[i] + 1 < a.F_src ? i0[i] + 1 : a.F_src - 1;
-                        ev = (j1 == i0[i + 1] ? q0[i + 1] : pv_q(ar[j1])) - q0[i];
+                        const long j1 = tk::i1(i0[i], a.F_src);
+                        ev = (j1 == i0[i + 1] ? q0[i + 1] : tk::q(ar[j1])) - q0[i];
                     }
                 }
                 tv = ef ? ev : tv + ev;
@@ -137,12 +117,12 @@ __global__ __launch_bounds__(PV_THREADS) void phase_vocoder_kernel(const PvKerne
                 if (VEC) {                                    // F_out % 4 == 0: the unit is whole and 16-byte aligned
                     f32x4 o;
 #pragma unroll
-                    for (int i = 0; i < PV_PER_THREAD; ++i) o[i] = pv_angle(f[i] ? v[i] : pre + v[i]);
+                    for (int i = 0; i < PV_PER_THREAD; ++i) o[i] = tk::angle(f[i] ? v[i] : pre + v[i]);
                     *(f32x4*)(orow + g0) = o;
                 } else {
 #pragma unroll
                     for (int i = 0; i < PV_PER_THREAD; ++i)
-                        if (g0 + i < a.F_out) orow[g0 + i] = pv_angle(f[i] ? v[i] : pre + v[i]);
+                        if (g0 + i < a.F_out) orow[g0 + i] = tk::angle(f[i] ? v[i] : pre + v[i]);
                 }
             }
         }
@@ -155,25 +135,11 @@ __global__ __launch_bounds__(PV_THREADS) void phase_vocoder_kernel(const PvKerne
 }  // namespace
 
 extern "C" int pg_phase_vocoder(const pg_phase_vocoder_args* a, void* stream) {
-    if (!a || !a->A || !a->out) return pg_fail(PG_ERR_NULL, "phase_vocoder: args, A and out required");
-    if (a->n_ch <= 0 || a->bins <= 0 || a->F_src <= 0 || a->F_out <= 0) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: non-positive dimension");
-    if (!(a->src_per_out > 0.0) || !(a->src_per_out <= 1.7976931348623157e308)) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: src_per_out must be finite and positive");
-    if (!(a->reset_below >= 0.0f) || !(a->reset_below <= 3.402823466e+38f)) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: reset_below must be finite and not negative");
-    if (a->F_src > INT64_MAX / 2 / a->bins) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: plane beyond 2^62 elements");
-    if (a->a_stride < (int64_t)a->bins * a->F_src) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: a_stride shorter than a plane");
-    if (a->M && a->m_stride < (int64_t)a->bins * a->F_src) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: m_stride shorter than a plane");
-    const int64_t rows = (int64_t)a->n_ch * a->bins;
-    if (rows > INT64_MAX / 2 / a->F_out) return pg_fail(PG_ERR_SHAPE, "phase_vocoder: output beyond 2^62 elements");
-    if ((((uintptr_t)a->A) & 3) || (((uintptr_t)a->M) & 3) || (((uintptr_t)a->out) & 3)) return pg_fail(PG_ERR_ALIGN, "phase_vocoder: misaligned pointer");
-    const bool wide = (a->F_out & 3) == 0 && (((uintptr_t)a->out) & 15) == 0;
     PvKernelArgs k;
-    k.A = a->A; k.M = a->M; k.out = a->out;
-    k.src_per_out = a->src_per_out;
-    k.a_stride = a->n_ch == 1 ? 0 : a->a_stride; k.m_stride = a->n_ch == 1 ? 0 : a->m_stride;
-    k.F_src = a->F_src; k.F_out = a->F_out; k.rows = rows;
-    k.bins = a->bins; k.reset_below = a->reset_below;
-    long cap = (long)pg_cu_count() * 8; if (cap > PV_MAX_BLOCKS) cap = PV_MAX_BLOCKS; if (cap < 1) cap = 1;
-    const unsigned grid = (unsigned)(rows > cap ? cap : rows);
+    bool wide;
+    if (int e = pg_stretch_check("phase_vocoder", false, INT32_MAX, a, k, wide)) return e;
+    k.rows = (long)a->n_ch * a->bins;
+    const unsigned grid = pg_stream_grid(k.rows, 1);          // a workgroup per row
     hipStream_t st = (hipStream_t)stream;
     if (wide) hipLaunchKernelGGL(phase_vocoder_kernel<true>, dim3(grid), dim3(PV_THREADS), 0, st, k);
     else hipLaunchKernelGGL(phase_vocoder_kernel<false>, dim3(grid), dim3(PV_THREADS), 0, st, k);

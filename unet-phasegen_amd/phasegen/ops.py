@@ -703,6 +703,21 @@ def stft_crops_describe(*args, **kw):
     return _describe(_lib.load().pg_stft_crops_describe, a, "stft_crops_describe")
 
 
+def _out(out, want, device, who, rows=False):
+    """The ``out=`` argument of a wrapper: None -> a new float32 tensor shaped ``want``, else ``out`` itself, which must be shaped
+    ``want``.  ``rows``: the wrapper takes a row stride, so ``out`` must be a float32 device tensor with contiguous rows (the other
+    wrappers hand it to ``_dense``, which checks the rest)."""
+    if out is None:
+        return torch.empty(want, device=device, dtype=torch.float32)
+    if rows:
+        if not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == want and (want[-1] == 1 or out.stride(-1) == 1)):
+            raise ValueError(f"{who}: out must be a float32 device tensor of shape {want} with contiguous rows")
+        _on_current_device(out, "out")
+    elif tuple(out.shape) != want:
+        raise ValueError(f"{who}: out must be {want}, got {tuple(out.shape)}")
+    return out
+
+
 _RES_TYPES = {"kaiser_best": _lib.RS_KAISER_BEST, "kaiser_fast": _lib.RS_KAISER_FAST,
               _lib.RS_KAISER_BEST: _lib.RS_KAISER_BEST, _lib.RS_KAISER_FAST: _lib.RS_KAISER_FAST}
 _resample_banks = {}     # (U, D, quality, device) -> device copy of pg_resample_bank's output (read-only; at most 226 KB each)
@@ -752,12 +767,7 @@ def resample(x, orig_sr, target_sr, res_type="kaiser_best", out=None):
     if n_out < 0:
         _lib.check(int(n_out), "resample_out_len")
     want = (n_out,) if x.dim() == 1 else (n_sig, n_out)
-    if out is None:
-        out = torch.empty(want, device=x.device, dtype=torch.float32)
-    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == want and (n_out == 1 or out.stride(-1) == 1)):
-        raise ValueError(f"resample: out must be a float32 device tensor of shape {want} with contiguous rows")
-    else:
-        _on_current_device(out, "out")
+    out = _out(out, want, x.device, "resample", rows=True)
     o2 = out[None] if out.dim() == 1 else out
     quality = _RES_TYPES[res_type]
     a = _lib.ResampleArgs()
@@ -815,12 +825,7 @@ def stitch(clips, step, n_out, normalize=False, out=None, return_status=False):
     if clip_stride < T or track_stride < 0:
         raise ValueError(f"stitch: clips overlap in memory (strides {clips.stride()})")
     want = (n_out,) if clips.dim() == 2 else (n_tracks, n_out)
-    if out is None:
-        out = torch.empty(want, device=clips.device, dtype=torch.float32)
-    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == want and (n_out == 1 or out.stride(-1) == 1)):
-        raise ValueError(f"stitch: out must be a float32 device tensor of shape {want} with contiguous rows")
-    else:
-        _on_current_device(out, "out")
+    out = _out(out, want, clips.device, "stitch", rows=True)
     o2 = out[None] if out.dim() == 1 else out
     out_stride = o2.stride(0) if n_tracks > 1 else n_out
     if out_stride < n_out:
@@ -863,11 +868,7 @@ def spec_clips(plane, n_clips, frames, sf, src_per_out=1.0, out=None):
     p_stride = plane.stride(0) if n_ch > 1 else bins * F_src
     if p_stride < bins * F_src:
         raise ValueError(f"spec_clips: channels overlap in memory (strides {plane.stride()})")
-    want = (n_clips, n_ch, bins, frames)
-    if out is None:
-        out = torch.empty(want, device=plane.device, dtype=torch.float32)
-    elif tuple(out.shape) != want:
-        raise ValueError(f"spec_clips: out must be {want}, got {tuple(out.shape)}")
+    out = _out(out, (n_clips, n_ch, bins, frames), plane.device, "spec_clips")
     a = _lib.SpecClipsArgs()
     a.n_clips, a.n_ch, a.bins, a.frames, a.sf, a.F_src, a.src_per_out = n_clips, n_ch, bins, frames, sf, F_src, src_per_out
     a.P, a.p_stride, a.out = plane.data_ptr(), p_stride, _dense(out, "out")
@@ -900,11 +901,7 @@ def phase_join(phi, sf, ramp=None, out=None):
     if row_pitch < frames or ch_stride < plane or clip_stride < plane:
         raise ValueError(f"phase_join: rows overlap in memory (strides {phi.stride()})")
     F_out = (n_clips - 1) * sf + frames
-    want = (n_ch, bins, F_out)
-    if out is None:
-        out = torch.empty(want, device=phi.device, dtype=torch.float32)
-    elif tuple(out.shape) != want:
-        raise ValueError(f"phase_join: out must be {want}, got {tuple(out.shape)}")
+    out = _out(out, (n_ch, bins, F_out), phi.device, "phase_join")
     if ramp is None:
         ramp = _stitch_ramp(Vf, phi.device)
     elif tuple(ramp.shape) != (Vf,):
@@ -936,6 +933,28 @@ def _vocoder_plane(t, name, shape=None, who="phase_vocoder"):
     return stride
 
 
+def _stretch_args(a, who, angle, F_out, src_per_out, logmag, reset_below, out):
+    """Checks the arguments ``phase_vocoder`` and ``phase_lock`` share and fills the fields PhaseLockArgs has in common with
+    PhaseVocoderArgs (everything but the workspace) -> ``out``, allocated when None."""
+    a_stride = _vocoder_plane(angle, "angle", who=who)
+    n_ch, bins, F_src = angle.shape
+    F_out, src_per_out, reset_below = int(F_out), float(src_per_out), float(reset_below)
+    if F_out < 1:
+        raise ValueError(f"{who}: F_out must be positive, got {F_out}")
+    if not 0.0 < src_per_out < float("inf"):
+        raise ValueError(f"{who}: src_per_out must be finite and positive, got {src_per_out}")
+    if not 0.0 <= reset_below < float("inf"):
+        raise ValueError(f"{who}: reset_below must be finite and not negative, got {reset_below}")
+    if logmag is not None:
+        a.m_stride = _vocoder_plane(logmag, "logmag", angle.shape, who=who)
+        a.M = logmag.data_ptr()
+    out = _out(out, (n_ch, bins, F_out), angle.device, who)
+    a.n_ch, a.bins, a.F_src, a.F_out, a.src_per_out, a.reset_below = n_ch, bins, F_src, F_out, src_per_out, reset_below
+    a.A, a.a_stride = angle.data_ptr(), a_stride
+    a.out = _dense(out, "out")
+    return out
+
+
 def phase_vocoder(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=None):
     """The phase-vocoder phase of a time-stretched spectrogram (pg_phase_vocoder): angle (n_ch, bins, F_src) float32 on the device,
     frames contiguous, rows F_src apart, the channel stride free (``pol[:, 1]`` of a (n_ch, 2, bins, F) polar tensor is read in place)
@@ -944,27 +963,8 @@ def phase_vocoder(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, o
     exactly on a 2^32 grid of the turn.  ``logmag`` (same shape, ``pol[:, 0]``) and ``reset_below``: a frame whose log-magnitude is
     below the floor takes the analysis phase itself (the transient / silence reset); without either nothing resets after frame 0.
     src_per_out == 1.0 returns the analysis phase (to 2 pi / 2^33 and one rounding)."""
-    a_stride = _vocoder_plane(angle, "angle")
-    n_ch, bins, F_src = angle.shape
-    F_out, src_per_out, reset_below = int(F_out), float(src_per_out), float(reset_below)
-    if F_out < 1:
-        raise ValueError(f"phase_vocoder: F_out must be positive, got {F_out}")
-    if not 0.0 < src_per_out < float("inf"):
-        raise ValueError(f"phase_vocoder: src_per_out must be finite and positive, got {src_per_out}")
-    if not 0.0 <= reset_below < float("inf"):
-        raise ValueError(f"phase_vocoder: reset_below must be finite and not negative, got {reset_below}")
-    m_stride = _vocoder_plane(logmag, "logmag", angle.shape) if logmag is not None else 0
-    want = (n_ch, bins, F_out)
-    if out is None:
-        out = torch.empty(want, device=angle.device, dtype=torch.float32)
-    elif tuple(out.shape) != want:
-        raise ValueError(f"phase_vocoder: out must be {want}, got {tuple(out.shape)}")
     a = _lib.PhaseVocoderArgs()
-    a.n_ch, a.bins, a.F_src, a.F_out, a.src_per_out, a.reset_below = n_ch, bins, F_src, F_out, src_per_out, reset_below
-    a.A, a.a_stride = angle.data_ptr(), a_stride
-    if logmag is not None:
-        a.M, a.m_stride = logmag.data_ptr(), m_stride
-    a.out = _dense(out, "out")
+    out = _stretch_args(a, "phase_vocoder", angle, F_out, src_per_out, logmag, reset_below, out)
     _lib.check(_lib.load().pg_phase_vocoder(C.byref(a), _stream()), "phase_vocoder")
     return out
 
@@ -983,25 +983,8 @@ def phase_lock(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=
     phase.  Exact on a 2^32 grid of the turn, like ``phase_vocoder``; src_per_out == 1.0 returns the analysis phase."""
     if logmag is None:
         raise ValueError("phase_lock: logmag is required (the peaks are those of the log-magnitude)")
-    a_stride = _vocoder_plane(angle, "angle", who="phase_lock")
-    n_ch, bins, F_src = angle.shape
-    F_out, src_per_out, reset_below = int(F_out), float(src_per_out), float(reset_below)
-    if F_out < 1:
-        raise ValueError(f"phase_lock: F_out must be positive, got {F_out}")
-    if not 0.0 < src_per_out < float("inf"):
-        raise ValueError(f"phase_lock: src_per_out must be finite and positive, got {src_per_out}")
-    if not 0.0 <= reset_below < float("inf"):
-        raise ValueError(f"phase_lock: reset_below must be finite and not negative, got {reset_below}")
-    m_stride = _vocoder_plane(logmag, "logmag", angle.shape, who="phase_lock")
-    want = (n_ch, bins, F_out)
-    if out is None:
-        out = torch.empty(want, device=angle.device, dtype=torch.float32)
-    elif tuple(out.shape) != want:
-        raise ValueError(f"phase_lock: out must be {want}, got {tuple(out.shape)}")
     a = _lib.PhaseLockArgs()
-    a.n_ch, a.bins, a.F_src, a.F_out, a.src_per_out, a.reset_below = n_ch, bins, F_src, F_out, src_per_out, reset_below
-    a.A, a.a_stride, a.M, a.m_stride = angle.data_ptr(), a_stride, logmag.data_ptr(), m_stride
-    a.out = _dense(out, "out")
+    out = _stretch_args(a, "phase_lock", angle, F_out, src_per_out, logmag, reset_below, out)
     lib = _lib.load()
     a.workspace, a.workspace_bytes = _workspace(_lock_ws, angle.device, lib.pg_workspace_bytes_phase_lock(C.byref(a)), "workspace_bytes_phase_lock")
     _lib.check(lib.pg_phase_lock(C.byref(a), _stream()), "phase_lock")
