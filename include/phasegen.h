@@ -527,6 +527,49 @@ typedef struct pg_phase_lock_args {
 int64_t pg_workspace_bytes_phase_lock(const pg_phase_lock_args* a);   /* host function of n_ch, bins, F_out; negative = error code */
 int     pg_phase_lock(const pg_phase_lock_args* a, void* stream);
 
+/* pg_phase_spsi: a phase from the magnitudes ALONE, in one pass (single-pass spectrogram inversion; Beauregard, Harish & Wyse 2015;
+ * phasegen/track.py, phase="spsi"): the peaks of every frame advance by their interpolated frequency and every other bin follows its
+ * peak.  No analysis phase, no weights, no iteration: the comparator a predicted phase has to beat, and the only one that uses
+ * nothing a stretched spectrogram does not have.  Struct of its own, PG_VERSION unchanged; the reference has no counterpart; the
+ * arithmetic below is the contract.
+ *   M: the log-magnitude plane (n_ch, bins, F) fp32 ON THE OUTPUT GRID (no time mapping here), frames fastest, channels m_stride >=
+ *   bins F elements apart (pol[:, 0] of a polar tensor by pointer and stride).  n_fft, hop: 1 <= hop <= n_fft.  bin0: the FFT bin of
+ *   row 0 (1 for the project's DC-dropped planes), 0 <= bin0 <= 65536.  -> out (n_ch, bins, F), dense fp32.
+ *   Per channel, with m_g[b] = M[b][g]:
+ *   Peaks and regions.  The peaks of frame g and P_g(b) are pg_phase_lock's, word for word: PG_LOCK_REACH, the plateau rule, NaN,
+ *   and P_g(b) = b in a frame without any peak.
+ *   Offset of p = P_g(b), in fp32, nothing contracted, one IEEE division: alpha = m_g[p-1], beta = m_g[p], gamma = m_g[p+1],
+ *     d = fl(fl(alpha - beta) + fl(gamma - beta)),  n = 0.5f * fl(alpha - gamma),
+ *     delta = n / d if 0 < p < bins - 1 and d < 0, otherwise 0; and if not (|delta| <= 0.5), which covers NaN, delta = 0.
+ *   Advance, in double: x = ((double)(p + bin0) + (double)delta) * ((double)hop / (double)n_fft),
+ *     adv_g[p] = (uint32)(int64) rint(x * 4294967296.0)             round half to even, two's-complement wrap
+ *   Scan (uint32, wrapping).  Theta_0[b] = 0.  For g >= 1: Theta_g[b] = Theta_{g-1}[P_g(b)] + adv_g[P_g(b)].
+ *   Output.  out[b][g] = (float)((double)(int32)(Theta_g[b] + (((b + bin0) & 1) << 31)) * R), R as in pg_phase_vocoder.  The half turn
+ *   on odd FFT bins is the (-1)^k of a Hann window that starts at the frame's first sample (the project's and librosa's centred
+ *   framing).  Theta carries no parity, so a peak that moves to the next bin continues without a jump.
+ *   Consequences.  A plane whose columns are all equal gives Theta_g[b] = g adv[P(b)] exactly.  A channel's result does not depend
+ *   on n_ch, on its position, or on how the scan is split (frame g is a gather map, as in pg_phase_lock).  There is no reset_below.
+ *   Kernels: pg_phase_lock's three launches (compose, carry, apply; chunks of 32 frames) over another frame source: the staged
+ *   window holds the one plane, twice as wide in the same LDS, and is reloaded every window's width of frames; the advance is
+ *   formed from the frame's magnitudes in LDS.  16-byte stores where out and F allow, frame by frame otherwise (same bits).
+ *   workspace: pg_workspace_bytes_phase_spsi() bytes = 12 n_ch bins ceil(F / 32), as pg_phase_lock's.  The library allocates
+ *   nothing and keeps nothing.
+ *   Errors (host side, before any launch, in this order): NULL args / M / out PG_ERR_NULL; non-positive sizes, bins > 4096, hop or
+ *   n_fft outside 1 <= hop <= n_fft, bin0 outside [0, 65536], a plane or output beyond 2^62 elements, m_stride < bins F
+ *   PG_ERR_SHAPE; M, out or workspace not 4-byte aligned PG_ERR_ALIGN; workspace NULL or smaller than the query's answer
+ *   PG_ERR_WORKSPACE. */
+typedef struct pg_phase_spsi_args {
+    int32_t n_ch, bins;                          /* bins <= 4096                                                        */
+    int64_t F;                                   /* frames per row of M and of out                                      */
+    int32_t n_fft, hop;                          /* 1 <= hop <= n_fft                                                   */
+    int32_t bin0, _pad0;                         /* FFT bin of row 0; 0 <= bin0 <= 65536                                */
+    const float* M; int64_t m_stride;            /* (n_ch, bins, F), channels m_stride >= bins F elements apart         */
+    float* out;                                  /* (n_ch, bins, F), dense                                              */
+    void* workspace; int64_t workspace_bytes;
+} pg_phase_spsi_args;                            /* 72 bytes */
+int64_t pg_workspace_bytes_phase_spsi(const pg_phase_spsi_args* a);   /* host function of n_ch, bins, F; negative = error code */
+int     pg_phase_spsi(const pg_phase_spsi_args* a, void* stream);
+
 /* How far a reconstruction is from its source, reduced on the device: the sums from which SI-SDR / SNR (waveforms) and spectral
  * convergence / log-spectral distance (spectrograms) are formed on the host (phasegen/metrics.py).  The reference has no counterpart
  * (validate.py takes mean absolute waveform errors of three dataset clips on the host); the arithmetic below is the contract.

@@ -4,6 +4,11 @@
 // phase relations inside a lobe survive the stretch.  The reference has no counterpart; the arithmetic is the contract
 // (include/phasegen.h states it) and tests/_lock_ref.py restates it in numpy, bit for bit.
 //
+// pg_phase_spsi (single-pass spectrogram inversion; phase="spsi") is a second recurrence of the same shape and runs on the same
+// scan: the peaks, the regions and the three launches below are its too, only the frame source differs -- it reads M alone, on the
+// output grid itself, and a peak advances by its interpolated frequency instead of by a measured phase difference (LockSrc /
+// SpsiSrc below; tests/_spsi_ref.py).  What follows describes pg_phase_lock; where pg_phase_spsi differs the sources say so.
+//
 // The recurrence (q(), angle(), i0(g), i1(g) and the advance into frame g are pg_track.h's, shared with vocoder.hip).  Per channel,
 // T_g[b] (uint32, a fraction of a turn) is the rotation of bin b at output frame g against its analysis
 // phase: T_0 = 0 and T_g[b] = reset ? 0 : T_{g-1}[p] + e_g[p] with p = P_g(b) the peak bin b belongs to, e_g[p] = q(A[p][i1(g-1)]) -
@@ -63,9 +68,12 @@ struct LkArgs {
     int bins, nb;                                           // nb = BPT * blockDim.x >= bins
     int wt_compose, wt_apply;                               // source frames in the staged window of either kernel (a power of two; 0: none)
     float reset_below;
+    int bin0;                                               // SpsiSrc only: the FFT bin of row 0, and hop / n_fft in double
+    double hop_per_fft;
 };
 
-// what a thread reads of frame g for its bins: the magnitude, the quantised analysis phase and the advance e_g
+// what a thread reads of frame g for its bins: the magnitude, the quantised analysis phase and the advance e_g (SpsiSrc: qa is
+// the half turn of an odd FFT bin, and e is not known yet)
 template <int BPT>
 struct LkFrame { float m[BPT]; uint32_t qa[BPT]; uint32_t e[BPT]; };
 
@@ -130,6 +138,69 @@ __device__ __forceinline__ void lk_fetch(const LkArgs& a, const float* Ac, const
     }
 }
 
+// ---- The frame source.  The scan -- regions, compose, carry, apply -- is ONE piece of code over T_g[b] = T_{g-1}[P_g(b)] + c_g[P_g(b)];
+// a frame source says where frame g's magnitudes come from (fetch: f.m), how the advance of a peak is formed (EARLY: f.e, known
+// when the frame is fetched; otherwise advance(), from the frame's magnitudes in LDS after the first barrier of the region step),
+// when a region starts again from zero (reset) and what is added at the output (f.qa).  PLANES: planes in the staged window.
+
+// pg_phase_lock: the stretched time grid over M and q(A); the advance is measured on A; a quiet peak resets; q(A) is added.
+struct LockSrc {
+    static constexpr int PLANES = 2;
+    static constexpr bool EARLY = true;
+    template <int BPT>
+    static __device__ __forceinline__ void fetch(const LkArgs& a, const float* Ac, const float* Mc, long g, uint32_t* win, int wt, long& ws0,
+                                                 LkFrame<BPT>& f) { lk_fetch<BPT>(a, Ac, Mc, g, win, wt, ws0, f); }
+    static __device__ __forceinline__ uint32_t advance(const LkArgs&, const uint32_t*, int) { return 0u; }
+    static __device__ __forceinline__ bool reset(const LkArgs& a, long g, const uint32_t* msf, int p) {
+        return g == 0 || __uint_as_float(msf[p]) < a.reset_below;
+    }
+};
+
+// pg_phase_spsi: M on the output grid itself (frame g is column g; no A); the advance of bin p is its interpolated frequency times
+// hop / n_fft of a turn (include/phasegen.h: the offset in fp32 with one IEEE division, the advance in double); only frame 0
+// resets; the half turn of the odd FFT bins is added.
+struct SpsiSrc {
+    static constexpr int PLANES = 1;
+    static constexpr bool EARLY = false;
+    // The window holds frames [g - g % wt, + wt) of the one plane: wt divides LK_CHUNK and chunks begin on multiples of it, so it
+    // is reloaded every wt frames whatever the data.  (Every wave has left the previous window's reads two barriers behind.)
+    template <int BPT>
+    static __device__ __forceinline__ void fetch(const LkArgs& a, const float*, const float* Mc, long g, uint32_t* win, int wt, long&,
+                                                 LkFrame<BPT>& f) {
+        const int tid = threadIdx.x, nt = blockDim.x, pitch = wt + 1, k = wt ? (int)(g & (long)(wt - 1)) : 0;
+        if (wt && k == 0) {
+            const int shift = __builtin_ctz((unsigned)wt), n = a.bins << shift;
+            for (int e = tid; e < n; e += nt) {
+                const int r = e >> shift, kk = e & (wt - 1);
+                if (g + kk < a.F_src) win[r * pitch + kk] = __float_as_uint(Mc[(long)r * a.F_src + g + kk]);
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int j = 0; j < BPT; ++j) {
+            const int b = tid + j * nt;
+            f.m[j] = __uint_as_float(0x7fc00000u);
+            f.qa[j] = (uint32_t)((b + a.bin0) & 1) << 31;
+            f.e[j] = 0u;
+            if (b < a.bins) f.m[j] = wt ? __uint_as_float(win[b * pitch + k]) : Mc[(long)b * a.F_src + g];
+        }
+    }
+    // ms: the frame's magnitudes (bins past the end are NaN and never asked for)
+    static __device__ __forceinline__ uint32_t advance(const LkArgs& a, const uint32_t* ms, int p) {
+        float delta = 0.0f;
+        if (p > 0 && p < a.bins - 1) {
+            const float al = __uint_as_float(ms[p - 1]), be = __uint_as_float(ms[p]), ga = __uint_as_float(ms[p + 1]);
+            const float d = (al - be) + (ga - be);
+            const float n = 0.5f * (al - ga);
+            if (d < 0.0f) delta = n / d;
+            if (!(fabsf(delta) <= 0.5f)) delta = 0.0f;
+        }
+        const double x = ((double)(p + a.bin0) + (double)delta) * a.hop_per_fft;
+        return (uint32_t)(int64_t)rint(x * 4294967296.0);
+    }
+    static __device__ __forceinline__ bool reset(const LkArgs&, long g, const uint32_t*, int) { return g == 0; }
+};
+
 // the nearest set bit of the bitmask to bin b (a tie goes to the lower one); b itself when no bit is set.  nz: the non-empty words.
 __device__ __forceinline__ int lk_nearest(const uint64_t* pk, uint64_t nz, int b) {
     const int w = b >> 6, bit = b & 63;
@@ -153,14 +224,15 @@ __device__ __forceinline__ int lk_nearest(const uint64_t* pk, uint64_t nz, int b
 }
 
 // One frame's regions: p[j] = P_g(bin j of this thread).  ms / es: this frame's magnitude and advance buffers (nb words each; written
-// here, valid until the frame after the next writes them again); pk: the peak bitmask.  Two barriers.
-template <int BPT>
-__device__ __forceinline__ void lk_regions(const LkFrame<BPT>& f, uint32_t* ms, uint32_t* es, uint64_t* pk, int bins, int (&p)[BPT]) {
-    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6;
+// here, valid until the frame after the next writes them again); pk: the peak bitmask.  Two barriers.  A source whose advance is
+// formed from the neighbours' magnitudes fills es between the two (for every bin: in a frame without peaks every bin is its own).
+template <typename Src, int BPT>
+__device__ __forceinline__ void lk_regions(const LkArgs& a, const LkFrame<BPT>& f, uint32_t* ms, uint32_t* es, uint64_t* pk, int (&p)[BPT]) {
+    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, bins = a.bins;
 #pragma unroll
     for (int j = 0; j < BPT; ++j) {
         ms[tid + j * nt] = __float_as_uint(f.m[j]);
-        es[tid + j * nt] = f.e[j];
+        if (Src::EARLY) es[tid + j * nt] = f.e[j];
     }
     __syncthreads();
 #pragma unroll
@@ -175,6 +247,7 @@ __device__ __forceinline__ void lk_regions(const LkFrame<BPT>& f, uint32_t* ms, 
         }
         const uint64_t word = __ballot(peak);
         if (lane == 0) pk[j * (nt >> 6) + wave] = word;
+        if (!Src::EARLY && b < bins) es[b] = Src::advance(a, ms, b);
     }
     __syncthreads();
     const int n_words = BPT * (nt >> 6);
@@ -189,8 +262,8 @@ __device__ __forceinline__ void lk_regions(const LkFrame<BPT>& f, uint32_t* ms, 
 
 extern __shared__ __attribute__((aligned(16))) uint32_t lk_lds[];
 
-// LDS of compose: pk[64] (uint64), ms[2][nb], es[2][nb], S[2][nb + 1], C[2][nb + 1], win[2][nb][wt + 1]
-template <int BPT>
+// LDS of compose: pk[64] (uint64), ms[2][nb], es[2][nb], S[2][nb + 1], C[2][nb + 1], win[Src::PLANES][nb][wt + 1]
+template <typename Src, int BPT>
 __global__ __launch_bounds__(LK_MAX_THREADS) void lock_compose_kernel(const LkArgs a) {
     const int tid = threadIdx.x, nt = blockDim.x, nb = a.nb, bins = a.bins;
     uint64_t* pk = (uint64_t*)lk_lds;
@@ -214,12 +287,12 @@ __global__ __launch_bounds__(LK_MAX_THREADS) void lock_compose_kernel(const LkAr
     int cur = 0;
     for (long g = g0; g < g1; ++g) {
         LkFrame<BPT> f;
-        lk_fetch<BPT>(a, Ac, Mc, g, win, a.wt_compose, ws0, f);
+        Src::template fetch<BPT>(a, Ac, Mc, g, win, a.wt_compose, ws0, f);
         const int par = (int)(g & 1);
         const uint32_t* msf = ms + par * nb;
         const uint32_t* esf = es + par * nb;
         int p[BPT];
-        lk_regions<BPT>(f, ms + par * nb, es + par * nb, pk, bins, p);
+        lk_regions<Src, BPT>(a, f, ms + par * nb, es + par * nb, pk, p);
         const uint32_t* Sc = S + cur * (nb + 1);
         const uint32_t* Cc = Cm + cur * (nb + 1);
         uint32_t* Sn = S + (cur ^ 1) * (nb + 1);
@@ -229,7 +302,7 @@ __global__ __launch_bounds__(LK_MAX_THREADS) void lock_compose_kernel(const LkAr
             const int b = tid + j * nt;
             if (b < bins) {
                 const int pj = p[j];
-                const bool reset = g == 0 || __uint_as_float(msf[pj]) < a.reset_below;
+                const bool reset = Src::reset(a, g, msf, pj);
                 Sn[b] = reset ? (uint32_t)bins : Sc[pj];
                 Cn[b] = reset ? 0u : Cc[pj] + esf[pj];
             }
@@ -245,7 +318,7 @@ __global__ __launch_bounds__(LK_MAX_THREADS) void lock_compose_kernel(const LkAr
     }
 }
 
-// LDS of carry: T[2][nb + 1]
+// LDS of carry: T[2][nb + 1].  (Chunk maps are chunk maps: the carry serves every frame source.)
 template <int BPT>
 __global__ __launch_bounds__(LK_MAX_THREADS) void lock_carry_kernel(const LkArgs a) {
     const int tid = threadIdx.x, nt = blockDim.x, nb = a.nb, bins = a.bins;
@@ -300,8 +373,8 @@ __global__ __launch_bounds__(LK_MAX_THREADS) void lock_carry_kernel(const LkArgs
     }
 }
 
-// LDS of apply: pk[64] (uint64), ms[2][nb], es[2][nb], T[2][nb], win[2][nb][wt + 1]
-template <int BPT, bool VEC>
+// LDS of apply: pk[64] (uint64), ms[2][nb], es[2][nb], T[2][nb], win[Src::PLANES][nb][wt + 1]
+template <typename Src, int BPT, bool VEC>
 __global__ __launch_bounds__(LK_MAX_THREADS) void lock_apply_kernel(const LkArgs a) {
     const int tid = threadIdx.x, nt = blockDim.x, nb = a.nb, bins = a.bins;
     uint64_t* pk = (uint64_t*)lk_lds;
@@ -331,12 +404,12 @@ __global__ __launch_bounds__(LK_MAX_THREADS) void lock_apply_kernel(const LkArgs
             const long g = gq + u;
             if (g < g1) {                                    // (uniform over the workgroup)
                 LkFrame<BPT> f;
-                lk_fetch<BPT>(a, Ac, Mc, g, win, a.wt_apply, ws0, f);
+                Src::template fetch<BPT>(a, Ac, Mc, g, win, a.wt_apply, ws0, f);
                 const int par = u & 1;                       // (gq is a multiple of 4)
                 const uint32_t* msf = ms + par * nb;
                 const uint32_t* esf = es + par * nb;
                 int p[BPT];
-                lk_regions<BPT>(f, ms + par * nb, es + par * nb, pk, bins, p);
+                lk_regions<Src, BPT>(a, f, ms + par * nb, es + par * nb, pk, p);
                 const uint32_t* Tc = T + cur * nb;
                 uint32_t* Tn = T + (cur ^ 1) * nb;
 #pragma unroll
@@ -344,7 +417,7 @@ __global__ __launch_bounds__(LK_MAX_THREADS) void lock_apply_kernel(const LkArgs
                     const int b = tid + j * nt;
                     if (b < bins) {
                         const int pj = p[j];
-                        const bool reset = g == 0 || __uint_as_float(msf[pj]) < a.reset_below;
+                        const bool reset = Src::reset(a, g, msf, pj);
                         const uint32_t t = reset ? 0u : Tc[pj] + esf[pj];
                         Tn[b] = t;
                         const float v = tk::angle(t + f.qa[j]);
@@ -380,70 +453,110 @@ hipError_t lk_launch(Kernel kernel, long grid, int threads, int lds_bytes, hipSt
     return hipGetLastError();
 }
 
-// The window beside `base` bytes of LDS: the widest power of two up to the chunk's own span that fits into a CU's 160 KiB; 0 when
-// not even 2 frames fit.  (Measured at 1024 bins: 8 frames with one workgroup per CU and 4 frames with two take the same time
-// within 1 %; the wider window fetches every line half as often.)
-int lk_window(int base, int nb) {
+// The window of `planes` planes beside `base` bytes of LDS: the widest power of two up to the chunk's own span that fits into a
+// CU's 160 KiB; 0 when not even 2 frames fit.  (Measured at 1024 bins and two planes: 8 frames with one workgroup per CU and 4
+// frames with two take the same time within 1 %; the wider window fetches every line half as often.)  A source of one plane gets
+// twice the frames in the same bytes.
+int lk_window(int base, int nb, int planes) {
     int wt = 0;
     for (int t = 2; t <= LK_CHUNK; t *= 2)
-        if (base + 8 * nb * (t + 1) <= 160 * 1024) wt = t;
+        if (base + 4 * planes * nb * (t + 1) <= 160 * 1024) wt = t;
     return wt;
 }
 
-template <int BPT>
+template <typename Src, int BPT>
 hipError_t lk_run(LkArgs& k, int n_ch, int threads, bool wide, hipStream_t st) {
     const int nb = k.nb;
     int lds_compose = (2 * LK_WORDS + 4 * nb + 4 * (nb + 1)) * 4;
     const int lds_carry = 2 * (nb + 1) * 4;
     int lds_apply = (2 * LK_WORDS + 6 * nb) * 4;
-    k.wt_compose = lk_window(lds_compose, nb);
-    k.wt_apply = lk_window(lds_apply, nb);
-    if (k.wt_compose) lds_compose += 8 * nb * (k.wt_compose + 1);
-    if (k.wt_apply) lds_apply += 8 * nb * (k.wt_apply + 1);
+    k.wt_compose = lk_window(lds_compose, nb, Src::PLANES);
+    k.wt_apply = lk_window(lds_apply, nb, Src::PLANES);
+    if (k.wt_compose) lds_compose += 4 * Src::PLANES * nb * (k.wt_compose + 1);
+    if (k.wt_apply) lds_apply += 4 * Src::PLANES * nb * (k.wt_apply + 1);
     hipError_t e = hipSuccess;
     if (k.n_chunks > 1) {
-        e = lk_launch(lock_compose_kernel<BPT>, (long)n_ch * (k.n_chunks - 1), threads, lds_compose, st, k);
+        e = lk_launch(lock_compose_kernel<Src, BPT>, (long)n_ch * (k.n_chunks - 1), threads, lds_compose, st, k);
         if (e != hipSuccess) return e;
     }
     e = lk_launch(lock_carry_kernel<BPT>, n_ch, threads, lds_carry, st, k);
     if (e != hipSuccess) return e;
-    if (wide) return lk_launch(lock_apply_kernel<BPT, true>, (long)n_ch * k.n_chunks, threads, lds_apply, st, k);
-    return lk_launch(lock_apply_kernel<BPT, false>, (long)n_ch * k.n_chunks, threads, lds_apply, st, k);
+    if (wide) return lk_launch(lock_apply_kernel<Src, BPT, true>, (long)n_ch * k.n_chunks, threads, lds_apply, st, k);
+    return lk_launch(lock_apply_kernel<Src, BPT, false>, (long)n_ch * k.n_chunks, threads, lds_apply, st, k);
 }
 
 // shapes the workspace depends on -> bytes, or a negative error code
-int64_t lk_workspace_bytes(const pg_phase_lock_args* a) {
-    if (!a) return pg_fail(PG_ERR_NULL, "phase_lock: args required");
-    if (a->n_ch <= 0 || a->bins <= 0 || a->F_out <= 0) return pg_fail(PG_ERR_SHAPE, "phase_lock: non-positive dimension");
-    if (a->bins > LK_MAX_BINS) return pg_fail(PG_ERR_SHAPE, "phase_lock: more than 4096 bins");
-    const int64_t n_chunks = (a->F_out - 1) / LK_CHUNK + 1;
-    if (n_chunks > (int64_t)0x7fffffff / a->n_ch) return pg_fail(PG_ERR_SHAPE, "phase_lock: more than 2^31 - 1 (channel, chunk) pairs");
-    return (int64_t)a->n_ch * n_chunks * 3 * a->bins * 4;      // < 2^31 * 3 * 2^12 * 4
+int64_t lk_workspace_bytes(const char* op, int n_ch, int bins, int64_t F_out) {
+    if (n_ch <= 0 || bins <= 0 || F_out <= 0) return pg_failf(PG_ERR_SHAPE, "%s: non-positive dimension", op);
+    if (bins > LK_MAX_BINS) return pg_failf(PG_ERR_SHAPE, "%s: more than %d bins", op, LK_MAX_BINS);
+    const int64_t n_chunks = (F_out - 1) / LK_CHUNK + 1;
+    if (n_chunks > (int64_t)0x7fffffff / n_ch) return pg_failf(PG_ERR_SHAPE, "%s: more than 2^31 - 1 (channel, chunk) pairs", op);
+    return (int64_t)n_ch * n_chunks * 3 * bins * 4;            // < 2^31 * 3 * 2^12 * 4
+}
+
+// the three launches for the source Src; k holds everything but the plan
+template <typename Src>
+int lk_scan(const char* op, LkArgs& k, int n_ch, int64_t F_out, void* workspace, bool wide, void* stream) {
+    const int bpt = lk_bpt(k.bins), threads = lk_threads(k.bins);
+    k.ws = (uint32_t*)workspace;
+    k.n_chunks = (F_out - 1) / LK_CHUNK + 1;
+    k.nb = bpt * threads;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    switch (bpt) {
+        case 1: e = lk_run<Src, 1>(k, n_ch, threads, wide, st); break;
+        case 2: e = lk_run<Src, 2>(k, n_ch, threads, wide, st); break;
+        case 3: e = lk_run<Src, 3>(k, n_ch, threads, wide, st); break;
+        default: e = lk_run<Src, 4>(k, n_ch, threads, wide, st); break;
+    }
+    return e == hipSuccess ? PG_OK : pg_failf((int)e, "%s launch failed", op);
 }
 
 }  // namespace
 
-extern "C" int64_t pg_workspace_bytes_phase_lock(const pg_phase_lock_args* a) { return lk_workspace_bytes(a); }
+extern "C" int64_t pg_workspace_bytes_phase_lock(const pg_phase_lock_args* a) {
+    if (!a) return pg_fail(PG_ERR_NULL, "phase_lock: args required");
+    return lk_workspace_bytes("phase_lock", a->n_ch, a->bins, a->F_out);
+}
 
 extern "C" int pg_phase_lock(const pg_phase_lock_args* a, void* stream) {
     LkArgs k;
     bool wide;
     if (int e = pg_stretch_check("phase_lock", true, LK_MAX_BINS, a, k, wide)) return e;
     if (((uintptr_t)a->workspace) & 3) return pg_fail(PG_ERR_ALIGN, "phase_lock: misaligned pointer");
-    const int64_t need = lk_workspace_bytes(a);
+    const int64_t need = lk_workspace_bytes("phase_lock", a->n_ch, a->bins, a->F_out);
     if (need < 0) return (int)need;
     if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_lock: workspace missing or smaller than pg_workspace_bytes_phase_lock()");
-    const int bpt = lk_bpt(a->bins), threads = lk_threads(a->bins);
-    k.ws = (uint32_t*)a->workspace;
-    k.n_chunks = (a->F_out - 1) / LK_CHUNK + 1;
-    k.nb = bpt * threads;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e;
-    switch (bpt) {
-        case 1: e = lk_run<1>(k, a->n_ch, threads, wide, st); break;
-        case 2: e = lk_run<2>(k, a->n_ch, threads, wide, st); break;
-        case 3: e = lk_run<3>(k, a->n_ch, threads, wide, st); break;
-        default: e = lk_run<4>(k, a->n_ch, threads, wide, st); break;
-    }
-    return e == hipSuccess ? PG_OK : pg_fail((int)e, "phase_lock launch failed");
+    k.bin0 = 0; k.hop_per_fft = 0.0;
+    return lk_scan<LockSrc>("phase_lock", k, a->n_ch, a->F_out, a->workspace, wide, stream);
+}
+
+extern "C" int64_t pg_workspace_bytes_phase_spsi(const pg_phase_spsi_args* a) {
+    if (!a) return pg_fail(PG_ERR_NULL, "phase_spsi: args required");
+    return lk_workspace_bytes("phase_spsi", a->n_ch, a->bins, a->F);
+}
+
+// (the checks in the order of pg_stretch_check: NULL, shapes, ranges, strides, alignment, then the workspace)
+extern "C" int pg_phase_spsi(const pg_phase_spsi_args* a, void* stream) {
+    if (!a || !a->M || !a->out) return pg_fail(PG_ERR_NULL, "phase_spsi: args, M and out required");
+    if (a->n_ch <= 0 || a->bins <= 0 || a->F <= 0) return pg_fail(PG_ERR_SHAPE, "phase_spsi: non-positive dimension");
+    if (a->bins > LK_MAX_BINS) return pg_failf(PG_ERR_SHAPE, "phase_spsi: more than %d bins", LK_MAX_BINS);
+    if (a->n_fft < 1 || a->hop < 1 || a->hop > a->n_fft) return pg_fail(PG_ERR_SHAPE, "phase_spsi: need 1 <= hop <= n_fft");
+    if (a->bin0 < 0 || a->bin0 > 65536) return pg_fail(PG_ERR_SHAPE, "phase_spsi: bin0 must be within [0, 65536]");
+    if (a->F > INT64_MAX / 2 / a->bins) return pg_fail(PG_ERR_SHAPE, "phase_spsi: plane beyond 2^62 elements");
+    if (a->m_stride < (int64_t)a->bins * a->F) return pg_fail(PG_ERR_SHAPE, "phase_spsi: m_stride shorter than a plane");
+    if ((int64_t)a->n_ch * a->bins > INT64_MAX / 2 / a->F) return pg_fail(PG_ERR_SHAPE, "phase_spsi: output beyond 2^62 elements");
+    if ((((uintptr_t)a->M) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->workspace) & 3)) return pg_fail(PG_ERR_ALIGN, "phase_spsi: misaligned pointer");
+    const int64_t need = lk_workspace_bytes("phase_spsi", a->n_ch, a->bins, a->F);
+    if (need < 0) return (int)need;
+    if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_spsi: workspace missing or smaller than pg_workspace_bytes_phase_spsi()");
+    LkArgs k;
+    k.A = nullptr; k.M = a->M; k.out = a->out;
+    k.src_per_out = 1.0;                                     // the identity grid: frame g of `out` is column g of M
+    k.a_stride = 0; k.m_stride = a->n_ch == 1 ? 0 : a->m_stride;
+    k.F_src = a->F; k.F_out = a->F;
+    k.bins = a->bins; k.reset_below = 0.0f;
+    k.bin0 = a->bin0; k.hop_per_fft = (double)a->hop / (double)a->n_fft;
+    const bool wide = (a->F & 3) == 0 && pg_al16(a->out);
+    return lk_scan<SpsiSrc>("phase_spsi", k, a->n_ch, a->F, a->workspace, wide, stream);
 }

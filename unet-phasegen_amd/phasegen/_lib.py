@@ -197,6 +197,13 @@ class PhaseLockArgs(C.Structure):
     _fields_ = PhaseVocoderArgs._fields_ + [("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class PhaseSpsiArgs(C.Structure):
+    """pg_phase_spsi_args: a phase from the magnitudes alone, single-pass spectrogram inversion (include/phasegen.h)."""
+    _fields_ = [("n_ch", C.c_int32), ("bins", C.c_int32), ("F", C.c_int64), ("n_fft", C.c_int32), ("hop", C.c_int32),
+                ("bin0", C.c_int32), ("_pad0", C.c_int32), ("M", C.c_void_p), ("m_stride", C.c_int64), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class WaveCompareArgs(C.Structure):
     """pg_wave_compare_args: six sums per signal of a reference / estimate pair of waveforms (include/phasegen.h)."""
     _fields_ = [("n_signals", C.c_int32), ("_pad0", C.c_int32), ("n", C.c_int64),
@@ -263,6 +270,8 @@ SYMBOLS = {
     "pg_phase_vocoder": (C.c_int, [C.POINTER(PhaseVocoderArgs), C.c_void_p]),
     "pg_workspace_bytes_phase_lock": (C.c_int64, [C.POINTER(PhaseLockArgs)]),
     "pg_phase_lock": (C.c_int, [C.POINTER(PhaseLockArgs), C.c_void_p]),
+    "pg_workspace_bytes_phase_spsi": (C.c_int64, [C.POINTER(PhaseSpsiArgs)]),
+    "pg_phase_spsi": (C.c_int, [C.POINTER(PhaseSpsiArgs), C.c_void_p]),
     "pg_workspace_bytes_wave_compare": (C.c_int64, [C.POINTER(WaveCompareArgs)]),
     "pg_wave_compare": (C.c_int, [C.POINTER(WaveCompareArgs), C.c_void_p]),
     "pg_workspace_bytes_spec_compare": (C.c_int64, [C.POINTER(SpecCompareArgs)]),

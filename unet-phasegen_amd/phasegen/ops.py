@@ -991,6 +991,32 @@ def phase_lock(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=
     return out
 
 
+def phase_spsi(logmag, n_fft, hop, bin0=1, out=None):
+    """A phase from the magnitudes alone, in one pass (pg_phase_spsi; single-pass spectrogram inversion, Beauregard et al. 2015):
+    ``logmag`` (n_ch, bins <= 4096, F) float32 on the device, on the OUTPUT frame grid, frames contiguous, rows F apart, the channel
+    stride free (``pol[:, 0]`` of a (n_ch, 2, bins, F) polar tensor is read in place) -> (n_ch, bins, F), dense, in [-pi, pi].  The
+    peaks of every frame (``phase_lock``'s) advance by their parabola-interpolated frequency, (bin + offset) * hop / n_fft of a turn
+    per frame, every other bin follows its nearest peak, and odd FFT bins get the half turn of the centred Hann framing; ``bin0`` is
+    the FFT bin of row 0 (1: the DC row is dropped).  Exact on a 2^32 grid of the turn.  No analysis phase, no weights, no
+    iteration: the model-free estimate a predicted phase has to beat, and a start for Griffin-Lim."""
+    m_stride = _vocoder_plane(logmag, "logmag", who="phase_spsi")
+    n_ch, bins, F = logmag.shape
+    n_fft, hop, bin0 = int(n_fft), int(hop), int(bin0)
+    if not 1 <= hop <= n_fft:
+        raise ValueError(f"phase_spsi: need 1 <= hop <= n_fft, got hop {hop} and n_fft {n_fft}")
+    if not 0 <= bin0 <= 65536:
+        raise ValueError(f"phase_spsi: bin0 must be within [0, 65536], got {bin0}")
+    out = _out(out, (n_ch, bins, F), logmag.device, "phase_spsi")
+    a = _lib.PhaseSpsiArgs()
+    a.n_ch, a.bins, a.F, a.n_fft, a.hop, a.bin0 = n_ch, bins, F, n_fft, hop, bin0
+    a.M, a.m_stride = logmag.data_ptr(), m_stride
+    a.out = _dense(out, "out")
+    lib = _lib.load()
+    a.workspace, a.workspace_bytes = _workspace(_lock_ws, logmag.device, lib.pg_workspace_bytes_phase_spsi(C.byref(a)), "workspace_bytes_phase_spsi")
+    _lib.check(lib.pg_phase_spsi(C.byref(a), _stream()), "phase_spsi")
+    return out
+
+
 _compare_ws = _StreamCache()
 _caches.append(_compare_ws)
 

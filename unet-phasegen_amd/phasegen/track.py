@@ -29,6 +29,11 @@ along the output frames by its measured advance (ops.phase_vocoder); it needs no
 identity phase locking (ops.phase_lock: only the peaks of a frame advance, every other bin follows its peak).  A stretched track has
 no reference waveform, so ``evaluate_stretch`` reports ``metrics.consistency`` instead: how far the spectrogram of each phase source's result
 lands from the magnitudes that were imposed.
+
+phase="spsi" (spectral join) is single-pass spectrogram inversion (ops.phase_spsi): a phase from the output grid's magnitudes ALONE
+-- peaks advance by their interpolated frequency, every other bin follows its peak -- with no analysis phase, no weights and no
+iteration: the baseline a predicted phase has to beat, and the only comparator that uses nothing a stretched spectrogram lacks.
+``evaluate_track(gl_init="spsi")`` starts Griffin-Lim from it instead of from noise.
 """
 import collections
 import fractions
@@ -61,6 +66,8 @@ def track_plan(a_len, frames, hop_length, overlap_frames):
 
 
 PHASES = ("unet", "zero", "original", "griffinlim")
+REPORT_PHASES = PHASES + ("spsi",)                                # what evaluate_track reports ("spsi": spectral join only)
+GL_INITS = ("noise", "spsi")
 
 
 class _Analysis:
@@ -111,13 +118,16 @@ def _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, r
     return an
 
 
-def _clips(an, model, phase, hop_length, clip_batch, gl_iters=250, gl_seed=0):
+def _clips(an, model, phase, hop_length, clip_batch, gl_iters=250, gl_seed=0, gl_init="noise"):
     """Un-normalised clip audio (n_clips * n_ch, T) of one phase source."""
     logmag = an.pol[:, 0]
     n_sig, bins, frames = logmag.shape
     if phase == "griffinlim":
         n_fft = 2 * bins
-        return pg_audio.griffin_lim_batch(torch.exp(logmag) - 1.0, n_fft, hop_length, gl_iters, seed=gl_seed, normalize=False)[0]
+        init = None
+        if gl_init == "spsi":                                    # every clip starts from its single-pass inversion instead of noise
+            init = ops.istft(logmag, ops.phase_spsi(logmag, n_fft, hop_length), hop_length, mode=0, normalize=False)
+        return pg_audio.griffin_lim_batch(torch.exp(logmag) - 1.0, n_fft, hop_length, gl_iters, seed=gl_seed, normalize=False, init=init)[0]
     if phase == "unet":
         ph = torch.empty(n_sig, bins, frames, device=logmag.device)
         for i in range(0, n_sig, clip_batch):
@@ -129,10 +139,10 @@ def _clips(an, model, phase, hop_length, clip_batch, gl_iters=250, gl_seed=0):
     return pg_audio.synthesize(logmag, ph, hop_length, normalize=False)
 
 
-def _synthesise(an, model, phase, hop_length, clip_batch, normalize, gl_iters=250, gl_seed=0):
+def _synthesise(an, model, phase, hop_length, clip_batch, normalize, gl_iters=250, gl_seed=0, gl_init="noise"):
     """One phase source -> the stitched track (channels, a_len); raises when a sample is not finite."""
     with torch.cuda.device(an.a2.device), torch.no_grad():
-        clips = _clips(an, model, phase, hop_length, clip_batch, gl_iters, gl_seed)            # (n_clips * n_ch, T)
+        clips = _clips(an, model, phase, hop_length, clip_batch, gl_iters, gl_seed, gl_init)   # (n_clips * n_ch, T)
         out, _, bad = ops.stitch(clips.view(an.n_clips, an.n_ch, an.T).transpose(0, 1), an.step, an.a_len, normalize=normalize, return_status=True)
         if int(bad.item()) != 0:
             raise ValueError("Audio buffer is not finite everywhere")       # librosa.util.valid_audio's ParameterError
@@ -198,8 +208,9 @@ def _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, o
 # log1p|z| of the standardised spectrogram below which phase="vocoder" resets a bin: of {0, 0.01, 0.05, 0.2} the floor with the
 # smallest consistency on the synthetic melody at stretch 1.5 (tools/vocoder_bench.py; the four figures are in DESIGN.md section 4.11)
 VOCODER_RESET_BELOW = 0.2
-STRETCH_PHASES = ("unet", "vocoder", "zero", "vocoder_locked")
+STRETCH_PHASES = ("unet", "vocoder", "zero", "vocoder_locked", "spsi")
 VOCODER_PHASES = ("vocoder", "vocoder_locked")                    # the analysis' own phase, propagated: no model, spectral join only
+GRID_PHASES = VOCODER_PHASES + ("spsi",)                          # computed on the track's frame grid: no model, spectral join only
 
 
 def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below=None):
@@ -220,6 +231,11 @@ def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_bel
         # ... with identity phase locking: only the peaks of a frame advance, every other bin takes its peak's rotation
         ph = ops.phase_lock(an.pol[:, 1], pl.F_out, spo, logmag=logmag,
                             reset_below=VOCODER_RESET_BELOW if reset_below is None else reset_below)
+    elif phase == "spsi":
+        # from the magnitudes on the output grid alone: they come first, and nothing of the analysis' phase is read
+        mag = ops.spec_clips(logmag, 1, pl.F_out, pl.F_out, spo)[0]
+        ph = ops.phase_spsi(mag, 2 * bins, hop_length)
+        return mag, ops.istft(mag, ph, hop_length, mode=0, normalize=False)
     else:
         x = ops.spec_clips(logmag, pl.n_clips, frames, pl.sf, spo).view(pl.n_clips * n_ch, bins, frames)   # (clip, channel) order
         n_sig = x.shape[0]
@@ -263,10 +279,10 @@ def _check_join(who, join, stretch, phase_list):
     for p in phase_list:
         if join == "spectral" and p == "griffinlim":
             raise ValueError(f"{who}: phase 'griffinlim' is not available under join='spectral'")
-        if join != "spectral" and p in VOCODER_PHASES:
+        if join != "spectral" and p in GRID_PHASES:
             raise ValueError(f"{who}: phase {p!r} needs join='spectral' (it propagates the phase on the track's frame grid)")
         if stretch != 1.0 and p not in STRETCH_PHASES:
-            raise ValueError(f"{who}: stretch {stretch} needs phase 'unet', 'vocoder', 'vocoder_locked' or 'zero', got {p!r} (the analysis' own phase does not fit a resampled spectrogram)")
+            raise ValueError(f"{who}: stretch {stretch} needs phase 'unet', 'vocoder', 'vocoder_locked', 'spsi' or 'zero', got {p!r} (the analysis' own phase does not fit a resampled spectrogram)")
     return stretch
 
 
@@ -281,21 +297,25 @@ def peak_normalize(audio):
     return out[0] if audio.dim() == 1 else out
 
 
-def _keyword_options(impl, **options):
+def _keyword_options(impl, later=None, **options):
     """Decorator for the two public track functions: the decorated ``def`` states the POSITIONAL parameter list and the docstring --
     the list callers of the waveform-only functions have always seen, which stays as it is (``inspect.signature`` reports it) -- and
     the call itself goes to ``impl`` with, in addition, the keyword-only ``options`` (name=default), which may be passed by keyword
-    only.  ``fn.options`` lists them."""
+    only.  ``fn.options`` lists them.  ``later``: keyword-only options (name=default) added since callers began to compare
+    ``fn.options``, which therefore stays as it was; ``fn.later_options`` lists those."""
+    later = dict(later or {})
+
     def deco(fn):
         sig = inspect.signature(fn)
 
         @functools.wraps(fn)
         def call(*args, **kw):
-            opts = {k: kw.pop(k, d) for k, d in options.items()}
+            opts = {k: kw.pop(k, d) for k, d in {**options, **later}.items()}
             bound = sig.bind(*args, **kw)
             bound.apply_defaults()
             return impl(**bound.arguments, **opts)
         call.options = dict(options)
+        call.later_options = dict(later)
         return call
     return deco
 
@@ -303,8 +323,8 @@ def _keyword_options(impl, **options):
 def _reconstruct_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phase, normalize,
                        join, stretch):
     """``reconstruct_track`` with its keyword-only options spelled out."""
-    if phase not in ("unet", "original", "zero") + VOCODER_PHASES:
-        raise ValueError(f"reconstruct_track: phase must be 'unet', 'original', 'zero', 'vocoder' or 'vocoder_locked', got {phase!r}")
+    if phase not in ("unet", "original", "zero") + GRID_PHASES:
+        raise ValueError(f"reconstruct_track: phase must be 'unet', 'original', 'zero', 'vocoder', 'vocoder_locked' or 'spsi', got {phase!r}")
     if phase == "unet" and model is None:
         raise ValueError("reconstruct_track: phase='unet' needs a model")
     if clip_batch < 1:
@@ -336,16 +356,20 @@ def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, over
     join only, ``model`` may be None) is the phase vocoder: the analysis' own phase, propagated along the output frames by its
     measured advance (ops.phase_vocoder, floor ``VOCODER_RESET_BELOW``) -- the standard comparator of a time stretch.
     phase="vocoder_locked" (the same conditions) is that vocoder with identity phase locking (ops.phase_lock): only the spectral peaks
-    of a frame advance and every other bin keeps its analysis phase relation to its peak -- the stretch to use without weights."""
+    of a frame advance and every other bin keeps its analysis phase relation to its peak -- the stretch to use without weights.
+    phase="spsi" (the same conditions) is single-pass spectrogram inversion (ops.phase_spsi): a phase from the output grid's
+    magnitudes alone, the model-free baseline that reads nothing of the analysis' phase."""
 
 
 def _evaluate_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phases, gl_iters,
-                    gl_seed, floor, return_audio, join):
-    """``evaluate_track`` with its keyword-only option spelled out."""
+                    gl_seed, floor, return_audio, join, gl_init):
+    """``evaluate_track`` with its keyword-only options spelled out."""
     phases = tuple(phases)
     for p in phases:
-        if p not in PHASES:
-            raise ValueError(f"evaluate_track: unknown phase {p!r} (expected some of {PHASES})")
+        if p not in REPORT_PHASES:
+            raise ValueError(f"evaluate_track: unknown phase {p!r} (expected some of {REPORT_PHASES})")
+    if gl_init not in GL_INITS:
+        raise ValueError(f"evaluate_track: gl_init must be 'noise' or 'spsi', got {gl_init!r}")
     if len(set(phases)) != len(phases) or not phases:
         raise ValueError("evaluate_track: phases must be a non-empty list without repetitions")
     if "unet" in phases and model is None:
@@ -358,14 +382,14 @@ def _evaluate_track(model, audio, n_fft, hop_length, frames, overlap_frames, sta
     else:
         an = _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type)
     ref = an.a2[0] if an.mono else an.a2
-    res = {"n_samples": int(an.a_len), "sr": int(sr), "n_clips": int(an.n_clips), "join": join, "metrics": {}}
+    res = {"n_samples": int(an.a_len), "sr": int(sr), "n_clips": int(an.n_clips), "join": join, "gl_init": gl_init, "metrics": {}}
     if return_audio:
         res["audio"] = {}
     for p in phases:
         if join == "spectral":
             out = _synthesise_spectral(an, model, p, hop_length, frames, clip_batch, False)
         else:
-            out = _synthesise(an, model, p, hop_length, clip_batch, False, gl_iters, gl_seed)
+            out = _synthesise(an, model, p, hop_length, clip_batch, False, gl_iters, gl_seed, gl_init)
         out = out[0] if an.mono else out
         res["metrics"][p] = metrics.compare_audio(ref, out, n_fft, hop_length, floor)
         if return_audio:
@@ -373,7 +397,7 @@ def _evaluate_track(model, audio, n_fft, hop_length, frames, overlap_frames, sta
     return res
 
 
-@_keyword_options(_evaluate_track, join="waveform")
+@_keyword_options(_evaluate_track, later={"gl_init": "noise"}, join="waveform")
 def evaluate_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
                    res_type="kaiser_best", clip_batch=64, phases=("unet", "zero", "original"), gl_iters=250, gl_seed=0, floor=1e-10,
                    return_audio=False):
@@ -383,8 +407,10 @@ def evaluate_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap
     the un-normalised stitched track and ``metrics.compare_audio(input at sr, track, n_fft, hop_length, floor)``.
     -> {"n_samples", "sr", "n_clips", "join", "metrics": {phase: dict}} and, with ``return_audio``, "audio": {phase: device tensor
     shaped like the input}.  The "unet" audio has the bits of ``reconstruct_track(..., normalize=False)``.  ``model`` may be None
-    when "unet" is not asked for.  Keyword-only option (``evaluate_track.options``): ``join="waveform"`` or ``"spectral"``, as in
-    ``reconstruct_track`` ("griffinlim" is not available under "spectral")."""
+    when "unet" is not asked for.  Keyword-only options (``evaluate_track.options`` and ``.later_options``): ``join="waveform"`` or ``"spectral"``, as in
+    ``reconstruct_track`` ("griffinlim" is not available under "spectral"; "spsi", ops.phase_spsi on the track's magnitudes, only
+    there: ``REPORT_PHASES``); ``gl_init="noise"`` or ``"spsi"``: every clip's Griffin-Lim starts from noise or from the ISTFT of
+    its single-pass inversion (``griffin_lim_batch``'s ``init``).  The report records ``gl_init``."""
 
 
 def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
@@ -393,7 +419,7 @@ def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=1
     """The quality report of a STRETCHED track, which has no reference waveform to be compared with: ONE spectral analysis (as
     ``reconstruct_track(join="spectral", stretch=stretch)``), then for every entry of ``phases`` -- "unet" (the model's phase),
     "vocoder" (ops.phase_vocoder with the floor ``reset_below``; None: ``VOCODER_RESET_BELOW``), "zero" (none), "vocoder_locked"
-    (ops.phase_lock with the same floor) -- one synthesis and
+    (ops.phase_lock with the same floor), "spsi" (ops.phase_spsi on the resampled magnitudes alone) -- one synthesis and
     ``metrics.consistency`` of its untrimmed ISTFT output against the resampled log-magnitude plane it was made from: how far the
     spectrogram of the result lands from the magnitudes that were imposed.
     -> {"n_samples", "n_out", "sr", "stretch", "n_clips", "reset_below", "metrics": {phase: dict}} and, with ``return_audio``,
@@ -445,7 +471,7 @@ def pitch_shift(model, audio, semitones, n_fft=2048, hop_length=512, frames=128,
     """Pitch shift by ``semitones`` (within two octaves) without a change of tempo: the track is stretched by 2 ** (semitones / 12)
     through the spectral join (``reconstruct_track(join="spectral", stretch=...)``: same pitch, longer or shorter) and played back
     faster or slower by the same ratio (``preproc.resample`` by q / p, see ``pitch_ratio`` for the error in cents), then trimmed or
-    zero-padded to the input's length at ``sr``.  ``phase``: "unet", "vocoder", "vocoder_locked" or "zero", as in
+    zero-padded to the input's length at ``sr``.  ``phase``: "unet", "vocoder", "vocoder_locked", "spsi" or "zero", as in
     ``reconstruct_track``.
     -> float32 device tensor shaped like the input at ``sr``."""
     stretch, ratio = pitch_ratio(semitones)

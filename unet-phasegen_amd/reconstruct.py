@@ -25,6 +25,11 @@ peaks advance, every other bin follows its peak): the time stretch to use withou
 measured by, spectrogram consistency (``phasegen.track.evaluate_stretch``): spectral convergence and log-spectral distance between
 the magnitudes that were imposed and the spectrogram of the result, for ``--phase`` and the other phase sources that need no
 weights (and the model's when ``--weight`` is given), written as JSON.
+
+``--phase spsi`` is single-pass spectrogram inversion: a phase from the magnitudes alone (peaks advance by their interpolated
+frequency, every other bin follows its peak), the model-free baseline; it needs no ``--weight`` and implies the spectral join, like
+the vocoders.  ``--report_phases`` accepts ``spsi`` with ``--join spectral``, and ``--gl_init spsi`` starts the ``griffinlim`` report
+phase from that inversion instead of from noise.
 """
 import argparse
 import json
@@ -33,6 +38,9 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+GRID_PHASES = ("vocoder", "vocoder_locked", "spsi")              # computed on the track's frame grid: no weights, spectral join
 
 
 def main():
@@ -53,8 +61,11 @@ def main():
     parser.add_argument("--stereo", action="store_true", help="keep the file's channels instead of their mono average")
     parser.add_argument("--report", default=None, metavar="PATH", help="write a JSON quality report of the result against the input")
     parser.add_argument("--report_phases", default="unet,zero,original",
-                        help="comma list of phase sources to report: unet, zero, original, griffinlim ('unet' is always included)")
+                        help="comma list of phase sources to report: unet, zero, original, griffinlim, spsi (spsi: with --join spectral; "
+                             "'unet' is always included)")
     parser.add_argument("--gl_iters", default=250, type=int, help="Griffin-Lim iterations of the 'griffinlim' report phase")
+    parser.add_argument("--gl_init", choices=["noise", "spsi"], default="noise",
+                        help="where the 'griffinlim' report phase starts: noise (default) or the single-pass inversion of every clip")
     parser.add_argument("--join", choices=["waveform", "spectral"], default=None,
                         help="how overlapped clips become one track: crossfade the clips' waveforms (default), or join their phases "
                              "on the track's frame grid and invert once with the exact magnitudes")
@@ -62,9 +73,9 @@ def main():
                         help="play R times as long at the same pitch, 0.25 <= R <= 4 (implies --join spectral)")
     parser.add_argument("--pitch", default=None, type=float, metavar="SEMITONES",
                         help="shift the pitch at the same tempo, within +-24 semitones (implies --join spectral)")
-    parser.add_argument("--phase", choices=["unet", "vocoder", "vocoder_locked", "zero"], default="unet",
-                        help="where the phase comes from: the model (default), the phase vocoder, plain or with identity phase locking "
-                             "(both imply --join spectral), or none")
+    parser.add_argument("--phase", choices=["unet", "vocoder", "vocoder_locked", "spsi", "zero"], default="unet",
+                        help="where the phase comes from: the model (default), the phase vocoder, plain or with identity phase locking, "
+                             "single-pass inversion of the magnitudes alone (all three imply --join spectral), or none")
     parser.add_argument("--stretch_report", default=None, metavar="PATH",
                         help="with --stretch: write a JSON report of the spectrogram consistency of every phase source")
     args = parser.parse_args()
@@ -77,7 +88,7 @@ def main():
         parser.error("--stretch and --pitch need --join spectral")
     if modified and args.report is not None:
         parser.error("--report compares against the input: it works with --join, not with --stretch or --pitch")
-    if args.phase in ("vocoder", "vocoder_locked") and args.join == "waveform":
+    if args.phase in GRID_PHASES and args.join == "waveform":
         parser.error("--phase {} needs --join spectral".format(args.phase))
     if args.phase != "unet" and args.report is not None:
         parser.error("--report measures the model's phase: it needs --phase unet")
@@ -87,7 +98,7 @@ def main():
         parser.error("--stretch_report measures the stretched track on the analysed frame grid: it does not work with --pitch")
     if args.stretch_report is not None and args.report is not None:
         parser.error("--report and --stretch_report exclude each other")
-    join = "spectral" if (modified or args.stretch is not None or args.phase in ("vocoder", "vocoder_locked")) and args.join is None else (args.join or "waveform")
+    join = "spectral" if (modified or args.stretch is not None or args.phase in GRID_PHASES) and args.join is None else (args.join or "waveform")
     if args.stretch_report is not None and join != "spectral":
         parser.error("--stretch_report needs --join spectral")
     n_fft = 2 * args.channels if args.n_fft is None else args.n_fft
@@ -119,8 +130,10 @@ def main():
         if "unet" not in phases:
             phases.insert(0, "unet")
         for p in phases:
-            if p not in track.PHASES:
-                parser.error(f"--report_phases: unknown phase {p!r} (expected some of {', '.join(track.PHASES)})")
+            if p not in track.REPORT_PHASES:
+                parser.error(f"--report_phases: unknown phase {p!r} (expected some of {', '.join(track.REPORT_PHASES)})")
+            if p == "spsi" and join != "spectral":
+                parser.error("--report_phases: spsi needs --join spectral")
 
     start = time.time()
     kw = dict(n_fft=n_fft, hop_length=hop, frames=args.frames, overlap_frames=args.overlap_frames, stats=stats, osr=file_sr, sr=args.sr)
@@ -129,14 +142,14 @@ def main():
     if args.pitch is not None:
         out = track.pitch_shift(model, audio, args.pitch, phase=args.phase, **kw)
     elif args.stretch_report is not None:
-        # (the locked vocoder is reported when it is asked for; the other modes' reports stay as they were)
-        others = [p for p in track.STRETCH_PHASES if p not in (args.phase, "vocoder_locked") and (p != "unet" or model is not None)]
+        # (the locked vocoder and spsi are reported when they are asked for; the other modes' reports stay as they were)
+        others = [p for p in track.STRETCH_PHASES if p not in (args.phase, "vocoder_locked", "spsi") and (p != "unet" or model is not None)]
         stretch_report = track.evaluate_stretch(model, audio, args.stretch, phases=[args.phase] + others, return_audio=True, **kw)
         out = track.peak_normalize(stretch_report.pop("audio")[args.phase])
     elif args.report is None:
         out = track.reconstruct_track(model, audio, phase=args.phase, join=join, stretch=1.0 if args.stretch is None else args.stretch, **kw)
     else:
-        report = track.evaluate_track(model, audio, phases=phases, gl_iters=args.gl_iters, return_audio=True, join=join, **kw)
+        report = track.evaluate_track(model, audio, phases=phases, gl_iters=args.gl_iters, return_audio=True, join=join, gl_init=args.gl_init, **kw)
         out = track.peak_normalize(report.pop("audio")["unet"])
     out = out.cpu().numpy()
     took = time.time() - start
