@@ -527,6 +527,44 @@ typedef struct pg_phase_lock_args {
 int64_t pg_workspace_bytes_phase_lock(const pg_phase_lock_args* a);   /* host function of n_ch, bins, F_out; negative = error code */
 int     pg_phase_lock(const pg_phase_lock_args* a, void* stream);
 
+/* pg_phase_lock_linked: pg_phase_lock with the channels LINKED (phasegen/track.py, phase="vocoder_locked", link_channels=True).
+ * pg_phase_lock gives every channel its own peaks and its own rotation T, so the phases of one source in two channels drift apart by
+ * an arbitrary angle and the stereo image (and the mono sum) is lost; here all channels take ONE rotation, that of a reference plane
+ * pair (the channel mean, in the track layer).  Struct of its own, PG_VERSION unchanged; the reference has no counterpart; the
+ * arithmetic below is the contract.
+ *   A: the channels' angle planes (n_ch, bins, F_src), as pg_phase_lock's A.  Aref, Mref: the angle and the log-magnitude plane of
+ *   the reference, (bins, F_src) each, dense, both REQUIRED.  src_per_out, reset_below, F_src, F_out, q(), R, i0(g): pg_phase_lock's.
+ *   Rotation.  T_g[b] is, word for word, the rotation pg_phase_lock forms for the single channel (Aref, Mref): its peaks, its
+ *   regions P_g(b), its advance e_g[p] = q(Aref[p][i1(g-1)]) - q(Aref[p][i0(g)]), its reset below reset_below, and T_0 = 0.
+ *   Output.  For every channel c: out[c][b][g] = (float)((double)(int32)(T_g[b] + q(A[c][b][i0(g)])) * R).
+ *   Consequences.  n_ch == 1 with A == Aref gives the bits of pg_phase_lock(Aref, Mref); more generally any channel whose plane
+ *   equals Aref gets those bits.  src_per_out == 1.0 returns q(A[c]) for every channel (T is zero).  Before the final rounding
+ *   (T + a_c) - (T + a_d) == a_c - a_d holds in uint32: the inter-channel phase difference of the analysis survives in every cell.
+ *   A channel's result does not depend on n_ch or on the channel's position.
+ *   Kernels: pg_phase_lock's compose and carry run ONCE, on the reference, as for one channel; apply runs per (channel, chunk),
+ *   rebuilds the chunk's maps from (Mref, q(Aref)) and adds q(A[c]); its staged window holds three planes (8 source frames at 1024
+ *   bins, 2 at 2048, none at 4096).  All channels of a chunk read the same T slot, which nothing writes after carry.  16-byte stores
+ *   where out and F_out allow, frame by frame otherwise (same bits); 64-bit index arithmetic; no atomics.
+ *   workspace: pg_workspace_bytes_phase_lock_linked() bytes = 12 bins ceil(F_out / 32): one channel's worth, a function of bins and
+ *   F_out alone.  The library allocates nothing and keeps nothing.
+ *   Errors (host side, before any launch, in this order): NULL args / A / Aref / Mref / out PG_ERR_NULL; non-positive sizes, bins >
+ *   4096, src_per_out not finite or <= 0, reset_below not finite or < 0, a plane or output beyond 2^62 elements, a_stride < bins F_src,
+ *   more than 2^31 - 1 (channel, chunk) pairs PG_ERR_SHAPE; A, Aref, Mref, out or workspace not 4-byte aligned PG_ERR_ALIGN;
+ *   workspace NULL or smaller than the query's answer PG_ERR_WORKSPACE. */
+typedef struct pg_phase_lock_linked_args {
+    int32_t n_ch, bins;                          /* bins <= 4096                                                        */
+    int64_t F_src, F_out;                        /* frames per row of A, Aref and Mref, frames per row of out           */
+    double  src_per_out;                         /* source frames per output frame = 1 / stretch; finite, > 0          */
+    float   reset_below; int32_t _pad0;          /* a peak whose Mref is below this resets its region; finite, >= 0     */
+    const float* A; int64_t a_stride;            /* (n_ch, bins, F_src): the channels' angle planes, a_stride >= bins F_src apart */
+    const float* Aref;                           /* (bins, F_src): angle plane of the reference                         */
+    const float* Mref;                           /* (bins, F_src): log-magnitude plane of the reference, required       */
+    float* out;                                  /* (n_ch, bins, F_out), dense                                          */
+    void* workspace; int64_t workspace_bytes;
+} pg_phase_lock_linked_args;                     /* 96 bytes */
+int64_t pg_workspace_bytes_phase_lock_linked(const pg_phase_lock_linked_args* a);   /* host function of bins, F_out; negative = error code */
+int     pg_phase_lock_linked(const pg_phase_lock_linked_args* a, void* stream);
+
 /* pg_phase_spsi: a phase from the magnitudes ALONE, in one pass (single-pass spectrogram inversion; Beauregard, Harish & Wyse 2015;
  * phasegen/track.py, phase="spsi"): the peaks of every frame advance by their interpolated frequency and every other bin follows its
  * peak.  No analysis phase, no weights, no iteration: the comparator a predicted phase has to beat, and the only one that uses

@@ -9,6 +9,14 @@
 // output grid itself, and a peak advances by its interpolated frequency instead of by a measured phase difference (LockSrc /
 // SpsiSrc below; tests/_spsi_ref.py).  What follows describes pg_phase_lock; where pg_phase_spsi differs the sources say so.
 //
+// pg_phase_lock_linked (phase="vocoder_locked" with link_channels; tests/_link_ref.py) gives all channels ONE rotation, that of a
+// reference plane pair (Aref, Mref): compose and carry are pg_phase_lock's on the reference, run once with a channel count of 1, and
+// only apply runs per (channel, chunk) -- it rebuilds the chunk's maps from the reference, reads the one T slot of its chunk, which
+// nothing writes after carry, and adds q(A[c]) at the output (LinkSrc: a third plane in the staged window).  T cancels in the
+// uint32 difference of two channels, so the analysis' inter-channel phase differences survive the stretch exactly.  (One workgroup
+// serving all channels of a chunk from one map would save the recomputation of the maps; it needs n_ch planes of the window or a
+// pass per channel over stored maps, and is not done.)
+//
 // The recurrence (q(), angle(), i0(g), i1(g) and the advance into frame g are pg_track.h's, shared with vocoder.hip).  Per channel,
 // T_g[b] (uint32, a fraction of a turn) is the rotation of bin b at output frame g against its analysis
 // phase: T_0 = 0 and T_g[b] = reset ? 0 : T_{g-1}[p] + e_g[p] with p = P_g(b) the peak bin b belongs to, e_g[p] = q(A[p][i1(g-1)]) -
@@ -70,6 +78,7 @@ struct LkArgs {
     float reset_below;
     int bin0;                                               // SpsiSrc only: the FFT bin of row 0, and hop / n_fft in double
     double hop_per_fft;
+    const float* X; long x_stride;                          // LinkSrc only: the channels' angle planes (A and M are the reference's)
 };
 
 // what a thread reads of frame g for its bins: the magnitude, the quantised analysis phase and the advance e_g (SpsiSrc: qa is
@@ -77,8 +86,8 @@ struct LkArgs {
 template <int BPT>
 struct LkFrame { float m[BPT]; uint32_t qa[BPT]; uint32_t e[BPT]; };
 
-template <int BPT>
-__device__ __forceinline__ void lk_load(const LkArgs& a, const float* Ac, const float* Mc, long g, LkFrame<BPT>& f) {
+template <int BPT, bool LINKED>
+__device__ __forceinline__ void lk_load(const LkArgs& a, const float* Ac, const float* Mc, const float* Xc, long g, LkFrame<BPT>& f) {
     const tk::Advance adv = tk::advance(g, a.src_per_out, a.F_src);
     const long i0 = adv.i0, i1p = adv.i1p;
 #pragma unroll
@@ -91,6 +100,7 @@ __device__ __forceinline__ void lk_load(const LkArgs& a, const float* Ac, const 
             f.m[j] = Mc[row + i0];
             f.qa[j] = tk::q(Ac[row + i0]);
             f.e[j] = (i1p == i0 ? f.qa[j] : tk::q(Ac[row + i1p])) - f.qa[j];
+            if (LINKED) f.qa[j] = tk::q(Xc[row + i0]);      // (the advance is the reference's; the channel's own phase is what is added)
         }
     }
 }
@@ -99,17 +109,19 @@ __device__ __forceinline__ void lk_load(const LkArgs& a, const float* Ac, const 
 // segment is one request -- and kept transposed in LDS as win[b * (wt + 1) + k] (an odd pitch: a frame's column is read without bank
 // conflicts).  ws0: the window's first source frame, -1 before the first load; uniform over the workgroup, as is every branch here.
 // A frame whose two positions are further apart than a window (src_per_out >= wt), or a plane too wide for a window to fit into LDS
-// beside the maps (wt == 0), is read by every thread from its own rows instead.
-template <int BPT>
-__device__ __forceinline__ void lk_fetch(const LkArgs& a, const float* Ac, const float* Mc, long g, uint32_t* win, int wt, long& ws0,
-                                         LkFrame<BPT>& f) {
+// beside the maps (wt == 0), is read by every thread from its own rows instead.  LINKED: a third plane, q(X) of the workgroup's
+// channel, is staged beside the reference's two and is what f.qa holds.
+template <int BPT, bool LINKED>
+__device__ __forceinline__ void lk_fetch(const LkArgs& a, const float* Ac, const float* Mc, const float* Xc, long g, uint32_t* win, int wt,
+                                         long& ws0, LkFrame<BPT>& f) {
     const tk::Advance adv = tk::advance(g, a.src_per_out, a.F_src);
     const long i0 = adv.i0, i1p = adv.i1p;
     const long lo = i0 < i1p ? i0 : i1p, hi = i0 < i1p ? i1p : i0;
-    if (wt == 0 || hi - lo >= wt) { lk_load<BPT>(a, Ac, Mc, g, f); return; }
+    if (wt == 0 || hi - lo >= wt) { lk_load<BPT, LINKED>(a, Ac, Mc, Xc, g, f); return; }
     const int pitch = wt + 1, tid = threadIdx.x, nt = blockDim.x;
     uint32_t* winM = win;
     uint32_t* winA = win + a.nb * pitch;
+    uint32_t* winX = winA + a.nb * pitch;                   // (LINKED only)
     if (ws0 < 0 || lo < ws0 || hi >= ws0 + wt) {
         // (every wave has left the previous frame's window reads behind: two barriers ago)
         ws0 = lo;
@@ -120,6 +132,7 @@ __device__ __forceinline__ void lk_fetch(const LkArgs& a, const float* Ac, const
                 const long at = (long)r * a.F_src + ws0 + k;
                 winM[r * pitch + k] = __float_as_uint(Mc[at]);
                 winA[r * pitch + k] = tk::q(Ac[at]);
+                if (LINKED) winX[r * pitch + k] = tk::q(Xc[at]);
             }
         }
         __syncthreads();
@@ -134,6 +147,7 @@ __device__ __forceinline__ void lk_fetch(const LkArgs& a, const float* Ac, const
             f.m[j] = __uint_as_float(winM[b * pitch + k0]);
             f.qa[j] = winA[b * pitch + k0];
             f.e[j] = winA[b * pitch + k1] - f.qa[j];
+            if (LINKED) f.qa[j] = winX[b * pitch + k0];
         }
     }
 }
@@ -142,18 +156,31 @@ __device__ __forceinline__ void lk_fetch(const LkArgs& a, const float* Ac, const
 // a frame source says where frame g's magnitudes come from (fetch: f.m), how the advance of a peak is formed (EARLY: f.e, known
 // when the frame is fetched; otherwise advance(), from the frame's magnitudes in LDS after the first barrier of the region step),
 // when a region starts again from zero (reset) and what is added at the output (f.qa).  PLANES: planes in the staged window.
+// LINKED: every channel of the launch reads channel 0's T from the workspace and its own plane Xc beside the shared (Ac, Mc).
 
 // pg_phase_lock: the stretched time grid over M and q(A); the advance is measured on A; a quiet peak resets; q(A) is added.
 struct LockSrc {
     static constexpr int PLANES = 2;
     static constexpr bool EARLY = true;
+    static constexpr bool LINKED = false;
     template <int BPT>
-    static __device__ __forceinline__ void fetch(const LkArgs& a, const float* Ac, const float* Mc, long g, uint32_t* win, int wt, long& ws0,
-                                                 LkFrame<BPT>& f) { lk_fetch<BPT>(a, Ac, Mc, g, win, wt, ws0, f); }
+    static __device__ __forceinline__ void fetch(const LkArgs& a, const float* Ac, const float* Mc, const float*, long g, uint32_t* win, int wt,
+                                                 long& ws0, LkFrame<BPT>& f) { lk_fetch<BPT, false>(a, Ac, Mc, nullptr, g, win, wt, ws0, f); }
     static __device__ __forceinline__ uint32_t advance(const LkArgs&, const uint32_t*, int) { return 0u; }
     static __device__ __forceinline__ bool reset(const LkArgs& a, long g, const uint32_t* msf, int p) {
         return g == 0 || __uint_as_float(msf[p]) < a.reset_below;
     }
+};
+
+// pg_phase_lock_linked, the apply launch alone: LockSrc on the reference's planes (Ac = Aref, Mc = Mref, shared by all channels:
+// the maps, the advances and the resets are pg_phase_lock's of the reference, and compose and carry ARE LockSrc's, run once), but
+// what is added at the output is q(X) of the workgroup's own channel, a third plane of the window.
+struct LinkSrc : LockSrc {
+    static constexpr int PLANES = 3;
+    static constexpr bool LINKED = true;
+    template <int BPT>
+    static __device__ __forceinline__ void fetch(const LkArgs& a, const float* Ac, const float* Mc, const float* Xc, long g, uint32_t* win,
+                                                 int wt, long& ws0, LkFrame<BPT>& f) { lk_fetch<BPT, true>(a, Ac, Mc, Xc, g, win, wt, ws0, f); }
 };
 
 // pg_phase_spsi: M on the output grid itself (frame g is column g; no A); the advance of bin p is its interpolated frequency times
@@ -162,11 +189,12 @@ struct LockSrc {
 struct SpsiSrc {
     static constexpr int PLANES = 1;
     static constexpr bool EARLY = false;
+    static constexpr bool LINKED = false;
     // The window holds frames [g - g % wt, + wt) of the one plane: wt divides LK_CHUNK and chunks begin on multiples of it, so it
     // is reloaded every wt frames whatever the data.  (Every wave has left the previous window's reads two barriers behind.)
     template <int BPT>
-    static __device__ __forceinline__ void fetch(const LkArgs& a, const float*, const float* Mc, long g, uint32_t* win, int wt, long&,
-                                                 LkFrame<BPT>& f) {
+    static __device__ __forceinline__ void fetch(const LkArgs& a, const float*, const float* Mc, const float*, long g, uint32_t* win, int wt,
+                                                 long&, LkFrame<BPT>& f) {
         const int tid = threadIdx.x, nt = blockDim.x, pitch = wt + 1, k = wt ? (int)(g & (long)(wt - 1)) : 0;
         if (wt && k == 0) {
             const int shift = __builtin_ctz((unsigned)wt), n = a.bins << shift;
@@ -287,7 +315,7 @@ __global__ __launch_bounds__(LK_MAX_THREADS) void lock_compose_kernel(const LkAr
     int cur = 0;
     for (long g = g0; g < g1; ++g) {
         LkFrame<BPT> f;
-        Src::template fetch<BPT>(a, Ac, Mc, g, win, a.wt_compose, ws0, f);
+        Src::template fetch<BPT>(a, Ac, Mc, nullptr, g, win, a.wt_compose, ws0, f);
         const int par = (int)(g & 1);
         const uint32_t* msf = ms + par * nb;
         const uint32_t* esf = es + par * nb;
@@ -385,8 +413,9 @@ __global__ __launch_bounds__(LK_MAX_THREADS) void lock_apply_kernel(const LkArgs
     const long c = (long)blockIdx.x / a.n_chunks, k = (long)blockIdx.x - c * a.n_chunks;
     const float* Ac = a.A + c * a.a_stride;
     const float* Mc = a.M + c * a.m_stride;
+    const float* Xc = Src::LINKED ? a.X + c * a.x_stride : nullptr;
     float* oc = a.out + c * (long)bins * a.F_out;
-    const uint32_t* w = a.ws + (c * a.n_chunks + k) * 3 * (long)bins + 2 * (long)bins;
+    const uint32_t* w = a.ws + ((Src::LINKED ? 0 : c) * a.n_chunks + k) * 3 * (long)bins + 2 * (long)bins;   // (LINKED: one T for all channels)
 #pragma unroll
     for (int j = 0; j < BPT; ++j) {
         const int b = tid + j * nt;
@@ -404,7 +433,7 @@ __global__ __launch_bounds__(LK_MAX_THREADS) void lock_apply_kernel(const LkArgs
             const long g = gq + u;
             if (g < g1) {                                    // (uniform over the workgroup)
                 LkFrame<BPT> f;
-                Src::template fetch<BPT>(a, Ac, Mc, g, win, a.wt_apply, ws0, f);
+                Src::template fetch<BPT>(a, Ac, Mc, Xc, g, win, a.wt_apply, ws0, f);
                 const int par = u & 1;                       // (gq is a multiple of 4)
                 const uint32_t* msf = ms + par * nb;
                 const uint32_t* esf = es + par * nb;
@@ -464,22 +493,24 @@ int lk_window(int base, int nb, int planes) {
     return wt;
 }
 
-template <typename Src, int BPT>
-hipError_t lk_run(LkArgs& k, int n_ch, int threads, bool wide, hipStream_t st) {
+// Scan: the source of compose (and of the carry's maps), over n_scan channels; Src: the source of apply, over n_ch channels -- the
+// same source and count but for pg_phase_lock_linked, whose scan is the reference's alone.
+template <typename Scan, typename Src, int BPT>
+hipError_t lk_run(LkArgs& k, int n_scan, int n_ch, int threads, bool wide, hipStream_t st) {
     const int nb = k.nb;
     int lds_compose = (2 * LK_WORDS + 4 * nb + 4 * (nb + 1)) * 4;
     const int lds_carry = 2 * (nb + 1) * 4;
     int lds_apply = (2 * LK_WORDS + 6 * nb) * 4;
-    k.wt_compose = lk_window(lds_compose, nb, Src::PLANES);
+    k.wt_compose = lk_window(lds_compose, nb, Scan::PLANES);
     k.wt_apply = lk_window(lds_apply, nb, Src::PLANES);
-    if (k.wt_compose) lds_compose += 4 * Src::PLANES * nb * (k.wt_compose + 1);
+    if (k.wt_compose) lds_compose += 4 * Scan::PLANES * nb * (k.wt_compose + 1);
     if (k.wt_apply) lds_apply += 4 * Src::PLANES * nb * (k.wt_apply + 1);
     hipError_t e = hipSuccess;
     if (k.n_chunks > 1) {
-        e = lk_launch(lock_compose_kernel<Src, BPT>, (long)n_ch * (k.n_chunks - 1), threads, lds_compose, st, k);
+        e = lk_launch(lock_compose_kernel<Scan, BPT>, (long)n_scan * (k.n_chunks - 1), threads, lds_compose, st, k);
         if (e != hipSuccess) return e;
     }
-    e = lk_launch(lock_carry_kernel<BPT>, n_ch, threads, lds_carry, st, k);
+    e = lk_launch(lock_carry_kernel<BPT>, n_scan, threads, lds_carry, st, k);
     if (e != hipSuccess) return e;
     if (wide) return lk_launch(lock_apply_kernel<Src, BPT, true>, (long)n_ch * k.n_chunks, threads, lds_apply, st, k);
     return lk_launch(lock_apply_kernel<Src, BPT, false>, (long)n_ch * k.n_chunks, threads, lds_apply, st, k);
@@ -494,9 +525,9 @@ int64_t lk_workspace_bytes(const char* op, int n_ch, int bins, int64_t F_out) {
     return (int64_t)n_ch * n_chunks * 3 * bins * 4;            // < 2^31 * 3 * 2^12 * 4
 }
 
-// the three launches for the source Src; k holds everything but the plan
-template <typename Src>
-int lk_scan(const char* op, LkArgs& k, int n_ch, int64_t F_out, void* workspace, bool wide, void* stream) {
+// the three launches for the sources Scan (compose, carry: n_scan channels) and Src (apply: n_ch); k holds everything but the plan
+template <typename Scan, typename Src>
+int lk_scan(const char* op, LkArgs& k, int n_scan, int n_ch, int64_t F_out, void* workspace, bool wide, void* stream) {
     const int bpt = lk_bpt(k.bins), threads = lk_threads(k.bins);
     k.ws = (uint32_t*)workspace;
     k.n_chunks = (F_out - 1) / LK_CHUNK + 1;
@@ -504,10 +535,10 @@ int lk_scan(const char* op, LkArgs& k, int n_ch, int64_t F_out, void* workspace,
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
     switch (bpt) {
-        case 1: e = lk_run<Src, 1>(k, n_ch, threads, wide, st); break;
-        case 2: e = lk_run<Src, 2>(k, n_ch, threads, wide, st); break;
-        case 3: e = lk_run<Src, 3>(k, n_ch, threads, wide, st); break;
-        default: e = lk_run<Src, 4>(k, n_ch, threads, wide, st); break;
+        case 1: e = lk_run<Scan, Src, 1>(k, n_scan, n_ch, threads, wide, st); break;
+        case 2: e = lk_run<Scan, Src, 2>(k, n_scan, n_ch, threads, wide, st); break;
+        case 3: e = lk_run<Scan, Src, 3>(k, n_scan, n_ch, threads, wide, st); break;
+        default: e = lk_run<Scan, Src, 4>(k, n_scan, n_ch, threads, wide, st); break;
     }
     return e == hipSuccess ? PG_OK : pg_failf((int)e, "%s launch failed", op);
 }
@@ -527,8 +558,46 @@ extern "C" int pg_phase_lock(const pg_phase_lock_args* a, void* stream) {
     const int64_t need = lk_workspace_bytes("phase_lock", a->n_ch, a->bins, a->F_out);
     if (need < 0) return (int)need;
     if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_lock: workspace missing or smaller than pg_workspace_bytes_phase_lock()");
+    k.bin0 = 0; k.hop_per_fft = 0.0; k.X = nullptr; k.x_stride = 0;
+    return lk_scan<LockSrc, LockSrc>("phase_lock", k, a->n_ch, a->n_ch, a->F_out, a->workspace, wide, stream);
+}
+
+// one channel's worth whatever n_ch: the scan is the reference's alone
+static int64_t lk_linked_workspace_bytes(int n_ch, int bins, int64_t F_out) {
+    const int64_t all = lk_workspace_bytes("phase_lock_linked", n_ch, bins, F_out);   // (n_ch > 0, and the apply grid's (channel, chunk) pairs)
+    return all < 0 ? all : all / n_ch;
+}
+
+extern "C" int64_t pg_workspace_bytes_phase_lock_linked(const pg_phase_lock_linked_args* a) {
+    if (!a) return pg_fail(PG_ERR_NULL, "phase_lock_linked: args required");
+    return lk_linked_workspace_bytes(a->n_ch, a->bins, a->F_out);
+}
+
+// (the checks in the order of pg_stretch_check and pg_phase_lock: NULL, shapes, alignment, then the workspace)
+extern "C" int pg_phase_lock_linked(const pg_phase_lock_linked_args* a, void* stream) {
+    if (!a || !a->A || !a->Aref || !a->Mref || !a->out) return pg_fail(PG_ERR_NULL, "phase_lock_linked: args, A, Aref, Mref and out required");
+    if (a->n_ch <= 0 || a->bins <= 0 || a->F_src <= 0 || a->F_out <= 0) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: non-positive dimension");
+    if (a->bins > LK_MAX_BINS) return pg_failf(PG_ERR_SHAPE, "phase_lock_linked: more than %d bins", LK_MAX_BINS);
+    if (!(a->src_per_out > 0.0) || !(a->src_per_out <= DBL_MAX)) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: src_per_out must be finite and positive");
+    if (!(a->reset_below >= 0.0f) || !pg_finite(a->reset_below)) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: reset_below must be finite and not negative");
+    if (a->F_src > INT64_MAX / 2 / a->bins) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: plane beyond 2^62 elements");
+    if (a->a_stride < (int64_t)a->bins * a->F_src) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: a_stride shorter than a plane");
+    if ((int64_t)a->n_ch * a->bins > INT64_MAX / 2 / a->F_out) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: output beyond 2^62 elements");
+    if ((((uintptr_t)a->A) & 3) || (((uintptr_t)a->Aref) & 3) || (((uintptr_t)a->Mref) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->workspace) & 3))
+        return pg_fail(PG_ERR_ALIGN, "phase_lock_linked: misaligned pointer");
+    const int64_t need = lk_linked_workspace_bytes(a->n_ch, a->bins, a->F_out);
+    if (need < 0) return (int)need;
+    if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_lock_linked: workspace missing or smaller than pg_workspace_bytes_phase_lock_linked()");
+    LkArgs k;
+    k.A = a->Aref; k.M = a->Mref; k.out = a->out;           // the scan's planes, shared by every channel: strides 0
+    k.X = a->A; k.x_stride = a->n_ch == 1 ? 0 : a->a_stride;
+    k.src_per_out = a->src_per_out;
+    k.a_stride = 0; k.m_stride = 0;
+    k.F_src = a->F_src; k.F_out = a->F_out;
+    k.bins = a->bins; k.reset_below = a->reset_below;
     k.bin0 = 0; k.hop_per_fft = 0.0;
-    return lk_scan<LockSrc>("phase_lock", k, a->n_ch, a->F_out, a->workspace, wide, stream);
+    const bool wide = (a->F_out & 3) == 0 && pg_al16(a->out);
+    return lk_scan<LockSrc, LinkSrc>("phase_lock_linked", k, 1, a->n_ch, a->F_out, a->workspace, wide, stream);
 }
 
 extern "C" int64_t pg_workspace_bytes_phase_spsi(const pg_phase_spsi_args* a) {
@@ -556,7 +625,7 @@ extern "C" int pg_phase_spsi(const pg_phase_spsi_args* a, void* stream) {
     k.a_stride = 0; k.m_stride = a->n_ch == 1 ? 0 : a->m_stride;
     k.F_src = a->F; k.F_out = a->F;
     k.bins = a->bins; k.reset_below = 0.0f;
-    k.bin0 = a->bin0; k.hop_per_fft = (double)a->hop / (double)a->n_fft;
+    k.bin0 = a->bin0; k.hop_per_fft = (double)a->hop / (double)a->n_fft; k.X = nullptr; k.x_stride = 0;
     const bool wide = (a->F & 3) == 0 && pg_al16(a->out);
-    return lk_scan<SpsiSrc>("phase_spsi", k, a->n_ch, a->F, a->workspace, wide, stream);
+    return lk_scan<SpsiSrc, SpsiSrc>("phase_spsi", k, a->n_ch, a->n_ch, a->F, a->workspace, wide, stream);
 }

@@ -197,6 +197,14 @@ class PhaseLockArgs(C.Structure):
     _fields_ = PhaseVocoderArgs._fields_ + [("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class PhaseLockLinkedArgs(C.Structure):
+    """pg_phase_lock_linked_args: identity phase locking with ONE rotation, the reference plane's, for all channels (include/phasegen.h)."""
+    _fields_ = [("n_ch", C.c_int32), ("bins", C.c_int32), ("F_src", C.c_int64), ("F_out", C.c_int64),
+                ("src_per_out", C.c_double), ("reset_below", C.c_float), ("_pad0", C.c_int32),
+                ("A", C.c_void_p), ("a_stride", C.c_int64), ("Aref", C.c_void_p), ("Mref", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class PhaseSpsiArgs(C.Structure):
     """pg_phase_spsi_args: a phase from the magnitudes alone, single-pass spectrogram inversion (include/phasegen.h)."""
     _fields_ = [("n_ch", C.c_int32), ("bins", C.c_int32), ("F", C.c_int64), ("n_fft", C.c_int32), ("hop", C.c_int32),
@@ -270,6 +278,8 @@ SYMBOLS = {
     "pg_phase_vocoder": (C.c_int, [C.POINTER(PhaseVocoderArgs), C.c_void_p]),
     "pg_workspace_bytes_phase_lock": (C.c_int64, [C.POINTER(PhaseLockArgs)]),
     "pg_phase_lock": (C.c_int, [C.POINTER(PhaseLockArgs), C.c_void_p]),
+    "pg_workspace_bytes_phase_lock_linked": (C.c_int64, [C.POINTER(PhaseLockLinkedArgs)]),
+    "pg_phase_lock_linked": (C.c_int, [C.POINTER(PhaseLockLinkedArgs), C.c_void_p]),
     "pg_workspace_bytes_phase_spsi": (C.c_int64, [C.POINTER(PhaseSpsiArgs)]),
     "pg_phase_spsi": (C.c_int, [C.POINTER(PhaseSpsiArgs), C.c_void_p]),
     "pg_workspace_bytes_wave_compare": (C.c_int64, [C.POINTER(WaveCompareArgs)]),

@@ -991,6 +991,44 @@ def phase_lock(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=
     return out
 
 
+def phase_lock_linked(angle, ref_angle, ref_logmag, F_out, src_per_out=1.0, reset_below=0.0, out=None):
+    """``phase_lock`` with the channels linked (pg_phase_lock_linked): ``angle`` (n_ch, bins <= 4096, F_src) as in ``phase_lock``, read
+    in place from a polar tensor; ``ref_angle`` and ``ref_logmag``: the planes of ONE reference channel (the channel mean, in
+    phasegen.track), (bins, F_src) or (1, bins, F_src), dense -> (n_ch, bins, F_out), dense, in [-pi, pi].  The peaks, the regions
+    and the rotation are those ``phase_lock(ref_angle, ..., logmag=ref_logmag)`` forms, once, and every channel adds its own
+    analysis phase to that one rotation: the phase difference between any two channels is the analysis' own in every cell, so the
+    stereo image and the mono sum survive the stretch.  A channel equal to the reference gets ``phase_lock``'s bits;
+    src_per_out == 1.0 returns the analysis phase."""
+    who = "phase_lock_linked"
+    a_stride = _vocoder_plane(angle, "angle", who=who)
+    n_ch, bins, F_src = angle.shape
+    refs = []
+    for t, name in ((ref_angle, "ref_angle"), (ref_logmag, "ref_logmag")):
+        if torch.is_tensor(t) and t.dim() == 2:
+            t = t[None]
+        _vocoder_plane(t, name, who=who)
+        if tuple(t.shape) != (1, bins, F_src):
+            raise ValueError(f"{who}: {name} must be (bins, F_src) or (1, bins, F_src) = {(1, bins, F_src)}, got {tuple(t.shape)}")
+        refs.append(t)
+    F_out, src_per_out, reset_below = int(F_out), float(src_per_out), float(reset_below)
+    if F_out < 1:
+        raise ValueError(f"{who}: F_out must be positive, got {F_out}")
+    if not 0.0 < src_per_out < float("inf"):
+        raise ValueError(f"{who}: src_per_out must be finite and positive, got {src_per_out}")
+    if not 0.0 <= reset_below < float("inf"):
+        raise ValueError(f"{who}: reset_below must be finite and not negative, got {reset_below}")
+    out = _out(out, (n_ch, bins, F_out), angle.device, who)
+    a = _lib.PhaseLockLinkedArgs()
+    a.n_ch, a.bins, a.F_src, a.F_out, a.src_per_out, a.reset_below = n_ch, bins, F_src, F_out, src_per_out, reset_below
+    a.A, a.a_stride = angle.data_ptr(), a_stride
+    a.Aref, a.Mref = refs[0].data_ptr(), refs[1].data_ptr()
+    a.out = _dense(out, "out")
+    lib = _lib.load()
+    a.workspace, a.workspace_bytes = _workspace(_lock_ws, angle.device, lib.pg_workspace_bytes_phase_lock_linked(C.byref(a)), "workspace_bytes_phase_lock_linked")
+    _lib.check(lib.pg_phase_lock_linked(C.byref(a), _stream()), who)
+    return out
+
+
 def phase_spsi(logmag, n_fft, hop, bin0=1, out=None):
     """A phase from the magnitudes alone, in one pass (pg_phase_spsi; single-pass spectrogram inversion, Beauregard et al. 2015):
     ``logmag`` (n_ch, bins <= 4096, F) float32 on the device, on the OUTPUT frame grid, frames contiguous, rows F apart, the channel
@@ -1135,6 +1173,15 @@ def standardize_(x):
     lib = _lib.load()
     stats = moments(x)
     _lib.check(lib.pg_standardize(C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(stats.data_ptr()), _stream()), "standardize")
+    return stats
+
+
+def standardize_stats_(x, stats):
+    """``standardize_`` with the moments of ANOTHER reduction: x = (x - mean) / std in place with the two-double device tensor
+    ``stats`` = {mean, std} (``moments`` of a part of x, say), the same pg_standardize launch.  Returns ``stats``."""
+    if not (torch.is_tensor(stats) and stats.is_cuda and stats.dtype == torch.float64 and stats.numel() == 2 and stats.is_contiguous()):
+        raise TypeError("standardize_stats_: stats must be a dense device tensor of two float64 values")
+    _lib.check(_lib.load().pg_standardize(C.c_void_p(_dense(x, "x")), x.numel(), C.c_void_p(stats.data_ptr()), _stream()), "standardize")
     return stats
 
 

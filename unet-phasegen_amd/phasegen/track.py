@@ -28,7 +28,10 @@ phase="vocoder" (spectral join) is the phase vocoder, the comparator of every ti
 along the output frames by its measured advance (ops.phase_vocoder); it needs no model.  phase="vocoder_locked" is that vocoder with
 identity phase locking (ops.phase_lock: only the peaks of a frame advance, every other bin follows its peak).  A stretched track has
 no reference waveform, so ``evaluate_stretch`` reports ``metrics.consistency`` instead: how far the spectrogram of each phase source's result
-lands from the magnitudes that were imposed.
+lands from the magnitudes that were imposed.  On its own that locking works per channel, each with its own peaks and its own
+rotation, so the phases of one source in two channels drift apart; ``link_channels=True`` gives all channels ONE rotation, that of
+the channel mean (ops.phase_lock_linked), so the analysis' inter-channel phase differences -- the stereo image, and how the channels
+sum to mono -- survive the stretch, and ``evaluate_stretch`` then also reports the consistency of the channel mean ("mid_metrics").
 
 phase="spsi" (spectral join) is single-pass spectrogram inversion (ops.phase_spsi): a phase from the output grid's magnitudes ALONE
 -- peaks advance by their interpolated frequency, every other bin follows its peak -- with no analysis phase, no weights and no
@@ -72,7 +75,7 @@ GL_INITS = ("noise", "spsi")
 
 class _Analysis:
     """What every phase source shares: the track at ``sr`` (a2: (channels, a_len)), the clip plan and the clips' [log1p|z| ; angle]."""
-    __slots__ = ("a2", "mono", "n_ch", "a_len", "T", "step", "n_clips", "bins", "pol", "plan", "stretch")
+    __slots__ = ("a2", "mono", "n_ch", "a_len", "T", "step", "n_clips", "bins", "pol", "plan", "stretch", "link")
 
 
 def _load(audio, osr, sr, res_type):
@@ -87,6 +90,7 @@ def _load(audio, osr, sr, res_type):
         raise ValueError(f"reconstruct_track: audio must be (samples,) or (channels, samples), got {tuple(a.shape)}")
     an = _Analysis()
     an.mono = a.dim() == 1
+    an.link = False
     an.a2 = (a[None] if an.mono else a).contiguous()
     an.n_ch, an.a_len = an.a2.shape
     return an
@@ -180,10 +184,16 @@ def spectral_plan(a_len, frames, hop_length, overlap_frames, stretch=1.0):
     return SpectralPlan(sf, Vf, a_out, n_clips, F_out, F_src, hop_length * (F_src - 1))
 
 
-def _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch):
-    """resample -> ONE whole-track STFT per channel -> standardise -> polar: an.pol (n_ch, 2, bins, F_src) on the global frame grid."""
+def _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch, link=False):
+    """resample -> ONE whole-track STFT per channel -> standardise -> polar: an.pol (n_ch, 2, bins, F_src) on the global frame grid.
+    ``link``: one more row is analysed, the channel mean (the reference of ops.phase_lock_linked), standardised with the SAME
+    (mean, std) as the channels -- the track's own moments are those of the channels alone -- so an.pol is (n_ch + 1, 2, bins, F_src)
+    and an.pol[:n_ch] has the bits it has without the option."""
     an = _load(audio, osr, sr, res_type)
-    a2, n_ch, a_len = an.a2, an.n_ch, an.a_len
+    an.link = bool(link)
+    n_ch, a_len = an.n_ch, an.a_len
+    a2 = torch.cat([an.a2, an.a2.mean(0, keepdim=True)]) if an.link else an.a2      # (rows, a_len); one channel: the mean is the channel
+    rows = a2.shape[0]
     an.stretch = float(stretch)
     an.plan = pl = spectral_plan(a_len, frames, hop_length, overlap_frames, stretch)
     an.n_clips, an.bins = pl.n_clips, n_fft // 2
@@ -191,16 +201,19 @@ def _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, o
     with torch.cuda.device(dev), torch.no_grad():
         if stats is not None:
             # channel c is the region [c a_len, (c + 1) a_len) of the flat buffer; the crop is zero past its end (pg_stft_crops)
-            begin = torch.arange(n_ch, dtype=torch.int64) * a_len
+            begin = torch.arange(rows, dtype=torch.int64) * a_len
             an.pol = ops.stft_crops(a2.reshape(-1), begin.to(dev), (begin + a_len).to(dev), pl.n_src, n_fft, hop_length, polar=True,
                                     stats=(stats[0], stats[1]))
             return an
         # the track's own moments (zero tail included) need the unnormalised tensor: three launches on the zero-padded track
-        padded = torch.zeros(n_ch, pl.n_src, device=dev, dtype=torch.float32)
+        padded = torch.zeros(rows, pl.n_src, device=dev, dtype=torch.float32)
         n = min(a_len, pl.n_src)
         padded[:, :n] = a2[:, :n]
-        x = ops.stft(padded, n_fft, hop_length)                                               # (n_ch, 2, bins, F_src)
-        ops.standardize_(x)
+        x = ops.stft(padded, n_fft, hop_length)                                               # (rows, 2, bins, F_src)
+        if an.link:
+            ops.standardize_stats_(x, ops.moments(x[:n_ch]))                                  # the channels' moments, for the mean row too
+        else:
+            ops.standardize_(x)
         an.pol = ops.polar(x)
     return an
 
@@ -218,19 +231,24 @@ def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_bel
     untrimmed ISTFT of it under that phase (n_ch, hop * (F_out - 1)).  Called under the device and no_grad."""
     pl, n_ch, bins = an.plan, an.n_ch, an.bins
     spo = 1.0 / an.stretch
-    logmag = an.pol[:, 0]                                                                     # (n_ch, bins, F_src), read in place
+    pol = an.pol[:n_ch]                                                                       # (linked: row n_ch is the channel mean)
+    logmag = pol[:, 0]                                                                        # (n_ch, bins, F_src), read in place
     if phase == "zero":
         ph = torch.zeros(n_ch, bins, pl.F_out, device=logmag.device)                          # (the join of zeros is zero)
     elif phase == "original":
-        ph = ops.phase_join(ops.spec_clips(an.pol[:, 1], pl.n_clips, frames, pl.sf, spo), pl.sf)
+        ph = ops.phase_join(ops.spec_clips(pol[:, 1], pl.n_clips, frames, pl.sf, spo), pl.sf)
     elif phase == "vocoder":
         # the analysis' own phase, propagated along the output grid by its measured advance (no model, no clips)
-        ph = ops.phase_vocoder(an.pol[:, 1], pl.F_out, spo, logmag=logmag,
+        ph = ops.phase_vocoder(pol[:, 1], pl.F_out, spo, logmag=logmag,
                                reset_below=VOCODER_RESET_BELOW if reset_below is None else reset_below)
     elif phase == "vocoder_locked":
         # ... with identity phase locking: only the peaks of a frame advance, every other bin takes its peak's rotation
-        ph = ops.phase_lock(an.pol[:, 1], pl.F_out, spo, logmag=logmag,
-                            reset_below=VOCODER_RESET_BELOW if reset_below is None else reset_below)
+        # (linked: ONE rotation for all channels, the channel mean's, so the analysis' inter-channel phase differences survive)
+        floor = VOCODER_RESET_BELOW if reset_below is None else reset_below
+        if an.link:
+            ph = ops.phase_lock_linked(pol[:, 1], an.pol[n_ch, 1], an.pol[n_ch, 0], pl.F_out, spo, reset_below=floor)
+        else:
+            ph = ops.phase_lock(pol[:, 1], pl.F_out, spo, logmag=logmag, reset_below=floor)
     elif phase == "spsi":
         # from the magnitudes on the output grid alone: they come first, and nothing of the analysis' phase is read
         mag = ops.spec_clips(logmag, 1, pl.F_out, pl.F_out, spo)[0]
@@ -286,6 +304,13 @@ def _check_join(who, join, stretch, phase_list):
     return stretch
 
 
+def _check_link(who, link_channels, join, phase_list):
+    """link_channels: only the locked vocoder under the spectral join has channels to link"""
+    if link_channels and (join != "spectral" or "vocoder_locked" not in phase_list):
+        raise ValueError(f"{who}: link_channels needs join='spectral' and phase 'vocoder_locked', got join {join!r} and {tuple(phase_list)!r}")
+    return bool(link_channels)
+
+
 def peak_normalize(audio):
     """utils.py:42 for a whole track on the device: audio (samples,) or (channels, samples) divided by its joint peak -- the second
     launch of pg_stitch over one clip per channel, so ``peak_normalize(reconstruct_track(..., normalize=False))`` has the bits of
@@ -321,7 +346,7 @@ def _keyword_options(impl, later=None, **options):
 
 
 def _reconstruct_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phase, normalize,
-                       join, stretch):
+                       join, stretch, link_channels):
     """``reconstruct_track`` with its keyword-only options spelled out."""
     if phase not in ("unet", "original", "zero") + GRID_PHASES:
         raise ValueError(f"reconstruct_track: phase must be 'unet', 'original', 'zero', 'vocoder', 'vocoder_locked' or 'spsi', got {phase!r}")
@@ -330,8 +355,9 @@ def _reconstruct_track(model, audio, n_fft, hop_length, frames, overlap_frames, 
     if clip_batch < 1:
         raise ValueError("reconstruct_track: clip_batch must be positive")
     stretch = _check_join("reconstruct_track", join, stretch, (phase,))
+    link = _check_link("reconstruct_track", link_channels, join, (phase,))
     if join == "spectral":
-        an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch)
+        an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch, link)
         out = _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize)
         return out[0] if an.mono else out
     an = _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type)
@@ -339,7 +365,7 @@ def _reconstruct_track(model, audio, n_fft, hop_length, frames, overlap_frames, 
     return out[0] if an.mono else out
 
 
-@_keyword_options(_reconstruct_track, join="waveform", stretch=1.0)
+@_keyword_options(_reconstruct_track, later={"link_channels": False}, join="waveform", stretch=1.0)
 def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None,
                       osr=None, sr=16000, res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True):
     """audio (samples,) or (channels, samples), host array or device tensor, at ``sr`` -- or at ``osr`` when given (resampled to
@@ -358,7 +384,11 @@ def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, over
     phase="vocoder_locked" (the same conditions) is that vocoder with identity phase locking (ops.phase_lock): only the spectral peaks
     of a frame advance and every other bin keeps its analysis phase relation to its peak -- the stretch to use without weights.
     phase="spsi" (the same conditions) is single-pass spectrogram inversion (ops.phase_spsi): a phase from the output grid's
-    magnitudes alone, the model-free baseline that reads nothing of the analysis' phase."""
+    magnitudes alone, the model-free baseline that reads nothing of the analysis' phase.
+    ``link_channels=False`` (``reconstruct_track.later_options``; spectral join and phase="vocoder_locked" only, else ValueError): all
+    channels take ONE rotation, that of their mean (ops.phase_lock_linked), instead of one each, so the phase difference between two
+    channels stays the analysis' own in every cell and the stereo image and the mono sum survive the stretch; mono input gives the
+    bits of the unlinked call."""
 
 
 def _evaluate_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phases, gl_iters,
@@ -413,19 +443,9 @@ def evaluate_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap
     its single-pass inversion (``griffin_lim_batch``'s ``init``).  The report records ``gl_init``."""
 
 
-def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
-                     res_type="kaiser_best", clip_batch=64, phases=("unet", "vocoder", "zero"), reset_below=None, floor=1e-10,
-                     return_audio=False):
-    """The quality report of a STRETCHED track, which has no reference waveform to be compared with: ONE spectral analysis (as
-    ``reconstruct_track(join="spectral", stretch=stretch)``), then for every entry of ``phases`` -- "unet" (the model's phase),
-    "vocoder" (ops.phase_vocoder with the floor ``reset_below``; None: ``VOCODER_RESET_BELOW``), "zero" (none), "vocoder_locked"
-    (ops.phase_lock with the same floor), "spsi" (ops.phase_spsi on the resampled magnitudes alone) -- one synthesis and
-    ``metrics.consistency`` of its untrimmed ISTFT output against the resampled log-magnitude plane it was made from: how far the
-    spectrogram of the result lands from the magnitudes that were imposed.
-    -> {"n_samples", "n_out", "sr", "stretch", "n_clips", "reset_below", "metrics": {phase: dict}} and, with ``return_audio``,
-    "audio": {phase: un-normalised device tensor of round(a_len * stretch) samples per channel}.  The "unet" and "zero" audio has the
-    bits of ``reconstruct_track(..., normalize=False, join="spectral", stretch=stretch)``.  ``model`` may be None when "unet" is not
-    asked for."""
+def _evaluate_stretch(model, audio, stretch, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phases,
+                      reset_below, floor, return_audio, link_channels):
+    """``evaluate_stretch`` with its keyword-only option spelled out."""
     phases = tuple(phases)
     for p in phases:
         if p not in STRETCH_PHASES:
@@ -440,19 +460,46 @@ def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=1
     if not 0.0 <= reset_below < math.inf:
         raise ValueError(f"evaluate_stretch: reset_below must be finite and not negative, got {reset_below}")
     stretch = _check_join("evaluate_stretch", "spectral", stretch, phases)
-    an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch)
+    link = _check_link("evaluate_stretch", link_channels, "spectral", phases)
+    an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch, link)
     res = {"n_samples": int(an.a_len), "n_out": int(an.plan.a_out), "sr": int(sr), "stretch": stretch, "n_clips": int(an.n_clips),
            "reset_below": reset_below, "metrics": {}}
+    if link:
+        res["link_channels"], res["mid_metrics"] = True, {}
     if return_audio:
         res["audio"] = {}
     with torch.cuda.device(an.a2.device), torch.no_grad():
+        if link:        # the mid signal's imposed magnitudes: the mean row's plane, resampled as the channels' are
+            mid_mag = ops.spec_clips(an.pol[an.n_ch:, 0], 1, an.plan.F_out, an.plan.F_out, 1.0 / an.stretch)[0]
         for p in phases:
             mag, full = _invert_spectral(an, model, p, hop_length, frames, clip_batch, reset_below)
             out = _trim_spectral(an, full, False)
             res["metrics"][p] = metrics.consistency(mag, full, n_fft, hop_length, floor)
+            if link:
+                res["mid_metrics"][p] = metrics.consistency(mid_mag, full.mean(0, keepdim=True), n_fft, hop_length, floor)
             if return_audio:
                 res["audio"][p] = out[0] if an.mono else out
     return res
+
+
+@_keyword_options(_evaluate_stretch, later={"link_channels": False})
+def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
+                     res_type="kaiser_best", clip_batch=64, phases=("unet", "vocoder", "zero"), reset_below=None, floor=1e-10,
+                     return_audio=False):
+    """The quality report of a STRETCHED track, which has no reference waveform to be compared with: ONE spectral analysis (as
+    ``reconstruct_track(join="spectral", stretch=stretch)``), then for every entry of ``phases`` -- "unet" (the model's phase),
+    "vocoder" (ops.phase_vocoder with the floor ``reset_below``; None: ``VOCODER_RESET_BELOW``), "zero" (none), "vocoder_locked"
+    (ops.phase_lock with the same floor), "spsi" (ops.phase_spsi on the resampled magnitudes alone) -- one synthesis and
+    ``metrics.consistency`` of its untrimmed ISTFT output against the resampled log-magnitude plane it was made from: how far the
+    spectrogram of the result lands from the magnitudes that were imposed.
+    -> {"n_samples", "n_out", "sr", "stretch", "n_clips", "reset_below", "metrics": {phase: dict}} and, with ``return_audio``,
+    "audio": {phase: un-normalised device tensor of round(a_len * stretch) samples per channel}.  The "unet" and "zero" audio has the
+    bits of ``reconstruct_track(..., normalize=False, join="spectral", stretch=stretch)``.  ``model`` may be None when "unet" is not
+    asked for.  Keyword-only option (``evaluate_stretch.later_options``): ``link_channels=False``, as in ``reconstruct_track``
+    ("vocoder_locked" must be among ``phases``, which alone it changes); with it the report also holds "link_channels": True and
+    "mid_metrics": {phase: ``metrics.consistency`` of the channel mean of the untrimmed output against the resampled log-magnitude
+    plane of the channel mean of the input}, for every phase asked for: what the channels' sum to mono lost.  Without it the report
+    has the keys above and no others."""
 
 
 def pitch_ratio(semitones, max_denominator=1024):
@@ -467,18 +514,19 @@ def pitch_ratio(semitones, max_denominator=1024):
 
 
 def pitch_shift(model, audio, semitones, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
-                res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True):
+                res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True, *, link_channels=False):
     """Pitch shift by ``semitones`` (within two octaves) without a change of tempo: the track is stretched by 2 ** (semitones / 12)
     through the spectral join (``reconstruct_track(join="spectral", stretch=...)``: same pitch, longer or shorter) and played back
     faster or slower by the same ratio (``preproc.resample`` by q / p, see ``pitch_ratio`` for the error in cents), then trimmed or
     zero-padded to the input's length at ``sr``.  ``phase``: "unet", "vocoder", "vocoder_locked", "spsi" or "zero", as in
-    ``reconstruct_track``.
+    ``reconstruct_track``; ``link_channels`` (keyword only) is forwarded to it.
     -> float32 device tensor shaped like the input at ``sr``."""
     stretch, ratio = pitch_ratio(semitones)
+    _check_link("pitch_shift", link_channels, "spectral", (phase,))
     a = preproc.resample(audio, osr, sr, res_type=res_type) if osr is not None else audio
     a_len = int(a.shape[-1])
     out = reconstruct_track(model, a, n_fft, hop_length, frames, overlap_frames, stats, None, sr, res_type, clip_batch, phase,
-                            normalize=False, join="spectral", stretch=stretch)
+                            normalize=False, join="spectral", stretch=stretch, link_channels=link_channels)
     if ratio != 1:
         out = preproc.resample(out, ratio.numerator, ratio.denominator, res_type=res_type)
     if out.shape[-1] >= a_len:

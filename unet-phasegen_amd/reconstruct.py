@@ -30,6 +30,11 @@ weights (and the model's when ``--weight`` is given), written as JSON.
 frequency, every other bin follows its peak), the model-free baseline; it needs no ``--weight`` and implies the spectral join, like
 the vocoders.  ``--report_phases`` accepts ``spsi`` with ``--join spectral``, and ``--gl_init spsi`` starts the ``griffinlim`` report
 phase from that inversion instead of from noise.
+
+``--link_channels`` (with ``--stereo`` and ``--phase vocoder_locked``; for ``--stretch``, ``--pitch`` and ``--stretch_report``) gives
+all channels ONE rotation, that of their mean, instead of one each (``phasegen.ops.phase_lock_linked``): the phase difference
+between the channels stays the analysis' own, so the stereo image and the sum to mono survive the stretch.  The stretch report then
+also holds ``mid_metrics``, the consistency of the channels' mean.
 """
 import argparse
 import json
@@ -78,6 +83,8 @@ def main():
                              "single-pass inversion of the magnitudes alone (all three imply --join spectral), or none")
     parser.add_argument("--stretch_report", default=None, metavar="PATH",
                         help="with --stretch: write a JSON report of the spectrogram consistency of every phase source")
+    parser.add_argument("--link_channels", action="store_true",
+                        help="with --phase vocoder_locked: one rotation for all channels, that of their mean (keeps the stereo image)")
     args = parser.parse_args()
     if args.phase == "unet" and args.weight is None:
         parser.error("the following arguments are required: --weight")
@@ -92,6 +99,8 @@ def main():
         parser.error("--phase {} needs --join spectral".format(args.phase))
     if args.phase != "unet" and args.report is not None:
         parser.error("--report measures the model's phase: it needs --phase unet")
+    if args.link_channels and args.phase != "vocoder_locked":
+        parser.error("--link_channels needs --phase vocoder_locked")
     if args.stretch_report is not None and args.stretch is None:
         parser.error("--stretch_report needs --stretch")
     if args.stretch_report is not None and args.pitch is not None:
@@ -140,14 +149,16 @@ def main():
     report = None
     stretch_report = None
     if args.pitch is not None:
-        out = track.pitch_shift(model, audio, args.pitch, phase=args.phase, **kw)
+        out = track.pitch_shift(model, audio, args.pitch, phase=args.phase, link_channels=args.link_channels, **kw)
     elif args.stretch_report is not None:
         # (the locked vocoder and spsi are reported when they are asked for; the other modes' reports stay as they were)
         others = [p for p in track.STRETCH_PHASES if p not in (args.phase, "vocoder_locked", "spsi") and (p != "unet" or model is not None)]
-        stretch_report = track.evaluate_stretch(model, audio, args.stretch, phases=[args.phase] + others, return_audio=True, **kw)
+        stretch_report = track.evaluate_stretch(model, audio, args.stretch, phases=[args.phase] + others, return_audio=True,
+                                                link_channels=args.link_channels, **kw)
         out = track.peak_normalize(stretch_report.pop("audio")[args.phase])
     elif args.report is None:
-        out = track.reconstruct_track(model, audio, phase=args.phase, join=join, stretch=1.0 if args.stretch is None else args.stretch, **kw)
+        out = track.reconstruct_track(model, audio, phase=args.phase, join=join, stretch=1.0 if args.stretch is None else args.stretch,
+                                      link_channels=args.link_channels, **kw)
     else:
         report = track.evaluate_track(model, audio, phases=phases, gl_iters=args.gl_iters, return_audio=True, join=join, gl_init=args.gl_init, **kw)
         out = track.peak_normalize(report.pop("audio")["unet"])
@@ -169,6 +180,9 @@ def main():
             json.dump(stretch_report, f, indent=1)
         print("Stretch report (consistency): " + "; ".join("{} spectral convergence {:.4f}, LSD {:.2f} dB".format(
             p, m["spectral_convergence"], m["lsd_db"]) for p, m in stretch_report["metrics"].items()))
+        if "mid_metrics" in stretch_report:
+            print("Stretch report (consistency of the channel mean): " + "; ".join("{} spectral convergence {:.4f}".format(
+                p, m["spectral_convergence"]) for p, m in stretch_report["mid_metrics"].items()))
 
 
 if __name__ == "__main__":
