@@ -15,6 +15,46 @@
  *     streams / threads are independent.  A workspace belongs to ONE stream at a time.
  *   - every call is asynchronous on the hipStream_t passed as `void* stream`; no internal syncs.
  *   - return 0 on success, <0 = PG_ERR_* (bad argument), >0 = hipError_t from the launch.
+ *
+ * Non-finite values
+ *   A NaN or +-inf in an input is ordinary data to every entry point: no call fails on it, and what it does to the outputs is
+ *   part of the contract.  The entry points that state a rule of their own keep it (pg_stitch's count, pg_phase_join's fallback,
+ *   pg_phase_vocoder's q(x) and "a NaN in M does not reset", pg_phase_lock / _linked / pg_phase_spsi, slot 5 of the compare kernels).
+ *   For every other one -- the conv entry points, pg_conv_fwd_h, pg_bn_fwd / _bwd, pg_clipnorm_fwd, pg_loss_fwd_bwd, pg_adam_step,
+ *   pg_cast_rows_bf16, pg_stft, pg_stft_crops, pg_polar, pg_istft, pg_gl_project, pg_ola_nt, pg_moments / pg_standardize,
+ *   pg_resample, pg_spec_clips -- let ref(x) be the entry point's documented formula evaluated in IEEE arithmetic on the input
+ *   with ONE element replaced by NaN, +inf or -inf, where
+ *     - an activation is the select x >= 0 ? x : slope * x, its derivative x > 0 ? 1 : slope (a NaN in a dgrad's mask source is a
+ *       comparison that fails: the factor is the slope, nothing else happens);
+ *     - zero padding, the zeros between the frames of a transposed convolution and the samples outside a signal's ends are "no term",
+ *       not a product with zero;
+ *     - a maximum (the peak of pg_istft / pg_ola_nt with normalize) that sees a NaN is a NaN: the whole signal becomes NaN;
+ *     - z = re + 1j * im of pg_polar / pg_gl_project is data.py:40's arithmetic: an infinite im makes the real part NaN on its way;
+ *     - a term of a transform whose coefficient is exactly zero (cos or sin of a multiple of pi / 2: every bin at taps 0 and n_fft / 2,
+ *       the imaginary part of the Nyquist bin) may carry the non-finite value or not: a fast transform never forms that product.
+ *   R1, nothing is swallowed: an output element that is non-finite in ref is non-finite on the device.  No exceptions.  (Finite
+ *       against non-finite is what is promised, not NaN against inf: the bf16x3 split answers NaN for inf, inf - inf.)
+ *   R2, nothing spreads: an output element that is finite in ref and equal there to ref of the clean input has the bits of the same
+ *       call on the clean input, and a clean call after a poisoned one on the same workspace has the clean bits.  Exceptions:
+ *     C1  zeros that are multiplied in.  The convolution kernels read padding, inserted zeros and the frames past the end of the
+ *         partner operand as 0.0 and multiply, and 0 * NaN = 0 * inf = NaN.  A non-finite WEIGHT w[o, c, j] may therefore turn
+ *         every frame of every sample of its output channel o (forward) or input channel c (dgrad) into NaN, not only the frames
+ *         whose window holds tap j on a real sample; a non-finite x[b, c, t] (dy[b, o, t]) of a WGRAD may turn every tap of
+ *         dw[., c, .] (dw[o, ., .]) into NaN, not only the taps that pair frame t with a frame of dy (x).  Never another channel
+ *         (pair).  All kernel families, all precisions, pg_conv_fwd_h included.  Skipping those products would put a select on
+ *         every fragment load of the benchmarked kernels.
+ *     C2  zero-weight phantom taps.  The im2col transposed form (conv_t: the ConvTranspose1d forward and the Conv1d dgrad where the
+ *         raw-window kernels do not apply) runs its taps phase by phase and rounds k up to stride * ceil(k / stride) taps of zero
+ *         weight where the stride does not divide k.  A non-finite input frame t (x of the forward, dy of the dgrad) may turn the
+ *         frames t stride - pad + j, j = k .. stride ceil(k / stride) - 1, of every channel of its sample into NaN: the one or two
+ *         frames behind its window.
+ *   Cones (what ref makes non-finite), for orientation: conv forward / dgrad -- the frames of one sample whose window holds the
+ *   element, every channel (a weight: one channel, every sample); wgrad -- one channel's taps; BatchNorm -- the channel (clipnorm:
+ *   the row) with its save_* and running buffers; loss -- two of the three losses and one element of dpred; Adam -- that element's
+ *   p / m / v; STFT -- every bin of the frames that hold the sample; ISTFT -- the samples the frame overlaps (normalize: the
+ *   signal); resample -- the outputs whose taps hold the sample; spec_clips -- the output frames that read the source frame with
+ *   a non-zero weight; moments / standardize -- everything.  fp32 denormals are not covered by this section.
+ *   tests/_nonfinite.py, tests/test_nonfinite_host.py and tests/test_z_nonfinite_gpu.py hold every entry point to it.
  */
 #ifndef PHASEGEN_H
 #define PHASEGEN_H

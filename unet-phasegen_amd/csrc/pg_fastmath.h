@@ -28,6 +28,10 @@ __device__ __forceinline__ float pg_atan01(float a) {
 
 // np.angle / atan2f semantics for finite arguments: signed zeros select the branch (atan2(+0, -x) = +pi, atan2(-0, -x) = -pi,
 // atan2(+-0, -0) = +-pi), the axes are exact (0, +-pi/2, +-pi as float32).
+// Non-finite arguments: a NaN in either argument returns NaN (one unordered compare and a select behind the finite path, whose
+// bits it leaves alone).  An infinite argument returns a finite angle as atan2f does: one infinity against a finite value lands on
+// its axis (0, +-pi/2, +-pi); (+-inf, +-inf) gives inf * rcp(inf) = NaN in the ratio and so NaN, where atan2f says +-pi/4, +-3pi/4.
+// The magnitude beside it is +inf in every such cell, so the cell as a whole stays non-finite (include/phasegen.h, "Non-finite values").
 __device__ __forceinline__ float pg_atan2(float y, float x) {
     float ax = fabsf(x), ay = fabsf(y);
     float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
@@ -38,7 +42,8 @@ __device__ __forceinline__ float pg_atan2(float y, float x) {
     float r = pg_atan01(a);
     if (ay > ax) r = 1.57079632679489662f - r;
     if (__float_as_uint(x) >> 31) r = 3.14159265358979324f - r;
-    return copysignf(r, y);
+    r = copysignf(r, y);
+    return (ax != ax || ay != ay) ? __builtin_nanf("") : r;           // fmaxf / fminf drop a NaN: hand it through as atan2f does
 }
 
 // log1p(x) for x >= 0: log(u) + ((1 + x) - u) / u with u = fl(1 + x).  The rounding error of the addition, (1 + x) - u = x - (u - 1),

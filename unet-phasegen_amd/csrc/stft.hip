@@ -48,16 +48,24 @@ __device__ __forceinline__ float hann(int k, int n) { return 0.5f - 0.5f * cospi
 // accurate relative to its value, so this form is within a few u of the window at every tap.
 __device__ __forceinline__ float hann_tap(int k, int n) { const float s = sinpif((float)k / (float)n); return s * s; }
 
+// max(a, b) of two values that are >= 0, or NaN with the sign bit clear (fabsf results and maxima of them): read as unsigned integers
+// their bit patterns order like the values and every NaN lies above +inf, so a NaN survives the reduction where fmaxf would drop it
+// (include/phasegen.h, "Non-finite values": a peak that saw a NaN is a NaN).  One v_max_u32 for one v_max_f32.
+__device__ __forceinline__ float absmax(float a, float b) {
+    const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
+    return __uint_as_float(ua > ub ? ua : ub);
+}
+
 // Maximum of mx over a workgroup of WAVES waves, returned to every thread (a maximum is exact in any order): shuffle butterfly, one
 // LDS slot per wave, fold.  red[] is free again after the caller's next barrier.
 template <int WAVES> __device__ __forceinline__ float block_max(float mx, float* red) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    for (int off = 32; off > 0; off >>= 1) mx = absmax(mx, __shfl_xor(mx, off, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
     lds_barrier();
     mx = red[0];
 #pragma unroll
-    for (int i = 1; i < WAVES; ++i) mx = fmaxf(mx, red[i]);
+    for (int i = 1; i < WAVES; ++i) mx = absmax(mx, red[i]);
     return mx;
 }
 
@@ -525,9 +533,9 @@ __global__ __launch_bounds__(256) void istft_peak_normalize_kernel(float* audio,
     __shared__ float red[4];
     const int sig = blockIdx.y;
     float mx = 0.f;
-    for (int i = threadIdx.x; i < nparts; i += 256) mx = fmaxf(mx, partial[(long)sig * nparts + i]);
+    for (int i = threadIdx.x; i < nparts; i += 256) mx = absmax(mx, partial[(long)sig * nparts + i]);
     const float pk = block_max<4>(mx, red);
-    if (!(pk > 1.17549435e-38f)) return;
+    if (pk <= 1.17549435e-38f) return;                       // (a NaN peak goes on: the whole row becomes NaN)
     float* row = audio + (long)sig * len;
     if ((len & 3) == 0 && (((uintptr_t)audio) & 15) == 0) {
         for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < (len >> 2); i += gridDim.x * blockDim.x) {
@@ -1002,7 +1010,7 @@ __device__ __forceinline__ float ola_finalize(float4& acc, int ip, int N, int ho
     acc.y = wss[1] > 1.17549435e-38f ? acc.y / wss[1] : acc.y;
     acc.z = wss[2] > 1.17549435e-38f ? acc.z / wss[2] : acc.z;
     acc.w = wss[3] > 1.17549435e-38f ? acc.w / wss[3] : acc.w;
-    return fmaxf(fmaxf(fabsf(acc.x), fabsf(acc.y)), fmaxf(fabsf(acc.z), fabsf(acc.w)));
+    return absmax(absmax(fabsf(acc.x), fabsf(acc.y)), absmax(fabsf(acc.z), fabsf(acc.w)));
 }
 
 // partial[] layout of this path, per signal: [groups] peaks of the main kernel's finalised samples, then [groups] peaks of the seams
@@ -1057,7 +1065,7 @@ __global__ __launch_bounds__(WT, 4) void istft_ola_w_kernel(const pg_istft_args 
             if (blk >= NW && !last) { *(float4*)(tl + (pr - NW * hop)) = acc; continue; }        // tail: the next group's seam adds it
             if (i0 < 0 || i0 >= len) continue;                                                  // trimmed away
             if (blk < OW_HB && !first) { *(float4*)(out + i0) = acc; continue; }                 // head: partial sum, finalised at the seam
-            mx = fmaxf(mx, ola_finalize(acc, ip, N, hop, a.n_frames, wc));
+            mx = absmax(mx, ola_finalize(acc, ip, N, hop, a.n_frames, wc));
             *(float4*)(out + i0) = acc;
         }
         mx = block_max<NW>(mx, red);                          // (its barrier also: the regions are the next group's work space)
@@ -1085,7 +1093,7 @@ __global__ __launch_bounds__(256) void istft_seam_kernel(const pg_istft_args a, 
         float4 acc = *(const float4*)(out + i0);
         const float4 t = *(const float4*)(tl + pr);
         acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w;
-        mx = fmaxf(mx, ola_finalize(acc, ip, N, hop, a.n_frames, wc));
+        mx = absmax(mx, ola_finalize(acc, ip, N, hop, a.n_frames, wc));
         *(float4*)(out + i0) = acc;
     }
     mx = block_max<4>(mx, red);
@@ -1162,7 +1170,7 @@ __global__ __launch_bounds__(256) void istft_ola4_kernel(const pg_istft_args a, 
 #pragma unroll
             for (int j = 0; j < OLA_SPT; ++j) {
                 y[j] = wss[j] > 1.17549435e-38f ? acc[j] / wss[j] : acc[j];
-                mx = fmaxf(mx, fabsf(y[j]));
+                mx = absmax(mx, fabsf(y[j]));
             }
             *(float4*)out = make_float4(y[0], y[1], y[2], y[3]);
         } else {
@@ -1178,7 +1186,7 @@ __global__ __launch_bounds__(256) void istft_ola4_kernel(const pg_istft_args a, 
                 }
                 const float yv = wss > 1.17549435e-38f ? sum / wss : sum;
                 out[j] = yv;
-                mx = fmaxf(mx, fabsf(yv));
+                mx = absmax(mx, fabsf(yv));
             }
         }
     }
@@ -1199,7 +1207,7 @@ __global__ __launch_bounds__(256) void gl_project_kernel(const pg_gl_args a) {
         float re = S[e], im = S[total + e];
         pg_complex_from_parts(re, im);                      // np.angle on re + 1j*im
         const float mod = hypotf(re, im), m = mag[e];
-        const float c = mod > 0.f ? re / mod : 1.f, s = mod > 0.f ? im / mod : 0.f;   // angle(0) = 0
+        const float c = mod == 0.f ? 1.f : re / mod, s = mod == 0.f ? 0.f : im / mod;   // angle(0) = 0; a NaN modulus stays a NaN (mod > 0 would take it for 0)
         const float nr = m * c, ni = m * s;
         if (so) { so[e] = nr; so[total + e] = ni; }
         x[e] = nr;
@@ -1228,7 +1236,7 @@ __global__ __launch_bounds__(256) void ola_nt_kernel(pg_ola_args a, unsigned* pe
         }
         const float yv = wss > 1.17549435e-38f ? s / wss : s;
         a.audio[i] = yv;
-        mx = fmaxf(mx, fabsf(yv));
+        mx = absmax(mx, fabsf(yv));
     }
     mx = block_max<4>(mx, scratch);                           // (launched with 256 threads)
     if (threadIdx.x == 0) atomicMax(peak, __float_as_uint(mx));

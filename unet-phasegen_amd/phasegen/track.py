@@ -440,7 +440,9 @@ def evaluate_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap
     when "unet" is not asked for.  Keyword-only options (``evaluate_track.options`` and ``.later_options``): ``join="waveform"`` or ``"spectral"``, as in
     ``reconstruct_track`` ("griffinlim" is not available under "spectral"; "spsi", ops.phase_spsi on the track's magnitudes, only
     there: ``REPORT_PHASES``); ``gl_init="noise"`` or ``"spsi"``: every clip's Griffin-Lim starts from noise or from the ISTFT of
-    its single-pass inversion (``griffin_lim_batch``'s ``init``).  The report records ``gl_init``."""
+    its single-pass inversion (``griffin_lim_batch``'s ``init``).  The report records ``gl_init``.
+    Every synthesis is finite-checked before it is measured: raises ValueError("Audio buffer is not finite everywhere"), as
+    ``reconstruct_track`` does, and returns no report, when a sample of any of them is not finite."""
 
 
 def _evaluate_stretch(model, audio, stretch, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phases,
@@ -499,7 +501,9 @@ def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=1
     ("vocoder_locked" must be among ``phases``, which alone it changes); with it the report also holds "link_channels": True and
     "mid_metrics": {phase: ``metrics.consistency`` of the channel mean of the untrimmed output against the resampled log-magnitude
     plane of the channel mean of the input}, for every phase asked for: what the channels' sum to mono lost.  Without it the report
-    has the keys above and no others."""
+    has the keys above and no others.
+    Every synthesis is finite-checked before it is measured: raises ValueError("Audio buffer is not finite everywhere"), as
+    ``reconstruct_track`` does, and returns no report, when one of the round(a_len * stretch) samples of any of them is not finite."""
 
 
 def pitch_ratio(semitones, max_denominator=1024):
