@@ -19,10 +19,11 @@
  * Non-finite values
  *   A NaN or +-inf in an input is ordinary data to every entry point: no call fails on it, and what it does to the outputs is
  *   part of the contract.  The entry points that state a rule of their own keep it (pg_stitch's count, pg_phase_join's fallback,
- *   pg_phase_vocoder's q(x) and "a NaN in M does not reset", pg_phase_lock / _linked / pg_phase_spsi, slot 5 of the compare kernels).
+ *   pg_phase_vocoder's q(x) and "a NaN in M does not reset", pg_phase_lock / _linked / pg_phase_spsi, slot 5 of the compare kernels,
+ *   pg_hpss's total order).
  *   For every other one -- the conv entry points, pg_conv_fwd_h, pg_bn_fwd / _bwd, pg_clipnorm_fwd, pg_loss_fwd_bwd, pg_adam_step,
  *   pg_cast_rows_bf16, pg_stft, pg_stft_crops, pg_polar, pg_istft, pg_gl_project, pg_ola_nt, pg_moments / pg_standardize,
- *   pg_resample, pg_spec_clips -- let ref(x) be the entry point's documented formula evaluated in IEEE arithmetic on the input
+ *   pg_resample, pg_spec_clips, pg_ola_stretch -- let ref(x) be the entry point's documented formula evaluated in IEEE arithmetic on the input
  *   with ONE element replaced by NaN, +inf or -inf, where
  *     - an activation is the select x >= 0 ? x : slope * x, its derivative x > 0 ? 1 : slope (a NaN in a dgrad's mask source is a
  *       comparison that fails: the factor is the slope, nothing else happens);
@@ -53,7 +54,7 @@
  *   the row) with its save_* and running buffers; loss -- two of the three losses and one element of dpred; Adam -- that element's
  *   p / m / v; STFT -- every bin of the frames that hold the sample; ISTFT -- the samples the frame overlaps (normalize: the
  *   signal); resample -- the outputs whose taps hold the sample; spec_clips -- the output frames that read the source frame with
- *   a non-zero weight; moments / standardize -- everything.  fp32 denormals are not covered by this section.
+ *   a non-zero weight; ola_stretch -- the outputs one of whose covering frames reads the sample; moments / standardize -- everything.  fp32 denormals are not covered by this section.
  *   tests/_nonfinite.py, tests/test_nonfinite_host.py and tests/test_z_nonfinite_gpu.py hold every entry point to it.
  */
 #ifndef PHASEGEN_H
@@ -647,6 +648,86 @@ typedef struct pg_phase_spsi_args {
 } pg_phase_spsi_args;                            /* 72 bytes */
 int64_t pg_workspace_bytes_phase_spsi(const pg_phase_spsi_args* a);   /* host function of n_ch, bins, F; negative = error code */
 int     pg_phase_spsi(const pg_phase_spsi_args* a, void* stream);
+
+/* pg_hpss: harmonic / percussive split of a log-magnitude plane by median filtering (Fitzgerald 2010, binary masks), the first half
+ * of the transient-preserving stretch (Driedger, Mueller & Ewert 2014; phasegen/track.py, transients="ola"): the harmonic plane goes
+ * through the chosen phase source, the percussive plane through pg_ola_stretch.  Struct of its own, PG_VERSION unchanged; the
+ * reference has no counterpart; the arithmetic below is the contract.
+ *   M: (n_ch, bins, F) fp32, frames fastest, rows F apart, channels m_stride >= bins F elements apart (pol[:, 0] of a polar tensor by
+ *   pointer and stride).  win_t, win_f: the window along time and along frequency, odd, 1 <= win <= PG_HPSS_MAX_WIN (= 31).
+ *   -> harm, perc (n_ch, bins, F) each, dense fp32.
+ *   Order.  key(x) = bits(x) ^ (bits(x) >> 31 ? 0xFFFFFFFF : 0x80000000) as a uint32: the IEEE total order on the bit pattern.  -0
+ *   sorts below +0, a positive NaN above +inf, a negative NaN below -inf; equal keys are equal bits, so "the element of rank r" of
+ *   a window has well-defined bits.
+ *   Medians, per channel, with ht = (win_t - 1) / 2 and hf = (win_f - 1) / 2:
+ *     H[b][g] = the element of rank ht by key among M[b][clamp(g + d, 0, F - 1)], d = -ht .. ht,
+ *     P[b][g] = the element of rank hf by key among M[clamp(b + d, 0, bins - 1)][g], d = -hf .. hf
+ *   (edge replication keeps every window odd).
+ *   Split.  A cell is harmonic iff key(H[b][g]) >= key(P[b][g]).  A harmonic cell gives harm = M[b][g] (its bits) and perc = +0.0f;
+ *   any other cell gives perc = M[b][g] and harm = +0.0f.  The planes are the project's log1p magnitudes, so a zero is silence, and
+ *   a median commutes with any increasing map, so the decision is the one a linear-magnitude HPSS with binary masks makes.
+ *   Consequences.  Every cell lands in exactly one plane, bit for bit.  win_t == win_f == 1 makes everything harmonic.  A plane
+ *   constant along time with win_f == 1 is all harmonic, and so is a plane constant along frequency with win_t == 1 (the tie goes
+ *   to harm).  A channel's result does not depend on n_ch, on its position, or on how the kernel tiles the plane.  Non-finite
+ *   values are ordered data (the Order above): nothing else happens to them.
+ *   Kernel: one workgroup per (channel, 32 bins, 64 frames) tile, walked grid-stride; the tile and its halos of hf rows and ht frames
+ *   are staged through LDS once, as keys, with global reads along the frames; both medians are selection networks over LDS reads.
+ *   16-byte stores where harm, perc and F allow, element by element otherwise (same bits); 64-bit index arithmetic; no atomics.
+ *   There is no workspace: the library allocates nothing and keeps nothing.
+ *   Errors (host side, before any launch, in this order): NULL args / M / harm / perc PG_ERR_NULL; non-positive sizes, an even or
+ *   out-of-range window, a plane or output beyond 2^62 elements, m_stride < bins F PG_ERR_SHAPE; M, harm or perc not 4-byte aligned
+ *   PG_ERR_ALIGN. */
+#define PG_HPSS_MAX_WIN 31
+typedef struct pg_hpss_args {
+    int32_t n_ch, bins;
+    int64_t F;                                   /* frames per row                                                      */
+    int32_t win_t, win_f;                        /* odd, 1 <= win <= PG_HPSS_MAX_WIN                                    */
+    const float* M; int64_t m_stride;            /* (n_ch, bins, F), channels m_stride >= bins F elements apart         */
+    float* harm;                                 /* (n_ch, bins, F), dense                                              */
+    float* perc;                                 /* (n_ch, bins, F), dense                                              */
+} pg_hpss_args;                                  /* 56 bytes */
+int     pg_hpss(const pg_hpss_args* a, void* stream);
+
+/* pg_ola_stretch: time-domain overlap-add at a time ratio, the second half of the transient-preserving stretch: the frames of a
+ * short window are RELOCATED, not stretched, so a click stays a click.  Struct of its own, PG_VERSION unchanged; the reference has no
+ * counterpart; the arithmetic below is the contract.
+ *   x: (n_sig, n_in) fp32, rows x_stride >= n_in apart.  win: a DEVICE table of w = win_len floats, each finite and >= 0
+ *   (pg_ola_window fills a host copy of the default; the table is not read on the host: a negative or non-finite entry is the
+ *   caller's error and the formula says what happens).  base: optional (NULL), (n_sig, n_out), rows base_stride >= n_out apart,
+ *   added to the result.  -> y (n_sig, n_out), rows y_stride >= n_out apart.
+ *   Frames.  Output frame g >= 0 covers the output samples g hop - w/2 .. g hop + w/2 - 1; its centre in the input is
+ *     c_g = (int64) rint((double)(g hop) * src_per_out)             round half to even; a centre beyond 2^62 is outside every signal.
+ *   There is no upper limit on g, so y[t] does not depend on n_out.
+ *   Output sample t.  Over the covering frames in ascending g, with j = t - g hop + w/2 and s = c_g + j - w/2, in fp32, nothing
+ *   contracted:
+ *     den = fl(den + win[j])                       for every covering frame,
+ *     num = fl(num + fl(win[j] * x[s]))            only where 0 <= s < n_in: a sample outside the signal is "no term";
+ *     r = den > 0 ? num / den : 0                  one IEEE division;       y[t] = base ? fl(base[t] + r) : r.
+ *   Consequences.  At most w / hop + 1 frames cover a sample.  With src_per_out == 1 every term reads x[t], so
+ *   |r - x[t]| <= (2 k + 2) 2^-24 |x[t]| for k covering frames (k products and k - 1 additions above, k - 1 additions below, the
+ *   division; all weights non-negative): at most 12 2^-24 at the default 256 / 64 (k = 4 where hop divides w).  A row's result does not depend on n_sig or on its
+ *   position.  A non-finite x[s] reaches exactly the outputs whose covering frames read it: R1 and R2 of the Non-finite section
+ *   hold, with "no term" outside the ends.
+ *   Kernel: 4 output samples per thread, 16-byte stores where y and y_stride allow and sample by sample otherwise (same bits); the
+ *   window table is kept in LDS; neighbouring threads of one frame read neighbouring s.  64-bit index arithmetic; no atomics; no
+ *   workspace: the library allocates nothing and keeps nothing.
+ *   Errors (host side, before any launch, in this order): NULL args / x / win / y PG_ERR_NULL; non-positive sizes, win_len odd or
+ *   outside 2 .. 4096, hop outside 1 .. win_len / 2, src_per_out not finite or <= 0, signals beyond 2^62 elements, x_stride < n_in,
+ *   y_stride < n_out, (with base) base_stride < n_out PG_ERR_SHAPE; x, win, base or y not 4-byte aligned PG_ERR_ALIGN.
+ * pg_ola_window (HOST): win_host[j] = (float)(0.5 - 0.5 cos(2 pi j / win_len)), j < win_len, the periodic Hann window, formed in
+ *   double and rounded once; NULL PG_ERR_NULL, win_len odd or outside 2 .. 4096 PG_ERR_SHAPE.  At hop = win_len / 4 its shifted
+ *   copies sum to 2 wherever every covering frame exists. */
+typedef struct pg_ola_stretch_args {
+    int32_t n_sig, win_len, hop, _pad0;          /* win_len even, 2 <= win_len <= 4096; 1 <= hop <= win_len / 2         */
+    int64_t n_in, n_out;
+    double  src_per_out;                         /* input samples per output sample = 1 / stretch; finite, > 0         */
+    const float* x;    int64_t x_stride;         /* (n_sig, n_in)                                                       */
+    const float* win;                            /* DEVICE table of win_len floats, each finite and >= 0                */
+    const float* base; int64_t base_stride;      /* optional (NULL): (n_sig, n_out), added to the result                */
+    float* y;          int64_t y_stride;         /* (n_sig, n_out)                                                      */
+} pg_ola_stretch_args;                           /* 96 bytes */
+int     pg_ola_stretch(const pg_ola_stretch_args* a, void* stream);
+int     pg_ola_window(float* win_host, int32_t win_len);
 
 /* How far a reconstruction is from its source, reduced on the device: the sums from which SI-SDR / SNR (waveforms) and spectral
  * convergence / log-spectral distance (spectrograms) are formed on the host (phasegen/metrics.py).  The reference has no counterpart

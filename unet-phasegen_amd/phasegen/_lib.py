@@ -212,6 +212,23 @@ class PhaseSpsiArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+HPSS_MAX_WIN = 31     # PG_HPSS_MAX_WIN
+
+
+class HpssArgs(C.Structure):
+    """pg_hpss_args: harmonic / percussive split of a log-magnitude plane by median filtering (include/phasegen.h)."""
+    _fields_ = [("n_ch", C.c_int32), ("bins", C.c_int32), ("F", C.c_int64), ("win_t", C.c_int32), ("win_f", C.c_int32),
+                ("M", C.c_void_p), ("m_stride", C.c_int64), ("harm", C.c_void_p), ("perc", C.c_void_p)]
+
+
+class OlaStretchArgs(C.Structure):
+    """pg_ola_stretch_args: time-domain overlap-add of a short window at a time ratio (include/phasegen.h)."""
+    _fields_ = [("n_sig", C.c_int32), ("win_len", C.c_int32), ("hop", C.c_int32), ("_pad0", C.c_int32),
+                ("n_in", C.c_int64), ("n_out", C.c_int64), ("src_per_out", C.c_double),
+                ("x", C.c_void_p), ("x_stride", C.c_int64), ("win", C.c_void_p),
+                ("base", C.c_void_p), ("base_stride", C.c_int64), ("y", C.c_void_p), ("y_stride", C.c_int64)]
+
+
 class WaveCompareArgs(C.Structure):
     """pg_wave_compare_args: six sums per signal of a reference / estimate pair of waveforms (include/phasegen.h)."""
     _fields_ = [("n_signals", C.c_int32), ("_pad0", C.c_int32), ("n", C.c_int64),
@@ -282,6 +299,9 @@ SYMBOLS = {
     "pg_phase_lock_linked": (C.c_int, [C.POINTER(PhaseLockLinkedArgs), C.c_void_p]),
     "pg_workspace_bytes_phase_spsi": (C.c_int64, [C.POINTER(PhaseSpsiArgs)]),
     "pg_phase_spsi": (C.c_int, [C.POINTER(PhaseSpsiArgs), C.c_void_p]),
+    "pg_hpss": (C.c_int, [C.POINTER(HpssArgs), C.c_void_p]),
+    "pg_ola_stretch": (C.c_int, [C.POINTER(OlaStretchArgs), C.c_void_p]),
+    "pg_ola_window": (C.c_int, [C.c_void_p, C.c_int32]),
     "pg_workspace_bytes_wave_compare": (C.c_int64, [C.POINTER(WaveCompareArgs)]),
     "pg_wave_compare": (C.c_int, [C.POINTER(WaveCompareArgs), C.c_void_p]),
     "pg_workspace_bytes_spec_compare": (C.c_int64, [C.POINTER(SpecCompareArgs)]),

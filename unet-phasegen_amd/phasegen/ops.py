@@ -1055,6 +1055,102 @@ def phase_spsi(logmag, n_fft, hop, bin0=1, out=None):
     return out
 
 
+def hpss(logmag, win_t=17, win_f=17, out=None):
+    """Harmonic / percussive split of a log-magnitude plane by median filtering (pg_hpss; Fitzgerald 2010 with binary masks):
+    ``logmag`` (n_ch, bins, F) float32 on the device, frames contiguous, rows F apart, the channel stride free (``pol[:, 0]`` of a
+    polar tensor is read in place) -> (harm, perc), (n_ch, bins, F) each, dense.  A cell goes to ``harm`` when the median of the
+    ``win_t`` frames around it in its row is at least the median of the ``win_f`` bins around it in its frame (IEEE total order on the
+    bits, edges replicated), else to ``perc``; the other plane holds +0.0 there, so every cell lands in exactly one plane bit for
+    bit.  Windows are odd and at most 31.  ``out``: a (harm, perc) pair of dense tensors to fill."""
+    who = "hpss"
+    m_stride = _vocoder_plane(logmag, "logmag", who=who)
+    n_ch, bins, F = logmag.shape
+    win_t, win_f = int(win_t), int(win_f)
+    for w, name in ((win_t, "win_t"), (win_f, "win_f")):
+        if not (1 <= w <= _lib.HPSS_MAX_WIN and w % 2 == 1):
+            raise ValueError(f"{who}: {name} must be odd and within 1 .. {_lib.HPSS_MAX_WIN}, got {w}")
+    if out is not None and not (isinstance(out, (tuple, list)) and len(out) == 2):
+        raise ValueError(f"{who}: out must be a (harm, perc) pair")
+    harm = _out(None if out is None else out[0], (n_ch, bins, F), logmag.device, who)
+    perc = _out(None if out is None else out[1], (n_ch, bins, F), logmag.device, who)
+    a = _lib.HpssArgs()
+    a.n_ch, a.bins, a.F, a.win_t, a.win_f = n_ch, bins, F, win_t, win_f
+    a.M, a.m_stride = logmag.data_ptr(), m_stride
+    a.harm, a.perc = _dense(harm, "harm"), _dense(perc, "perc")
+    _lib.check(_lib.load().pg_hpss(C.byref(a), _stream()), who)
+    return harm, perc
+
+
+_ola_windows = {}        # (device, win_len) -> device copy of pg_ola_window's output (read-only)
+
+
+def ola_window_host(win_len):
+    """pg_ola_window: the periodic Hann window float32(0.5 - 0.5 cos(2 pi j / win_len)), built on the host in double (no GPU needed)."""
+    import numpy as np
+    win = np.empty(max(int(win_len), 0), np.float32)
+    _lib.check(_lib.load().pg_ola_window(win.ctypes.data_as(C.c_void_p) if win.size else None, int(win_len)), "ola_window")
+    return win
+
+
+def _ola_window(win_len, device):
+    key = (torch.device(device), win_len)
+    win = _ola_windows.get(key)
+    if win is None:
+        win = _ola_windows[key] = torch.from_numpy(ola_window_host(win_len)).to(device)
+    return win
+
+
+def _ola_rows(t, name, who):
+    """(n,) or (n_sig, n) float32 on the device, samples contiguous, the row stride free -> the 2-D view"""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() in (1, 2)):
+        raise ValueError(f"{who}: {name} must be a 1-D or 2-D float32 device tensor")
+    _on_current_device(t, name)
+    t2 = t[None] if t.dim() == 1 else t
+    if min(t2.shape) < 1:
+        raise ValueError(f"{who}: empty {name} {tuple(t.shape)}")
+    if (t2.shape[1] > 1 and t2.stride(1) != 1) or (t2.shape[0] > 1 and t2.stride(0) < t2.shape[1]):
+        raise ValueError(f"{who}: samples of {name} must be contiguous and rows must not overlap (strides {t.stride()})")
+    return t2
+
+
+def ola_stretch(x, n_out, src_per_out=1.0, win_len=256, hop=64, base=None, out=None):
+    """Time-domain overlap-add at a time ratio (pg_ola_stretch): x (n_in,) or (n_sig, n_in) float32 on the device, samples
+    contiguous, the row stride free -> (..., n_out).  Output frame g, ``win_len`` samples of a periodic Hann window around output
+    sample g * hop, is the input around sample rint(g * hop * src_per_out) (src_per_out = 1 / stretch), weighted, and every output
+    sample is the weighted sum over the frames that cover it divided by the sum of their weights: the frames are moved, not
+    stretched, so a click stays a click.  src_per_out == 1.0 returns x to a few ulps.  ``base`` (shaped like the result, rows free):
+    added to the result in the same launch.  The window table is built once per (device, win_len)."""
+    who = "ola_stretch"
+    x2 = _ola_rows(x, "x", who)
+    n_sig, n_in = x2.shape
+    n_out, src_per_out, win_len, hop = int(n_out), float(src_per_out), int(win_len), int(hop)
+    if n_out < 1:
+        raise ValueError(f"{who}: n_out must be positive, got {n_out}")
+    if not 0.0 < src_per_out < float("inf"):
+        raise ValueError(f"{who}: src_per_out must be finite and positive, got {src_per_out}")
+    if not (2 <= win_len <= 4096 and win_len % 2 == 0):
+        raise ValueError(f"{who}: win_len must be even and within 2 .. 4096, got {win_len}")
+    if not 1 <= hop <= win_len // 2:
+        raise ValueError(f"{who}: hop must be within 1 .. win_len / 2 = {win_len // 2}, got {hop}")
+    want = (n_out,) if x.dim() == 1 else (n_sig, n_out)
+    a = _lib.OlaStretchArgs()
+    if base is not None:
+        if not torch.is_tensor(base) or tuple(base.shape) != want:
+            raise ValueError(f"{who}: base must be shaped like the result, {want}")
+        b2 = _ola_rows(base, "base", who)
+        a.base, a.base_stride = b2.data_ptr(), (b2.stride(0) if n_sig > 1 else n_out)
+    out = _out(out, want, x.device, who, rows=True)
+    o2 = out[None] if out.dim() == 1 else out
+    if n_sig > 1 and o2.stride(0) < n_out:
+        raise ValueError(f"{who}: rows of out overlap (strides {out.stride()})")
+    a.n_sig, a.win_len, a.hop, a.n_in, a.n_out, a.src_per_out = n_sig, win_len, hop, n_in, n_out, src_per_out
+    a.x, a.x_stride = x2.data_ptr(), (x2.stride(0) if n_sig > 1 else n_in)
+    a.win = _ola_window(win_len, x.device).data_ptr()
+    a.y, a.y_stride = o2.data_ptr(), (o2.stride(0) if n_sig > 1 else n_out)
+    _lib.check(_lib.load().pg_ola_stretch(C.byref(a), _stream()), who)
+    return out
+
+
 _compare_ws = _StreamCache()
 _caches.append(_compare_ws)
 

@@ -37,6 +37,13 @@ phase="spsi" (spectral join) is single-pass spectrogram inversion (ops.phase_sps
 -- peaks advance by their interpolated frequency, every other bin follows its peak -- with no analysis phase, no weights and no
 iteration: the baseline a predicted phase has to beat, and the only comparator that uses nothing a stretched spectrogram lacks.
 ``evaluate_track(gl_init="spsi")`` starts Griffin-Lim from it instead of from noise.
+
+``transients="ola"`` (spectral join) keeps the clicks of a stretched track clicks (Driedger, Mueller & Ewert 2014).  Resampling the
+magnitudes along time spreads every onset over ``stretch`` times as many frames, and no phase can put it back together.  With the
+option the log-magnitude plane is split by median filtering into a harmonic and a percussive plane (ops.hpss, ``HPSS_WIN``); the
+harmonic plane goes through the chosen phase source exactly as the whole plane does without the option, the percussive plane is
+inverted on the SOURCE grid with the analysis' own phase and moved to the output grid in the time domain by overlap-add of a short
+window (ops.ola_stretch, ``TRANSIENT_WINDOW`` / ``TRANSIENT_HOP``), which relocates transients instead of stretching them.
 """
 import collections
 import fractions
@@ -224,15 +231,42 @@ VOCODER_RESET_BELOW = 0.2
 STRETCH_PHASES = ("unet", "vocoder", "zero", "vocoder_locked", "spsi")
 VOCODER_PHASES = ("vocoder", "vocoder_locked")                    # the analysis' own phase, propagated: no model, spectral join only
 GRID_PHASES = VOCODER_PHASES + ("spsi",)                          # computed on the track's frame grid: no model, spectral join only
+TRANSIENTS = (None, "ola")
+HPSS_WIN = (17, 17)                                               # ops.hpss windows (frames, bins) of transients="ola"
+TRANSIENT_WINDOW = 256                                            # ops.ola_stretch window and hop of the percussive part:
+TRANSIENT_HOP = 64                                                # 16 ms and 4 ms at 16 kHz
 
 
-def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below=None):
+def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below=None, transients=None):
     """One phase source -> (mag, audio): the log-magnitude plane on the output grid (n_ch, bins, F_out) and the un-normalised,
-    untrimmed ISTFT of it under that phase (n_ch, hop * (F_out - 1)).  Called under the device and no_grad."""
+    untrimmed ISTFT of it under that phase (n_ch, hop * (F_out - 1)).  Called under the device and no_grad.
+    ``transients="ola"``: the phase source sees the harmonic part of the plane only and the percussive part comes back through the
+    time domain (``_add_transients``); ``mag`` stays the FULL plane on the output grid, what the result is meant to show."""
     pl, n_ch, bins = an.plan, an.n_ch, an.bins
     spo = 1.0 / an.stretch
     pol = an.pol[:n_ch]                                                                       # (linked: row n_ch is the channel mean)
-    logmag = pol[:, 0]                                                                        # (n_ch, bins, F_src), read in place
+    if transients is not None:
+        # all rows are split, the linked mean row too: the reference's magnitudes are its own harmonic part.  The cells handed to
+        # the percussive side are zeros in `harm` and fall under the reset floor by themselves.
+        harm, perc = ops.hpss(an.pol[:, 0], *HPSS_WIN)
+        mag, audio = _invert_plane(an, model, phase, hop_length, frames, clip_batch, reset_below, pol, harm[:n_ch], harm[n_ch:])
+        audio = _add_transients(an, hop_length, pol, perc[:n_ch], audio)                      # ("ola": the one way there is)
+        return ops.spec_clips(pol[:, 0], 1, pl.F_out, pl.F_out, spo)[0], audio
+    return _invert_plane(an, model, phase, hop_length, frames, clip_batch, reset_below, pol, pol[:, 0], an.pol[n_ch:, 0])
+
+
+def _add_transients(an, hop_length, pol, perc, audio):
+    """The percussive plane (n_ch, bins, F_src) under the analysis' own phase, inverted on the source grid and moved onto the output
+    grid by overlap-add of a short window, added to the harmonic ``audio`` (n_ch, hop * (F_out - 1)) in the same launch."""
+    p_audio = ops.istft(perc, pol[:, 1], hop_length, mode=0, normalize=False)                 # (n_ch, hop * (F_src - 1))
+    return ops.ola_stretch(p_audio, audio.shape[1], 1.0 / an.stretch, TRANSIENT_WINDOW, TRANSIENT_HOP, base=audio)
+
+
+def _invert_plane(an, model, phase, hop_length, frames, clip_batch, reset_below, pol, logmag, ref_logmag):
+    """``_invert_spectral`` for one log-magnitude plane ``logmag`` (n_ch, bins, F_src) -- the analysis' own, read in place, or its
+    harmonic part -- and, linked, the plane of the channel mean ``ref_logmag`` (1, bins, F_src)."""
+    pl, n_ch, bins = an.plan, an.n_ch, an.bins
+    spo = 1.0 / an.stretch
     if phase == "zero":
         ph = torch.zeros(n_ch, bins, pl.F_out, device=logmag.device)                          # (the join of zeros is zero)
     elif phase == "original":
@@ -246,7 +280,7 @@ def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_bel
         # (linked: ONE rotation for all channels, the channel mean's, so the analysis' inter-channel phase differences survive)
         floor = VOCODER_RESET_BELOW if reset_below is None else reset_below
         if an.link:
-            ph = ops.phase_lock_linked(pol[:, 1], an.pol[n_ch, 1], an.pol[n_ch, 0], pl.F_out, spo, reset_below=floor)
+            ph = ops.phase_lock_linked(pol[:, 1], an.pol[n_ch, 1], ref_logmag[0], pl.F_out, spo, reset_below=floor)
         else:
             ph = ops.phase_lock(pol[:, 1], pl.F_out, spo, logmag=logmag, reset_below=floor)
     elif phase == "spsi":
@@ -279,12 +313,12 @@ def _trim_spectral(an, audio, normalize):
     return out
 
 
-def _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize, reset_below=None):
+def _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize, reset_below=None, transients=None):
     """One phase source -> the track (channels, a_out) through the spectral join: clip windows of the log-magnitude plane, forward,
     ONE phase per global frame (ops.phase_join; phase="vocoder": ops.phase_vocoder on the analysis' phase instead), ONE ISTFT with
     the plane's own magnitudes; raises when a sample is not finite."""
     with torch.cuda.device(an.a2.device), torch.no_grad():
-        _mag, audio = _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below)
+        _mag, audio = _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below, transients)
         return _trim_spectral(an, audio, normalize)
 
 
@@ -311,6 +345,15 @@ def _check_link(who, link_channels, join, phase_list):
     return bool(link_channels)
 
 
+def _check_transients(who, transients, join):
+    """transients: None or "ola"; the split works on the whole-track plane, which only the spectral join has"""
+    if transients not in TRANSIENTS:
+        raise ValueError(f"{who}: transients must be None or 'ola', got {transients!r}")
+    if transients is not None and join != "spectral":
+        raise ValueError(f"{who}: transients={transients!r} needs join='spectral', got join {join!r}")
+    return transients
+
+
 def peak_normalize(audio):
     """utils.py:42 for a whole track on the device: audio (samples,) or (channels, samples) divided by its joint peak -- the second
     launch of pg_stitch over one clip per channel, so ``peak_normalize(reconstruct_track(..., normalize=False))`` has the bits of
@@ -322,31 +365,33 @@ def peak_normalize(audio):
     return out[0] if audio.dim() == 1 else out
 
 
-def _keyword_options(impl, later=None, **options):
+def _keyword_options(impl, later=None, newer=None, **options):
     """Decorator for the two public track functions: the decorated ``def`` states the POSITIONAL parameter list and the docstring --
     the list callers of the waveform-only functions have always seen, which stays as it is (``inspect.signature`` reports it) -- and
     the call itself goes to ``impl`` with, in addition, the keyword-only ``options`` (name=default), which may be passed by keyword
     only.  ``fn.options`` lists them.  ``later``: keyword-only options (name=default) added since callers began to compare
-    ``fn.options``, which therefore stays as it was; ``fn.later_options`` lists those."""
-    later = dict(later or {})
+    ``fn.options``, which therefore stays as it was; ``fn.later_options`` lists those.  ``newer``: the same once more, for options
+    added since callers began to compare ``fn.later_options``; ``fn.newer_options`` lists those."""
+    later, newer = dict(later or {}), dict(newer or {})
 
     def deco(fn):
         sig = inspect.signature(fn)
 
         @functools.wraps(fn)
         def call(*args, **kw):
-            opts = {k: kw.pop(k, d) for k, d in {**options, **later}.items()}
+            opts = {k: kw.pop(k, d) for k, d in {**options, **later, **newer}.items()}
             bound = sig.bind(*args, **kw)
             bound.apply_defaults()
             return impl(**bound.arguments, **opts)
         call.options = dict(options)
         call.later_options = dict(later)
+        call.newer_options = dict(newer)
         return call
     return deco
 
 
 def _reconstruct_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phase, normalize,
-                       join, stretch, link_channels):
+                       join, stretch, link_channels, transients):
     """``reconstruct_track`` with its keyword-only options spelled out."""
     if phase not in ("unet", "original", "zero") + GRID_PHASES:
         raise ValueError(f"reconstruct_track: phase must be 'unet', 'original', 'zero', 'vocoder', 'vocoder_locked' or 'spsi', got {phase!r}")
@@ -356,16 +401,17 @@ def _reconstruct_track(model, audio, n_fft, hop_length, frames, overlap_frames, 
         raise ValueError("reconstruct_track: clip_batch must be positive")
     stretch = _check_join("reconstruct_track", join, stretch, (phase,))
     link = _check_link("reconstruct_track", link_channels, join, (phase,))
+    transients = _check_transients("reconstruct_track", transients, join)
     if join == "spectral":
         an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch, link)
-        out = _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize)
+        out = _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize, transients=transients)
         return out[0] if an.mono else out
     an = _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type)
     out = _synthesise(an, model, phase, hop_length, clip_batch, normalize)
     return out[0] if an.mono else out
 
 
-@_keyword_options(_reconstruct_track, later={"link_channels": False}, join="waveform", stretch=1.0)
+@_keyword_options(_reconstruct_track, later={"link_channels": False}, newer={"transients": None}, join="waveform", stretch=1.0)
 def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None,
                       osr=None, sr=16000, res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True):
     """audio (samples,) or (channels, samples), host array or device tensor, at ``sr`` -- or at ``osr`` when given (resampled to
@@ -388,7 +434,13 @@ def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, over
     ``link_channels=False`` (``reconstruct_track.later_options``; spectral join and phase="vocoder_locked" only, else ValueError): all
     channels take ONE rotation, that of their mean (ops.phase_lock_linked), instead of one each, so the phase difference between two
     channels stays the analysis' own in every cell and the stereo image and the mono sum survive the stretch; mono input gives the
-    bits of the unlinked call."""
+    bits of the unlinked call.
+    ``transients=None`` (``reconstruct_track.newer_options``; spectral join only, else ValueError; with every phase and with
+    ``link_channels``): ``"ola"`` splits the log-magnitude plane into a harmonic and a percussive part by median filtering (ops.hpss,
+    ``HPSS_WIN``), hands the harmonic part to the chosen phase source in the plane's place, inverts the percussive part on the source
+    grid with the analysis' own phase and moves it onto the output grid in the time domain (ops.ola_stretch, ``TRANSIENT_WINDOW`` /
+    ``TRANSIENT_HOP``): onsets are relocated instead of stretched.  None: not one launch and not one bit differs from a call
+    without the keyword."""
 
 
 def _evaluate_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phases, gl_iters,
@@ -446,8 +498,8 @@ def evaluate_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap
 
 
 def _evaluate_stretch(model, audio, stretch, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phases,
-                      reset_below, floor, return_audio, link_channels):
-    """``evaluate_stretch`` with its keyword-only option spelled out."""
+                      reset_below, floor, return_audio, link_channels, transients):
+    """``evaluate_stretch`` with its keyword-only options spelled out."""
     phases = tuple(phases)
     for p in phases:
         if p not in STRETCH_PHASES:
@@ -463,18 +515,21 @@ def _evaluate_stretch(model, audio, stretch, n_fft, hop_length, frames, overlap_
         raise ValueError(f"evaluate_stretch: reset_below must be finite and not negative, got {reset_below}")
     stretch = _check_join("evaluate_stretch", "spectral", stretch, phases)
     link = _check_link("evaluate_stretch", link_channels, "spectral", phases)
+    transients = _check_transients("evaluate_stretch", transients, "spectral")
     an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch, link)
     res = {"n_samples": int(an.a_len), "n_out": int(an.plan.a_out), "sr": int(sr), "stretch": stretch, "n_clips": int(an.n_clips),
            "reset_below": reset_below, "metrics": {}}
     if link:
         res["link_channels"], res["mid_metrics"] = True, {}
+    if transients is not None:
+        res["transients"] = transients
     if return_audio:
         res["audio"] = {}
     with torch.cuda.device(an.a2.device), torch.no_grad():
         if link:        # the mid signal's imposed magnitudes: the mean row's plane, resampled as the channels' are
             mid_mag = ops.spec_clips(an.pol[an.n_ch:, 0], 1, an.plan.F_out, an.plan.F_out, 1.0 / an.stretch)[0]
         for p in phases:
-            mag, full = _invert_spectral(an, model, p, hop_length, frames, clip_batch, reset_below)
+            mag, full = _invert_spectral(an, model, p, hop_length, frames, clip_batch, reset_below, transients)
             out = _trim_spectral(an, full, False)
             res["metrics"][p] = metrics.consistency(mag, full, n_fft, hop_length, floor)
             if link:
@@ -484,7 +539,7 @@ def _evaluate_stretch(model, audio, stretch, n_fft, hop_length, frames, overlap_
     return res
 
 
-@_keyword_options(_evaluate_stretch, later={"link_channels": False})
+@_keyword_options(_evaluate_stretch, later={"link_channels": False}, newer={"transients": None})
 def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
                      res_type="kaiser_best", clip_batch=64, phases=("unet", "vocoder", "zero"), reset_below=None, floor=1e-10,
                      return_audio=False):
@@ -501,7 +556,9 @@ def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=1
     ("vocoder_locked" must be among ``phases``, which alone it changes); with it the report also holds "link_channels": True and
     "mid_metrics": {phase: ``metrics.consistency`` of the channel mean of the untrimmed output against the resampled log-magnitude
     plane of the channel mean of the input}, for every phase asked for: what the channels' sum to mono lost.  Without it the report
-    has the keys above and no others.
+    has the keys above and no others.  ``transients=None`` (``evaluate_stretch.newer_options``): ``"ola"`` synthesises every phase
+    as ``reconstruct_track(..., transients="ola")`` does and records "transients": "ola" in the report; the consistency is still
+    measured against the FULL plane's magnitudes on the output grid.
     Every synthesis is finite-checked before it is measured: raises ValueError("Audio buffer is not finite everywhere"), as
     ``reconstruct_track`` does, and returns no report, when one of the round(a_len * stretch) samples of any of them is not finite."""
 
@@ -518,19 +575,20 @@ def pitch_ratio(semitones, max_denominator=1024):
 
 
 def pitch_shift(model, audio, semitones, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
-                res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True, *, link_channels=False):
+                res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True, *, link_channels=False, transients=None):
     """Pitch shift by ``semitones`` (within two octaves) without a change of tempo: the track is stretched by 2 ** (semitones / 12)
     through the spectral join (``reconstruct_track(join="spectral", stretch=...)``: same pitch, longer or shorter) and played back
     faster or slower by the same ratio (``preproc.resample`` by q / p, see ``pitch_ratio`` for the error in cents), then trimmed or
     zero-padded to the input's length at ``sr``.  ``phase``: "unet", "vocoder", "vocoder_locked", "spsi" or "zero", as in
-    ``reconstruct_track``; ``link_channels`` (keyword only) is forwarded to it.
+    ``reconstruct_track``; ``link_channels`` and ``transients`` (keyword only) are forwarded to it.
     -> float32 device tensor shaped like the input at ``sr``."""
     stretch, ratio = pitch_ratio(semitones)
     _check_link("pitch_shift", link_channels, "spectral", (phase,))
+    _check_transients("pitch_shift", transients, "spectral")
     a = preproc.resample(audio, osr, sr, res_type=res_type) if osr is not None else audio
     a_len = int(a.shape[-1])
     out = reconstruct_track(model, a, n_fft, hop_length, frames, overlap_frames, stats, None, sr, res_type, clip_batch, phase,
-                            normalize=False, join="spectral", stretch=stretch, link_channels=link_channels)
+                            normalize=False, join="spectral", stretch=stretch, link_channels=link_channels, transients=transients)
     if ratio != 1:
         out = preproc.resample(out, ratio.numerator, ratio.denominator, res_type=res_type)
     if out.shape[-1] >= a_len:

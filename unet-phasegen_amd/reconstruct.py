@@ -35,6 +35,11 @@ phase from that inversion instead of from noise.
 all channels ONE rotation, that of their mean, instead of one each (``phasegen.ops.phase_lock_linked``): the phase difference
 between the channels stays the analysis' own, so the stereo image and the sum to mono survive the stretch.  The stretch report then
 also holds ``mid_metrics``, the consistency of the channels' mean.
+
+``--transients ola`` (for ``--stretch``, ``--pitch`` and ``--stretch_report``, with every ``--phase``) keeps onsets sharp: the
+magnitudes are split into a harmonic and a percussive part by median filtering (``phasegen.ops.hpss``), the harmonic part is
+stretched with the chosen phase and the percussive part is moved in the time domain by overlap-add of a 16 ms window
+(``phasegen.ops.ola_stretch``), which relocates clicks instead of stretching them.
 """
 import argparse
 import json
@@ -85,6 +90,9 @@ def main():
                         help="with --stretch: write a JSON report of the spectrogram consistency of every phase source")
     parser.add_argument("--link_channels", action="store_true",
                         help="with --phase vocoder_locked: one rotation for all channels, that of their mean (keeps the stereo image)")
+    parser.add_argument("--transients", choices=["ola"], default=None,
+                        help="with --stretch or --pitch: split off the percussive part and move it in the time domain by overlap-add "
+                             "(keeps onsets sharp)")
     args = parser.parse_args()
     if args.phase == "unet" and args.weight is None:
         parser.error("the following arguments are required: --weight")
@@ -101,6 +109,12 @@ def main():
         parser.error("--report measures the model's phase: it needs --phase unet")
     if args.link_channels and args.phase != "vocoder_locked":
         parser.error("--link_channels needs --phase vocoder_locked")
+    if args.transients is not None and args.stretch is None and args.pitch is None:
+        parser.error("--transients needs --stretch or --pitch")
+    if args.transients is not None and args.report is not None:
+        parser.error("--report compares against the input: it does not work with --transients")
+    if args.transients is not None and args.join == "waveform":
+        parser.error("--transients needs --join spectral")
     if args.stretch_report is not None and args.stretch is None:
         parser.error("--stretch_report needs --stretch")
     if args.stretch_report is not None and args.pitch is not None:
@@ -149,16 +163,16 @@ def main():
     report = None
     stretch_report = None
     if args.pitch is not None:
-        out = track.pitch_shift(model, audio, args.pitch, phase=args.phase, link_channels=args.link_channels, **kw)
+        out = track.pitch_shift(model, audio, args.pitch, phase=args.phase, link_channels=args.link_channels, transients=args.transients, **kw)
     elif args.stretch_report is not None:
         # (the locked vocoder and spsi are reported when they are asked for; the other modes' reports stay as they were)
         others = [p for p in track.STRETCH_PHASES if p not in (args.phase, "vocoder_locked", "spsi") and (p != "unet" or model is not None)]
         stretch_report = track.evaluate_stretch(model, audio, args.stretch, phases=[args.phase] + others, return_audio=True,
-                                                link_channels=args.link_channels, **kw)
+                                                link_channels=args.link_channels, transients=args.transients, **kw)
         out = track.peak_normalize(stretch_report.pop("audio")[args.phase])
     elif args.report is None:
         out = track.reconstruct_track(model, audio, phase=args.phase, join=join, stretch=1.0 if args.stretch is None else args.stretch,
-                                      link_channels=args.link_channels, **kw)
+                                      link_channels=args.link_channels, transients=args.transients, **kw)
     else:
         report = track.evaluate_track(model, audio, phases=phases, gl_iters=args.gl_iters, return_audio=True, join=join, gl_init=args.gl_init, **kw)
         out = track.peak_normalize(report.pop("audio")["unet"])
