@@ -80,7 +80,11 @@ enum { PG_ACT_NONE = 0, PG_ACT_LEAKY02 = 1 /* nn.LeakyReLU(0.2), model.py:80 */,
 /* One descriptor serves the six convolution entry points.  Geometry is always that of the FORWARD op:
  *   Conv1d          x (B,Cin,Lin) * w (Cout,Cin,k)  -> y (B,Cout,Lout),  Lout = (Lin + 2 pad - k)/stride + 1
  *   ConvTranspose1d x (B,Cin,Lin) * w (Cin,Cout,k)  -> y (B,Cout,Lout),  Lout = (Lin - 1) stride - 2 pad + k
- * bias is never used (model.py:65-69: use_bias == False under BatchNorm). */
+ * bias is never used (model.py:65-69: use_bias == False under BatchNorm).
+ * Every tensor a kernel READS through a buffer descriptor must span less than 2 GiB - 16 bytes from its pointer, the batch stride
+ * included ((B - 1) * bs + C * L) * 4 < 0x7ffffff0: x and dy where they are gathered, w, and the dgrad's dx_add and dx_ref (dx_ref
+ * only where dx_mask uses it).  A larger one is refused before any launch with PG_ERR_SHAPE ("... exceeds 2 GiB (31-bit buffer
+ * offsets)").  The tensors a call WRITES (y, y2, dx) are addressed with 64-bit arithmetic: their batch strides have no such limit. */
 struct pg_adam_args;
 typedef struct pg_conv_args {
     int32_t B, Cin, Cout, Lin, Lout, k, stride, pad;

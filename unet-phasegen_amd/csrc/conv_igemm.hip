@@ -321,6 +321,10 @@ int set_extents(IgemmParams& p) {
         if ((long)p.B * p.LP >= (1L << 24) - 64) return pg_fail(PG_ERR_UNSUPPORTED, "wgrad: B*L must stay below 2^24");
         p.inv_LP = 1.0f / (float)p.LP;
     }
+    // the dgrad epilogue reads the addend and the mask source through descriptors too, at 32-bit offsets b * bs + m * Ly + t
+    // (conv_common.h, Epi): both are (B, M, Ly) views like dx, and a load past a truncated extent would return 0 without a word
+    if ((p.add && !extent_bytes(p.B, p.add_bs, p.M, p.Ly)) || (p.ref && p.mask_mode && !extent_bytes(p.B, p.ref_bs, p.M, p.Ly)))
+        return pg_fail(PG_ERR_SHAPE, "conv: dx_add / dx_ref exceeds 2 GiB (31-bit buffer offsets)");
     p.a_vec = p.w && (((long)p.Q * p.k) & 3) == 0 && ((uintptr_t)p.w & 15) == 0;
     return PG_OK;
 }
