@@ -10,6 +10,7 @@ tests/test_dp_rccl_gpu.py has RCCL but one rank).
 Expected values: a single-process emulation of SURVEY.md §8(e) -- two replicas with per-replica BatchNorm statistics, each
 backward on its own shard, gradients summed, Adam with grad_scale = 1/2 -- built from the same kernels.  A two-term sum is
 order-independent, so the two-rank run must match it BIT FOR BIT, and both ranks must hold identical parameters."""
+import contextlib
 import os
 import socket
 
@@ -30,7 +31,9 @@ def shard(rank):
     return torch.from_numpy(detgen.make_batch(BPER, C, L, seed=1 + rank))          # bench.py's per-rank seeding
 
 
-def worker(rank, port, q, compress):
+def worker(rank, port, q, compress, rule=None):
+    """``rule`` = (name of a rule of tests/_order.py, rank): that rank runs its steps under the rule's delays, the other one
+    under the transparent wrappers alone -- the ranks are skewed against each other."""
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=WORLD)
     try:
@@ -41,13 +44,32 @@ def worker(rank, port, q, compress):
         tr = Trainer(model, grad_compress=compress)
         assert tr.world == WORLD and tr.overlap_adam and model.engine.contended
         batch = shard(rank).cuda()
+        order, note = contextlib.nullcontext(), None
+        if rule is not None:
+            import _order
+            name, on_rank = rule
+            # D from one unperturbed step of a spare trainer: BOTH ranks take it, its collectives pair up like the real ones
+            spare = Trainer(UNetModel(C, 2 * C).load_numpy(detgen.make_params(C, seed=0)), grad_compress=compress)
+            step_ms = _order.measure_step_ms(spare, [batch, batch])
+            d, passes = _order.delay_for(step_ms) if rank == on_rank else (0.0, 0)
+            if rank == on_rank:              # (a side stream on the hardware queue of the step's stream cannot be made late)
+                tr._side = _order.independent_of(torch.cuda.current_stream(), tr._side, passes)
+            order = _order.perturbed(_order.RULES[name] if rank == on_rank else _order.P0, torch.cuda.current_stream(), tr._side, passes)
         losses = []
-        for _ in range(STEPS):
-            losses.append(tr.step(batch).cpu().numpy().copy())
-            assert not tr.reducer.pending
+        with order as h:
+            for _ in range(STEPS):
+                if h is not None:
+                    h.begin_step()
+                losses.append(tr.step(batch).cpu().numpy().copy())
+                assert not tr.reducer.pending
         torch.cuda.synchronize()
+        if h is not None:
+            _order.check_log(h, tr, STEPS)
+            names = {h.main: "the step's", h.side: "_side"}
+            note = (f"rank {rank} under {h.rule}: unperturbed step {step_ms:.2f} ms, D = {d:.1f} ms ({passes} passes), {len(h.fired)} delayed "
+                    f"launches on {[names[st] for st in h.streams_fired_on()]}")
         q.put((rank, np.stack(losses), model.engine.arena.flat.cpu().numpy().copy(),
-               model.engine.arena.grad.cpu().numpy().copy()))
+               model.engine.arena.grad.cpu().numpy().copy(), note))
         dist.barrier()
     finally:
         dist.destroy_process_group()
@@ -83,22 +105,27 @@ def emulate(compress):
     return [np.stack(l) for l in losses], trs[0].engine.arena.flat.cpu().numpy(), total.cpu().numpy()
 
 
-@pytest.mark.parametrize("compress", [None, "bf16"])
-def test_two_ranks_real_engine_match_the_two_replica_emulation(compress):
+def run_ranks(compress, rule=None):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    procs = [ctx.Process(target=worker, args=(r, port, q, compress)) for r in range(WORLD)]
+    procs = [ctx.Process(target=worker, args=(r, port, q, compress, rule)) for r in range(WORLD)]
     for p in procs:
         p.start()
     got = {}
     for _ in range(WORLD):
-        rank, losses, flat, grad = q.get(timeout=300)
+        rank, losses, flat, grad, note = q.get(timeout=300)
         got[rank] = (losses, flat, grad)
+        if note:
+            print(note)
     for p in procs:
         p.join(timeout=120)
         assert p.exitcode == 0
-    want_losses, want_flat, want_grad = emulate(compress)
+    return got
+
+
+def assert_matches_the_emulation(got, want):
+    want_losses, want_flat, want_grad = want
     assert np.array_equal(got[0][1], got[1][1]), "ranks diverged"
     assert np.array_equal(got[0][2], got[1][2])
     for r in range(WORLD):
@@ -106,6 +133,15 @@ def test_two_ranks_real_engine_match_the_two_replica_emulation(compress):
     assert np.array_equal(got[0][2], want_grad)
     assert np.array_equal(got[0][1], want_flat)
     assert not np.array_equal(want_losses[0], want_losses[1])       # the shards really differ
+
+
+@pytest.mark.parametrize("compress", [None, "bf16"])
+def test_two_ranks_real_engine_match_the_two_replica_emulation(compress):
+    assert_matches_the_emulation(run_ranks(compress), emulate(compress))
+
+
+# (the cases that run one rank under a rule, against the same emulation and assertions, are collected with the rest of the step-order
+# module: tests/test_z_step_order_gpu.py::test_two_ranks_skewed_against_each_other_match_the_two_replica_emulation)
 
 
 def val_worker(rank, port, q):
