@@ -54,8 +54,67 @@
  *   the row) with its save_* and running buffers; loss -- two of the three losses and one element of dpred; Adam -- that element's
  *   p / m / v; STFT -- every bin of the frames that hold the sample; ISTFT -- the samples the frame overlaps (normalize: the
  *   signal); resample -- the outputs whose taps hold the sample; spec_clips -- the output frames that read the source frame with
- *   a non-zero weight; ola_stretch -- the outputs one of whose covering frames reads the sample; moments / standardize -- everything.  fp32 denormals are not covered by this section.
+ *   a non-zero weight; ola_stretch -- the outputs one of whose covering frames reads the sample; moments / standardize -- everything.
  *   tests/_nonfinite.py, tests/test_nonfinite_host.py and tests/test_z_nonfinite_gpu.py hold every entry point to it.
+ *
+ * Magnitude range
+ *   Every finite fp32 value, denormals and FLT_MAX included, is ordinary data: no call faults on it.  What the exponent of the data
+ *   does to the outputs is contract, in four rules for the entry points that are compositions of additions, products with constants,
+ *   FMAs, maxima, selects and positively homogeneous activations, and as a stated domain for the others.  ref64 is the entry point's
+ *   documented formula in float64 on the fp32 values actually stored; B is the error bound the entry point meets on data of order
+ *   one (for a convolution: 4 x that of sequential fp32 accumulation of the same operands, per element, relative to sum |a b|).
+ *   M1, scale equivariance.  Multiply every operand by an exact power of two.  While every operand element and every output of ref64
+ *       stays a normal fp32 number (or an exact zero; and a normal bf16 number where the mode casts), the outputs are the outputs of
+ *       the unscaled call times the product of the powers, BIT FOR BIT.  Outputs the formula makes scale-free keep their bits: a
+ *       normalised pg_istft / pg_ola_nt, pg_gl_project in S, the angle of pg_polar, pg_standardize, and the phases of pg_phase_vocoder,
+ *       pg_phase_lock, pg_phase_lock_linked (magnitude plane and reset_below scaled together) and pg_phase_spsi.  No kernel holds an
+ *       absolute epsilon, a narrower intermediate or a flush on these paths.
+ *   M2, gradual underflow.  Operands normal, outputs of ref64 below FLT_MIN: |out - ref64| <= B 2^e + R 2^-150, 2^e the total scale
+ *       and R the number of roundings on the output's path ((2 t + 1) K + 3 for a convolution whose GEMM is K deep, t = 3 for the
+ *       bf16x3 split and 1 otherwise).  Nothing is flushed to zero.
+ *   M3, denormal operands.  The fp32 paths read them as they are: M1 / M2's bound against ref64 on the stored values.
+ *       The bf16, bf16x3 and pg_conv_fwd_h paths KEEP them as well (measured on an MI355X, gfx950, 2026-10-20: every element of every
+ *       row, no operand flushed to zero): the conversion rounds a denormal fp32 operand to the bf16 denormal (RNE; the smallest is
+ *       2^-133) and the bf16 MFMA multiplies it as it is, so the outputs are ref64 on the bf16-rounded operands within B.  For bf16x3
+ *       that is float32(hi) + float32(lo) with lo = bf16(x - hi), which has no bits below 2^-133 either: a denormal operand is carried
+ *       at bf16's precision by the split, not fp32's.  pg_cast_rows_bf16 rounds the same way.
+ *   M4, overflow.  With S = sum |a b| in float64 along an output's sum: S < FLT_MAX / 2 -- the output is finite and within B S;
+ *       |ref64| > FLT_MAX (1 + B) -- the output is +-inf with ref64's sign (bf16x3: or NaN, as R1 says).  In between (a partial sum
+ *       of a split-K or stream-K tile may overflow where the total does not) nothing is promised.  A store activation sees the
+ *       overflowed sum; these two zones are stated for the sum.
+ *   Which rule holds where:
+ *     M1 - M4  pg_conv1d_* / pg_convt1d_* forward, dgrad (with addend and mask) and wgrad (without the fused Adam epilogue, which is
+ *              not homogeneous) at fp32, bf16 and bf16x3; pg_conv_fwd_h (yh / yh2 are y activated and rounded once to bf16).
+ *     M1       pg_stft and pg_stft_crops without stats or polar, pg_istft mode 1, pg_ola_nt, pg_gl_project (equivariant in mag,
+ *              invariant in S), pg_resample, pg_stitch (normalize: invariant), pg_spec_clips, pg_ola_stretch (x and base scaled
+ *              together), pg_hpss (both planes), pg_bn_bwd in dy, pg_cast_rows_bf16 (a denormal input is rounded to the bf16
+ *              denormal, RNE, not flushed), pg_moments (in double), pg_standardize, |z| of pg_polar with use_exp = 0, the phase
+ *              kernels above; pg_wave_compare and pg_spec_compare: slots 0 - 3 scale with 2^(2 e) (pg_wave_compare's slot 4 with
+ *              2^e), as doubles, at every fp32 exponent of the inputs -- both kernels widen before they multiply.
+ *     M3 / M2  the same linear kernels (pg_stft, pg_istft mode 1, pg_ola_nt, pg_resample, pg_stitch, pg_spec_clips, pg_ola_stretch,
+ *              pg_hpss) on inputs below FLT_MIN: their gain is one or more, so outputs below FLT_MIN come from such inputs; these
+ *              are read as they are and the outputs are within B 2^e + R 2^-150 of ref64 (R = 16 n_fft for a transform: every
+ *              rounding in an output's cone), nothing flushed; pg_spec_clips, pg_ola_stretch and pg_hpss keep the bits of their
+ *              fp32 restatements there.
+ *   Domains of the entry points that are not homogeneous; outside them the result is unspecified (finite or not), inside them the
+ *   entry point meets its float64 restatement at its usual bound:
+ *     pg_polar           every finite (re, im): |z| within 6e-7 relative plus one rounding where |z| < FLT_MIN, the angle within 3e-7
+ *                        rad; |z| > FLT_MAX gives +inf, so use_exp = 1 wants |z| <= FLT_MAX (log1p of it would be finite, 88.7).
+ *     pg_spec_compare    slots 0 - 3 and 5: every finite cell.  Slot 4 rounds m^2 to fp32 inside the logarithm: it wants
+ *                        m^2 <= FLT_MAX (|z| < 2^64) for both magnitudes, and floor_power scaled along with the data.
+ *     pg_adam_step       |grad_scale g| < 2^63 (g^2 is formed in fp32) and v < 2^126.  Below, everything is IEEE arithmetic with
+ *                        denormals kept: g^2 and v underflow gradually, bit for bit as an fp32 restatement does.
+ *     pg_bn_fwd, pg_clipnorm_fwd   |x - mean| < 2^63 (the centred squares are formed in fp32); y2 / yh / yh2 are the fp32 y activated
+ *                        and, for the bf16 rows, rounded once, at every scale.  Data so small that the squares are
+ *                        denormals or zero is normalised by eps alone, as the formula says.
+ *     pg_loss_fwd_bwd    |m^ - m| < 2^63 per element and B C L (m^ - m)^2 summable in fp32; phases: |p| < 2^31 pi (pg_sincos's
+ *                        reduction), the angle terms are bounded by 4 at any magnitude.
+ *     pg_istft mode 0    the sum over a frame's bins of exp(m) below FLT_MAX / 4 (the butterflies add a frame's bins before the 1 / n_fft;
+ *                        a single cell may reach m = 87, exp(m) = 2^125.5); pg_sincos wants |phi| < 2^31 pi.
+ *     normalize (pg_istft, pg_ola_nt, pg_stitch)   a peak <= FLT_MIN leaves the signal as it is (the early return): scale-free
+ *                        outputs are promised for peaks above FLT_MIN.
+ *   tests/_range.py, tests/test_range_host.py and tests/test_z_range_gpu.py hold the rows named there; DESIGN.md section 4.17 lists
+ *   what was measured and what is not yet held.
  */
 #ifndef PHASEGEN_H
 #define PHASEGEN_H
@@ -751,10 +810,12 @@ int     pg_ola_window(float* win_host, int32_t win_len);
  *
  * pg_spec_compare: R (reference) and E (estimate) in the layout pg_stft writes, (n_signals, 2, bins, frames) fp32 = [re; im] planes
  *   bins * frames apart, signals r_stride / e_stride >= 2 bins frames apart; bins and frames are any positive integers.
- *   Per cell, in fp32 and uncontracted, with g_f = (float)gain[s]:
- *     mR = sqrtf(re^2 + im^2) of R, mE0 = sqrtf(re^2 + im^2) of E, mE = g_f mE0, L(m) = 10 log10f(fmaxf(m m, floor_power))
+ *   Per cell the four floats are widened to double BEFORE any product (as pg_wave_compare does), with g_f = (float)gain[s]:
+ *     mR = sqrt(re^2 + im^2) of R, mE0 = sqrt(re^2 + im^2) of E, mE = g_f mE0, all in double;
+ *     L(m) = 10 log10f(fmaxf((float)(m m), floor_power)) in fp32
  *   A cell where any of its four floats is NaN or +-inf is counted in slot 5 and taken as zero in both inputs.  The products mR mR,
- *   mE0 mE0, mR mE0, (mR - mE)^2 and (L(mR) - L(mE))^2 are formed in fp32 and promoted to double before they are added.
+ *   mE0 mE0, mR mE0 and (mR - mE)^2 are formed and added in double, so no finite cell overflows or vanishes in slots 0 - 3;
+ *   (L(mR) - L(mE))^2 is formed in fp32 and promoted (slot 4's domain: "Magnitude range" above).
  *     out[s] = { sum mR^2, sum mE0^2, sum mR mE0, sum (mR - mE)^2,
  *                sum over frames of sqrt((sum over bins of (L(mR) - L(mE))^2) / bins), number of non-finite cells }
  *   Slot 4 / frames is the log-spectral distance in dB; a cell that is zero in both inputs adds 0 to it (both levels are the floor's).

@@ -224,7 +224,9 @@ def test_adam_zero_gradient_block_on_zero_state_changes_nothing(thin):
 
 @pytest.mark.parametrize("thin", [False, True])
 def test_adam_tiny_gradients(thin):
-    """g = +-1e-20 on zero state, step 1: g^2 = 1e-40 and v = 1e-43 are fp32 denormals.  Whether or not the device keeps them,
+    """g = +-1e-20 on zero state, step 1: g^2 = 1e-40 and v = 1e-43 are fp32 denormals.  The device keeps them (include/phasegen.h,
+    "Magnitude range": the update is IEEE basic operations, denormals included), so p, m and v have the bits of the float32
+    emulation; and whether or not it did,
     denom = sqrt(v) / bc2_sqrt + eps = 1e-8 (1 + 1e-12) and the update step_size * m / denom = 1e-16 is far below half an ulp of
     p ~ 0.1 or 1e-6 step_size: p, m and v must be finite and within 1e-6 * step_size of the float64 formula."""
     n = 4 * 256 + 3
@@ -245,6 +247,7 @@ def test_adam_tiny_gradients(thin):
         got = got.cpu().numpy().astype(np.float64)
         assert np.isfinite(got).all()
         assert np.abs(got - want).max() <= 1e-6 * step_size
+    assert same, "pg_adam_step keeps fp32 denormals (include/phasegen.h, Magnitude range): g^2 and v must have the emulation's bits"
 
 
 def test_adam_thin_matches_torch_optim():

@@ -20,7 +20,8 @@
 //
 // pg_spec_compare.  A workgroup takes SC_FRAMES = 256 frames (64 lanes x 4) by SC_BINS = 64 bins of one signal; its wave w walks
 // bins 16 w .. 16 w + 15 of the block in ascending order, so lanes run along the contiguous frames and bins are split over the
-// waves.  Per cell, fp32: mR, mE0, mE = g mE0, L(m) = 10 log10f(max(m m, floor)); products are formed in fp32 and added in double.
+// waves.  Per cell the four floats are widened first: mR, mE0, mE = g mE0, their products and (mR - mE)^2 are formed and added in
+// double (no product of two inputs can overflow or vanish); L(m) = 10 log10f(max((float)(m m), floor)) and (L - L)^2 stay fp32.
 // The per-frame sums of (L(mR) - L(mE))^2 of the four waves meet in LDS and are added in ascending bin order; the block's 256
 // per-frame sums go to the workspace, its cell sums (slots 0-3, 5) through the tree above as well.  spec_tile_kernel (one
 // workgroup per signal and frame tile) adds each frame's bin blocks in ascending order, takes sqrt(sum / bins), reduces the 256
@@ -150,7 +151,8 @@ struct ScKernelArgs {
     float floor_power;
 };
 
-__device__ __forceinline__ float sc_level(float m, float floor_power) { return 10.f * log10f(fmaxf(m * m, floor_power)); }
+// the level stays an fp32 logarithm of the power rounded to fp32: it needs m m <= FLT_MAX (include/phasegen.h, "Magnitude range")
+__device__ __forceinline__ float sc_level(double m, float floor_power) { return 10.f * log10f(fmaxf((float)(m * m), floor_power)); }
 
 template <int VEC>
 __global__ __launch_bounds__(CMP_THREADS) void spec_compare_kernel(const ScKernelArgs a) {
@@ -196,14 +198,17 @@ __global__ __launch_bounds__(CMP_THREADS) void spec_compare_kernel(const ScKerne
                     ++bad;
                     rr[j] = ri[j] = er[j] = ei[j] = 0.f;
                 }
-                const float mR = sqrtf(rr[j] * rr[j] + ri[j] * ri[j]);
-                const float mE0 = sqrtf(er[j] * er[j] + ei[j] * ei[j]);
-                const float mE = gf * mE0;
-                const float d = mR - mE;
-                v[0] += (double)(mR * mR);
-                v[1] += (double)(mE0 * mE0);
-                v[2] += (double)(mR * mE0);
-                v[3] += (double)(d * d);
+                // widened BEFORE any product (as wave_compare_kernel does): the squares of two floats are exact doubles at every
+                // exponent, so nothing overflows above 2^63.5 or vanishes below 2^-75 on its way into the sums
+                const double rrd = (double)rr[j], rid = (double)ri[j], erd = (double)er[j], eid = (double)ei[j];
+                const double mR = sqrt(rrd * rrd + rid * rid);
+                const double mE0 = sqrt(erd * erd + eid * eid);
+                const double mE = (double)gf * mE0;
+                const double d = mR - mE;
+                v[0] += mR * mR;
+                v[1] += mE0 * mE0;
+                v[2] += mR * mE0;
+                v[3] += d * d;
                 const float dl = sc_level(mR, a.floor_power) - sc_level(mE, a.floor_power);
                 fs[j] += (double)(dl * dl);
             }

@@ -54,11 +54,14 @@ __device__ __forceinline__ float pg_log1p_pos(float x) {
     return logf(u) + (x - d) * __builtin_amdgcn_rcpf(u);
 }
 
-// |re + j im| without hypotf's scaling ladder: exact power-of-two pre-scaling only where the squares would leave the normal range
+// |re + j im| without hypotf's scaling ladder: exact power-of-two pre-scaling only where the squares would leave the normal range.
+// The small branch scales by 2^90, not 2^64: m reaches down to the smallest denormal, 2^-149, and 2^-149 2^64 = 2^-85 squares to
+// 2^-170, below every fp32 number (|z| came out 0 or coarsely rounded below 2^-139); 2^90 puts m in [2^-59, 2^30) and the square of
+// the larger part in [2^-118, 2^60).  The smaller part's square may still vanish: it is then below 2^-24 of the sum.
 __device__ __forceinline__ float pg_abs2(float re, float im) {
     const float m = fmaxf(fabsf(re), fabsf(im));
-    const float sc = m < 0x1p-60f ? 0x1p64f : (m > 0x1p60f ? 0x1p-64f : 1.0f);
-    const float isc = m < 0x1p-60f ? 0x1p-64f : (m > 0x1p60f ? 0x1p64f : 1.0f);
+    const float sc = m < 0x1p-60f ? 0x1p90f : (m > 0x1p60f ? 0x1p-64f : 1.0f);
+    const float isc = m < 0x1p-60f ? 0x1p-90f : (m > 0x1p60f ? 0x1p64f : 1.0f);
     re *= sc; im *= sc;
     return __builtin_sqrtf(__fmaf_rn(re, re, im * im)) * isc;
 }
