@@ -20,7 +20,8 @@
  *   A NaN or +-inf in an input is ordinary data to every entry point: no call fails on it, and what it does to the outputs is
  *   part of the contract.  The entry points that state a rule of their own keep it (pg_stitch's count, pg_phase_join's fallback,
  *   pg_phase_vocoder's q(x) and "a NaN in M does not reset", pg_phase_lock / _linked / pg_phase_spsi, slot 5 of the compare kernels,
- *   pg_hpss's total order).
+ *   pg_hpss's total order, pg_formant_shift's confinement: a non-finite or out-of-domain cell of its plane affects only the outputs
+ *   of its own (channel, frame), and every other frame has the bits of the clean call).
  *   For every other one -- the conv entry points, pg_conv_fwd_h, pg_bn_fwd / _bwd, pg_clipnorm_fwd, pg_loss_fwd_bwd, pg_adam_step,
  *   pg_cast_rows_bf16, pg_stft, pg_stft_crops, pg_polar, pg_istft, pg_gl_project, pg_ola_nt, pg_moments / pg_standardize,
  *   pg_resample, pg_spec_clips, pg_ola_stretch -- let ref(x) be the entry point's documented formula evaluated in IEEE arithmetic on the input
@@ -111,6 +112,7 @@
  *                        reduction), the angle terms are bounded by 4 at any magnitude.
  *     pg_istft mode 0    the sum over a frame's bins of exp(m) below FLT_MAX / 4 (the butterflies add a frame's bins before the 1 / n_fft;
  *                        a single cell may reach m = 87, exp(m) = 2^125.5); pg_sincos wants |phi| < 2^31 pi.
+ *     pg_formant_shift   the plane is a logarithm: no scale rule applies, and its stated domain (finite, 0 <= M <= 80) is the rule.
  *     normalize (pg_istft, pg_ola_nt, pg_stitch)   a peak <= FLT_MIN leaves the signal as it is (the early return): scale-free
  *                        outputs are promised for peaks above FLT_MIN.
  *   tests/_range.py, tests/test_range_host.py and tests/test_z_range_gpu.py hold the rows named there; DESIGN.md section 4.17 lists
@@ -791,6 +793,58 @@ typedef struct pg_ola_stretch_args {
 } pg_ola_stretch_args;                           /* 96 bytes */
 int     pg_ola_stretch(const pg_ola_stretch_args* a, void* stream);
 int     pg_ola_window(float* win_host, int32_t win_len);
+
+/* pg_formant_shift: the spectral envelope of every frame of a log1p-magnitude plane and, optionally, the plane with that envelope
+ * re-imposed at `ratio` times each bin's frequency -- formant preservation for a pitch shift (phasegen/track.py, formant_semitones,
+ * pitch_shift(formants="keep")): the resampling that moves the partials moves the envelope with them, and this moves it back.
+ * Struct of its own, PG_VERSION unchanged; the reference has no counterpart; the arithmetic below is the contract.
+ *   M: (n_ch, bins, F) fp32, frames fastest, rows F apart, channels m_ch_rows F elements apart with m_ch_rows >= bins: a count of
+ *   ROWS (2 bins for pol[:, 0] of a polar tensor, bins for a dense plane).  All sizes are int32_t and all address arithmetic inside
+ *   is 64-bit.  Limits: 1 <= bins <= 4096, 1 <= order <= min(bins, 64), 0 <= hold <= 64, 0 <= iters <= 16, F >= 1, n_ch >= 1.
+ *   Domain: cells finite with 0 <= M <= 80 (the project's log1p magnitudes; expm1 stays finite).  Outside it only the confinement
+ *   below is promised.
+ *   Basis.  pg_formant_basis_elems(bins, order) = order bins + order (negative = error code).  pg_formant_basis (HOST, in double,
+ *   rounded once) fills T[q][k] = cos(pi q (k + 1/2) / bins), q < order, k < bins, k fastest, and then s[q] = c_q w_q with c_0 = 1 / bins,
+ *   c_q = 2 / bins for q >= 1 and the Hann lifter w_q = (1 + cos(pi q / order)) / 2 (with it the smoother's infinity norm is 1.04 at
+ *   every order; with a rectangular lifter it is 2.4 .. 2.9 and the iterations would amplify rounding).  The caller passes a DEVICE
+ *   copy of the table as `basis`; the kernel reads no other coefficients.
+ *   Per (channel c, frame g), with x[k] = M[c][k][g]:
+ *     1. peak hold     h[k] = max over d = -hold .. hold of x[clamp(k + d, 0, bins - 1)]: exact; hold = 0 copies.
+ *     2. smoothing     S(v)[k] = sum_q T[q][k] (s[q] sum_j T[q][j] v[j]), in fp32, the order of each sum the kernel's own;  e = S(h).
+ *     3. iterations    `iters` times: e = S(max(h, e)).
+ *     4. env (optional, dense (n_ch, bins, F)):  env[c][k][g] = e[k].
+ *     5. out (optional, dense (n_ch, bins, F)):  p = (double)(k + 1) ratio - 1 clamped to [0, bins - 1] (bin k is FFT bin k + 1: DC is
+ *        dropped), i0 = floor(p), i1 = min(i0 + 1, bins - 1), w = (float)(p - i0), ew = e[i0] + w (e[i1] - e[i0]),
+ *        a = expm1(max(ew, 0)) + eps, b = expm1(max(e[k], 0)) + eps, out = log1p(expm1(x[k]) (a / b)), with the library's expm1
+ *        (2^(m log2 e) - 1) and log1p; one IEEE division, nothing contracted.  ratio == 1.0 copies M to out bit for bit (as
+ *        pg_spec_clips does at w == 0), and x[k] == 0 gives +0.0: the zeros pg_hpss writes as silence stay silence.
+ *   At least one of env and out is required.
+ *   Consequences.  A frame's result does not depend on n_ch, on F, on the frame's position or on how the kernel tiles the plane,
+ *   bit for bit.  A plane constant along frequency has itself as its envelope, to rounding (the rows of S sum to one).
+ *   Confinement: a non-finite or out-of-domain cell affects only outputs of its own (channel, frame); every other frame has the
+ *   bits of the clean call.
+ *   Kernel: one workgroup per tile of 32 consecutive frames (16 above 1024 bins, 8 above 2048) x ALL bins of one channel, kept in
+ *   LDS across the hold, the 1 + iters passes and the epilogue; both products of a pass run on the fp32 MFMA with the table
+ *   streamed from L2; the order of every sum is a function of (bins, order) alone.  16-byte loads and stores where the pointers and
+ *   F allow, element by element otherwise (same bits); no atomics.  There is no workspace: the library allocates nothing and
+ *   keeps nothing.
+ *   Errors (host side, before any launch, in this order): NULL args / M / basis, or env and out both NULL, PG_ERR_NULL; non-positive
+ *   sizes, bins > 4096, m_ch_rows < bins, order / hold / iters outside their limits, a plane beyond 2^62 elements, ratio not finite
+ *   or outside [0.25, 4], eps not finite or <= 0 PG_ERR_SHAPE; M, basis, env or out not 4-byte aligned PG_ERR_ALIGN.  Messages begin
+ *   "formant_shift: ".  pg_formant_basis / _elems: NULL PG_ERR_NULL, bins or order outside the limits PG_ERR_SHAPE. */
+typedef struct pg_formant_args {
+    int32_t n_ch, bins, F, m_ch_rows;            /* channels m_ch_rows * F elements apart, m_ch_rows >= bins            */
+    int32_t order, hold, iters, _pad0;           /* 1 <= order <= min(bins, 64), 0 <= hold <= 64, 0 <= iters <= 16      */
+    double  ratio;                               /* finite, in [0.25, 4]; 1.0 copies M to out                           */
+    float   eps, _pad1;                          /* finite, > 0: the floor under both linear envelopes                  */
+    const float* M;                              /* (n_ch, bins, F), see above                                          */
+    const float* basis;                          /* DEVICE copy of pg_formant_basis's table, order bins + order floats  */
+    float* env;                                  /* optional (NULL): (n_ch, bins, F), dense                             */
+    float* out;                                  /* optional (NULL): (n_ch, bins, F), dense                             */
+} pg_formant_args;                               /* 80 bytes */
+int     pg_formant_shift(const pg_formant_args* a, void* stream);
+int64_t pg_formant_basis_elems(int32_t bins, int32_t order);
+int     pg_formant_basis(float* basis_host, int32_t bins, int32_t order);
 
 /* How far a reconstruction is from its source, reduced on the device: the sums from which SI-SDR / SNR (waveforms) and spectral
  * convergence / log-spectral distance (spectrograms) are formed on the host (phasegen/metrics.py).  The reference has no counterpart

@@ -229,6 +229,18 @@ class OlaStretchArgs(C.Structure):
                 ("base", C.c_void_p), ("base_stride", C.c_int64), ("y", C.c_void_p), ("y_stride", C.c_int64)]
 
 
+FORMANT_MAX_BINS, FORMANT_MAX_ORDER, FORMANT_MAX_HOLD, FORMANT_MAX_ITERS = 4096, 64, 64, 16     # pg_formant_shift's limits
+
+
+class FormantArgs(C.Structure):
+    """pg_formant_args: the spectral envelope of a log-magnitude plane, optionally re-imposed at a frequency ratio (include/phasegen.h).
+    No 64-bit field: every size is an int32 and the channel stride is a count of rows."""
+    _fields_ = [("n_ch", C.c_int32), ("bins", C.c_int32), ("F", C.c_int32), ("m_ch_rows", C.c_int32),
+                ("order", C.c_int32), ("hold", C.c_int32), ("iters", C.c_int32), ("_pad0", C.c_int32),
+                ("ratio", C.c_double), ("eps", C.c_float), ("_pad1", C.c_float),
+                ("M", C.c_void_p), ("basis", C.c_void_p), ("env", C.c_void_p), ("out", C.c_void_p)]
+
+
 class WaveCompareArgs(C.Structure):
     """pg_wave_compare_args: six sums per signal of a reference / estimate pair of waveforms (include/phasegen.h)."""
     _fields_ = [("n_signals", C.c_int32), ("_pad0", C.c_int32), ("n", C.c_int64),
@@ -302,6 +314,9 @@ SYMBOLS = {
     "pg_hpss": (C.c_int, [C.POINTER(HpssArgs), C.c_void_p]),
     "pg_ola_stretch": (C.c_int, [C.POINTER(OlaStretchArgs), C.c_void_p]),
     "pg_ola_window": (C.c_int, [C.c_void_p, C.c_int32]),
+    "pg_formant_shift": (C.c_int, [C.POINTER(FormantArgs), C.c_void_p]),
+    "pg_formant_basis_elems": (C.c_int64, [C.c_int32, C.c_int32]),
+    "pg_formant_basis": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "pg_workspace_bytes_wave_compare": (C.c_int64, [C.POINTER(WaveCompareArgs)]),
     "pg_wave_compare": (C.c_int, [C.POINTER(WaveCompareArgs), C.c_void_p]),
     "pg_workspace_bytes_spec_compare": (C.c_int64, [C.POINTER(SpecCompareArgs)]),

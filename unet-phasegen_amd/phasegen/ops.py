@@ -1151,6 +1151,93 @@ def ola_stretch(x, n_out, src_per_out=1.0, win_len=256, hop=64, base=None, out=N
     return out
 
 
+_formant_bases = {}      # (device, bins, order) -> device copy of pg_formant_basis's output (read-only; at most 1 MiB each)
+
+
+def formant_basis_host(bins, order):
+    """pg_formant_basis: the cosine table T[q][k] = cos(pi q (k + 1/2) / bins), (order, bins) row-major, followed by the ``order``
+    liftered weights s[q], as ONE float32 array of order * bins + order entries, built on the host in double (no GPU needed)."""
+    import numpy as np
+    bins, order = int(bins), int(order)
+    n = _lib.load().pg_formant_basis_elems(bins, order)
+    _lib.check(min(n, 0), "formant_basis_elems")
+    basis = np.empty(n, np.float32)
+    _lib.check(_lib.load().pg_formant_basis(basis.ctypes.data_as(C.c_void_p), bins, order), "formant_basis")
+    return basis
+
+
+def _formant_basis(bins, order, device):
+    key = (torch.device(device), bins, order)
+    basis = _formant_bases.get(key)
+    if basis is None:
+        basis = _formant_bases[key] = torch.from_numpy(formant_basis_host(bins, order)).to(device)
+    return basis
+
+
+def formant_shift(logmag, ratio, order=64, hold=16, iters=2, eps=0.01, return_env=False, out=None):
+    """The spectral envelope of every frame of a log-magnitude plane, re-imposed at ``ratio`` times each bin's frequency
+    (pg_formant_shift): ``logmag`` (n_ch, bins, F) float32 on the device, cells within [0, 80], frames contiguous, rows F apart, the
+    channel stride a whole number of rows (``pol[:, 0]`` of a polar tensor is read in place) -> (n_ch, bins, F), dense.  Per frame:
+    a peak hold over ``hold`` bins on either side, a liftered cosine smoothing of ``order`` coefficients, ``iters`` repetitions of
+    "smooth the maximum of the held frame and the envelope"; then out = log1p(expm1(x) a / b) with a, b = expm1 of the envelope at
+    bin (k + 1) ratio - 1 and at bin k, plus ``eps``.  ratio == 1.0 returns the plane's bits; a zero cell stays +0.0.
+    ``ratio`` > 1 reads the envelope higher up, i.e. moves the formants DOWN by that factor.  ``return_env``: -> (out, env), the
+    envelope itself (n_ch, bins, F).  ``out``: a dense tensor to fill.  The table is built once per (device, bins, order)."""
+    who = "formant_shift"
+    if not (torch.is_tensor(logmag) and logmag.is_cuda and logmag.dtype == torch.float32 and logmag.dim() == 3):
+        raise ValueError(f"{who}: logmag must be a 3-D float32 device tensor (n_ch, bins, F)")
+    stride = _vocoder_plane(logmag, "logmag", who=who)
+    n_ch, bins, F = logmag.shape
+    ratio, order, hold, iters, eps = float(ratio), int(order), int(hold), int(iters), float(eps)
+    if bins > _lib.FORMANT_MAX_BINS:
+        raise ValueError(f"{who}: at most {_lib.FORMANT_MAX_BINS} bins, got {bins}")
+    if stride % F != 0:
+        raise ValueError(f"{who}: the channel stride of logmag must be a whole number of rows of {F} frames (strides {logmag.stride()})")
+    if not 1 <= order <= min(bins, _lib.FORMANT_MAX_ORDER):
+        raise ValueError(f"{who}: order must be within 1 .. min(bins, {_lib.FORMANT_MAX_ORDER}) = {min(bins, _lib.FORMANT_MAX_ORDER)}, got {order}")
+    if not 0 <= hold <= _lib.FORMANT_MAX_HOLD:
+        raise ValueError(f"{who}: hold must be within 0 .. {_lib.FORMANT_MAX_HOLD}, got {hold}")
+    if not 0 <= iters <= _lib.FORMANT_MAX_ITERS:
+        raise ValueError(f"{who}: iters must be within 0 .. {_lib.FORMANT_MAX_ITERS}, got {iters}")
+    if not 0.25 <= ratio <= 4.0:
+        raise ValueError(f"{who}: ratio must be within [0.25, 4], got {ratio}")
+    if not 0.0 < eps < float("inf"):
+        raise ValueError(f"{who}: eps must be finite and positive, got {eps}")
+    if stride // F >= 1 << 31 or F >= 1 << 31:
+        raise ValueError(f"{who}: more than 2^31 - 1 frames or rows between channels")
+    out = _out(out, (n_ch, bins, F), logmag.device, who)
+    a = _lib.FormantArgs()
+    a.n_ch, a.bins, a.F, a.m_ch_rows = n_ch, bins, F, stride // F
+    a.order, a.hold, a.iters, a.ratio, a.eps = order, hold, iters, ratio, eps
+    a.M, a.basis = logmag.data_ptr(), _formant_basis(bins, order, logmag.device).data_ptr()
+    a.out = _dense(out, "out")
+    env = None
+    if return_env:
+        env = torch.empty((n_ch, bins, F), device=logmag.device, dtype=torch.float32)
+        a.env = env.data_ptr()
+    _lib.check(_lib.load().pg_formant_shift(C.byref(a), _stream()), who)
+    return (out, env) if return_env else out
+
+
+def formant_envelope(logmag, order=64, hold=16, iters=2, out=None):
+    """The envelope alone (pg_formant_shift with ``env`` only): ``logmag`` as in ``formant_shift`` -> (n_ch, bins, F), dense."""
+    who = "formant_envelope"
+    stride = _vocoder_plane(logmag, "logmag", who=who)
+    n_ch, bins, F = logmag.shape
+    order, hold, iters = int(order), int(hold), int(iters)
+    if bins > _lib.FORMANT_MAX_BINS or stride % F != 0 or not 1 <= order <= min(bins, _lib.FORMANT_MAX_ORDER) \
+            or not 0 <= hold <= _lib.FORMANT_MAX_HOLD or not 0 <= iters <= _lib.FORMANT_MAX_ITERS or stride // F >= 1 << 31 or F >= 1 << 31:
+        raise ValueError(f"{who}: arguments outside formant_shift's limits (bins {bins}, order {order}, hold {hold}, iters {iters}, strides {logmag.stride()})")
+    out = _out(out, (n_ch, bins, F), logmag.device, who)
+    a = _lib.FormantArgs()
+    a.n_ch, a.bins, a.F, a.m_ch_rows = n_ch, bins, F, stride // F
+    a.order, a.hold, a.iters, a.ratio, a.eps = order, hold, iters, 1.0, 0.01
+    a.M, a.basis = logmag.data_ptr(), _formant_basis(bins, order, logmag.device).data_ptr()
+    a.env = _dense(out, "out")
+    _lib.check(_lib.load().pg_formant_shift(C.byref(a), _stream()), who)
+    return out
+
+
 _compare_ws = _StreamCache()
 _caches.append(_compare_ws)
 

@@ -235,24 +235,35 @@ TRANSIENTS = (None, "ola")
 HPSS_WIN = (17, 17)                                               # ops.hpss windows (frames, bins) of transients="ola"
 TRANSIENT_WINDOW = 256                                            # ops.ola_stretch window and hop of the percussive part:
 TRANSIENT_HOP = 64                                                # 16 ms and 4 ms at 16 kHz
+FORMANTS = (None, "keep")
+# ops.formant_shift's estimator under formant_semitones / formants="keep": cosine order, peak hold (bins on either side), iterations and
+# the floor under both linear envelopes (tools/formant_bench.py; the figures are in DESIGN.md section 4.18)
+FORMANT_ORDER, FORMANT_HOLD, FORMANT_ITERS, FORMANT_EPS = 64, 16, 2, 0.01
 
 
-def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below=None, transients=None):
+def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below=None, transients=None, formant_semitones=0.0):
     """One phase source -> (mag, audio): the log-magnitude plane on the output grid (n_ch, bins, F_out) and the un-normalised,
     untrimmed ISTFT of it under that phase (n_ch, hop * (F_out - 1)).  Called under the device and no_grad.
     ``transients="ola"``: the phase source sees the harmonic part of the plane only and the percussive part comes back through the
-    time domain (``_add_transients``); ``mag`` stays the FULL plane on the output grid, what the result is meant to show."""
+    time domain (``_add_transients``); ``mag`` stays the FULL plane on the output grid, what the result is meant to show.
+    ``formant_semitones`` != 0: the whole analysed plane, the linked mean row included, is first replaced by itself with its spectral
+    envelope moved by that many semitones (ONE ops.formant_shift call), so the split, every phase source, the ISTFT magnitudes and
+    ``mag`` see the corrected plane."""
     pl, n_ch, bins = an.plan, an.n_ch, an.bins
     spo = 1.0 / an.stretch
     pol = an.pol[:n_ch]                                                                       # (linked: row n_ch is the channel mean)
+    plane = an.pol[:, 0]
+    if formant_semitones != 0.0:
+        plane = ops.formant_shift(plane, 2.0 ** (-formant_semitones / 12.0), min(FORMANT_ORDER, bins), FORMANT_HOLD, FORMANT_ITERS,
+                                  FORMANT_EPS)                                                # (a model narrower than the order: all its bins)
     if transients is not None:
         # all rows are split, the linked mean row too: the reference's magnitudes are its own harmonic part.  The cells handed to
         # the percussive side are zeros in `harm` and fall under the reset floor by themselves.
-        harm, perc = ops.hpss(an.pol[:, 0], *HPSS_WIN)
+        harm, perc = ops.hpss(plane, *HPSS_WIN)
         mag, audio = _invert_plane(an, model, phase, hop_length, frames, clip_batch, reset_below, pol, harm[:n_ch], harm[n_ch:])
         audio = _add_transients(an, hop_length, pol, perc[:n_ch], audio)                      # ("ola": the one way there is)
-        return ops.spec_clips(pol[:, 0], 1, pl.F_out, pl.F_out, spo)[0], audio
-    return _invert_plane(an, model, phase, hop_length, frames, clip_batch, reset_below, pol, pol[:, 0], an.pol[n_ch:, 0])
+        return ops.spec_clips(plane[:n_ch], 1, pl.F_out, pl.F_out, spo)[0], audio
+    return _invert_plane(an, model, phase, hop_length, frames, clip_batch, reset_below, pol, plane[:n_ch], plane[n_ch:])
 
 
 def _add_transients(an, hop_length, pol, perc, audio):
@@ -313,12 +324,12 @@ def _trim_spectral(an, audio, normalize):
     return out
 
 
-def _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize, reset_below=None, transients=None):
+def _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize, reset_below=None, transients=None, formant_semitones=0.0):
     """One phase source -> the track (channels, a_out) through the spectral join: clip windows of the log-magnitude plane, forward,
     ONE phase per global frame (ops.phase_join; phase="vocoder": ops.phase_vocoder on the analysis' phase instead), ONE ISTFT with
     the plane's own magnitudes; raises when a sample is not finite."""
     with torch.cuda.device(an.a2.device), torch.no_grad():
-        _mag, audio = _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below, transients)
+        _mag, audio = _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_below, transients, formant_semitones)
         return _trim_spectral(an, audio, normalize)
 
 
@@ -354,6 +365,17 @@ def _check_transients(who, transients, join):
     return transients
 
 
+def _check_formants(who, formant_semitones, join):
+    """formant_semitones: a finite shift within two octaves; the correction works on the whole-track plane, which only the spectral
+    join has"""
+    fs = float(formant_semitones)
+    if not (fs == fs and -24.0 <= fs <= 24.0):
+        raise ValueError(f"{who}: formant_semitones must be within [-24, 24], got {formant_semitones}")
+    if fs != 0.0 and join != "spectral":
+        raise ValueError(f"{who}: formant_semitones={fs} needs join='spectral', got join {join!r}")
+    return fs
+
+
 def peak_normalize(audio):
     """utils.py:42 for a whole track on the device: audio (samples,) or (channels, samples) divided by its joint peak -- the second
     launch of pg_stitch over one clip per channel, so ``peak_normalize(reconstruct_track(..., normalize=False))`` has the bits of
@@ -365,33 +387,35 @@ def peak_normalize(audio):
     return out[0] if audio.dim() == 1 else out
 
 
-def _keyword_options(impl, later=None, newer=None, **options):
+def _keyword_options(impl, later=None, newer=None, newest=None, **options):
     """Decorator for the two public track functions: the decorated ``def`` states the POSITIONAL parameter list and the docstring --
     the list callers of the waveform-only functions have always seen, which stays as it is (``inspect.signature`` reports it) -- and
     the call itself goes to ``impl`` with, in addition, the keyword-only ``options`` (name=default), which may be passed by keyword
     only.  ``fn.options`` lists them.  ``later``: keyword-only options (name=default) added since callers began to compare
     ``fn.options``, which therefore stays as it was; ``fn.later_options`` lists those.  ``newer``: the same once more, for options
-    added since callers began to compare ``fn.later_options``; ``fn.newer_options`` lists those."""
-    later, newer = dict(later or {}), dict(newer or {})
+    added since callers began to compare ``fn.later_options``; ``fn.newer_options`` lists those.  ``newest``: and once more, for
+    options added since callers began to compare ``fn.newer_options``; ``fn.newest_options`` lists those."""
+    later, newer, newest = dict(later or {}), dict(newer or {}), dict(newest or {})
 
     def deco(fn):
         sig = inspect.signature(fn)
 
         @functools.wraps(fn)
         def call(*args, **kw):
-            opts = {k: kw.pop(k, d) for k, d in {**options, **later, **newer}.items()}
+            opts = {k: kw.pop(k, d) for k, d in {**options, **later, **newer, **newest}.items()}
             bound = sig.bind(*args, **kw)
             bound.apply_defaults()
             return impl(**bound.arguments, **opts)
         call.options = dict(options)
         call.later_options = dict(later)
         call.newer_options = dict(newer)
+        call.newest_options = dict(newest)
         return call
     return deco
 
 
 def _reconstruct_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phase, normalize,
-                       join, stretch, link_channels, transients):
+                       join, stretch, link_channels, transients, formant_semitones):
     """``reconstruct_track`` with its keyword-only options spelled out."""
     if phase not in ("unet", "original", "zero") + GRID_PHASES:
         raise ValueError(f"reconstruct_track: phase must be 'unet', 'original', 'zero', 'vocoder', 'vocoder_locked' or 'spsi', got {phase!r}")
@@ -402,16 +426,19 @@ def _reconstruct_track(model, audio, n_fft, hop_length, frames, overlap_frames, 
     stretch = _check_join("reconstruct_track", join, stretch, (phase,))
     link = _check_link("reconstruct_track", link_channels, join, (phase,))
     transients = _check_transients("reconstruct_track", transients, join)
+    formant_semitones = _check_formants("reconstruct_track", formant_semitones, join)
     if join == "spectral":
         an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch, link)
-        out = _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize, transients=transients)
+        out = _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, normalize, transients=transients,
+                                   formant_semitones=formant_semitones)
         return out[0] if an.mono else out
     an = _analyse(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type)
     out = _synthesise(an, model, phase, hop_length, clip_batch, normalize)
     return out[0] if an.mono else out
 
 
-@_keyword_options(_reconstruct_track, later={"link_channels": False}, newer={"transients": None}, join="waveform", stretch=1.0)
+@_keyword_options(_reconstruct_track, later={"link_channels": False}, newer={"transients": None}, newest={"formant_semitones": 0.0},
+                  join="waveform", stretch=1.0)
 def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None,
                       osr=None, sr=16000, res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True):
     """audio (samples,) or (channels, samples), host array or device tensor, at ``sr`` -- or at ``osr`` when given (resampled to
@@ -440,7 +467,13 @@ def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, over
     ``HPSS_WIN``), hands the harmonic part to the chosen phase source in the plane's place, inverts the percussive part on the source
     grid with the analysis' own phase and moves it onto the output grid in the time domain (ops.ola_stretch, ``TRANSIENT_WINDOW`` /
     ``TRANSIENT_HOP``): onsets are relocated instead of stretched.  None: not one launch and not one bit differs from a call
-    without the keyword."""
+    without the keyword.
+    ``formant_semitones=0.0`` (``reconstruct_track.newest_options``; spectral join only, else ValueError; with every phase, with
+    ``link_channels`` and with ``transients``): the spectral envelope of every analysed frame -- peak hold, liftered cosine smoothing,
+    a few iterations (ops.formant_shift, ``FORMANT_ORDER`` / ``FORMANT_HOLD`` / ``FORMANT_ITERS`` / ``FORMANT_EPS``) -- is moved by that
+    many semitones while the partials stay where they are; the corrected plane replaces the analysed one before anything else reads
+    it.  ``pitch_shift(formants="keep")`` passes the negative of its shift, so that the resampling puts the formants back.  0.0: not
+    one launch and not one bit differs from a call without the keyword."""
 
 
 def _evaluate_track(model, audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phases, gl_iters,
@@ -498,7 +531,7 @@ def evaluate_track(model, audio, n_fft=2048, hop_length=512, frames=128, overlap
 
 
 def _evaluate_stretch(model, audio, stretch, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phases,
-                      reset_below, floor, return_audio, link_channels, transients):
+                      reset_below, floor, return_audio, link_channels, transients, formant_semitones):
     """``evaluate_stretch`` with its keyword-only options spelled out."""
     phases = tuple(phases)
     for p in phases:
@@ -516,6 +549,7 @@ def _evaluate_stretch(model, audio, stretch, n_fft, hop_length, frames, overlap_
     stretch = _check_join("evaluate_stretch", "spectral", stretch, phases)
     link = _check_link("evaluate_stretch", link_channels, "spectral", phases)
     transients = _check_transients("evaluate_stretch", transients, "spectral")
+    formant_semitones = _check_formants("evaluate_stretch", formant_semitones, "spectral")
     an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch, link)
     res = {"n_samples": int(an.a_len), "n_out": int(an.plan.a_out), "sr": int(sr), "stretch": stretch, "n_clips": int(an.n_clips),
            "reset_below": reset_below, "metrics": {}}
@@ -523,13 +557,15 @@ def _evaluate_stretch(model, audio, stretch, n_fft, hop_length, frames, overlap_
         res["link_channels"], res["mid_metrics"] = True, {}
     if transients is not None:
         res["transients"] = transients
+    if formant_semitones != 0.0:
+        res["formant_semitones"] = formant_semitones
     if return_audio:
         res["audio"] = {}
     with torch.cuda.device(an.a2.device), torch.no_grad():
         if link:        # the mid signal's imposed magnitudes: the mean row's plane, resampled as the channels' are
             mid_mag = ops.spec_clips(an.pol[an.n_ch:, 0], 1, an.plan.F_out, an.plan.F_out, 1.0 / an.stretch)[0]
         for p in phases:
-            mag, full = _invert_spectral(an, model, p, hop_length, frames, clip_batch, reset_below, transients)
+            mag, full = _invert_spectral(an, model, p, hop_length, frames, clip_batch, reset_below, transients, formant_semitones)
             out = _trim_spectral(an, full, False)
             res["metrics"][p] = metrics.consistency(mag, full, n_fft, hop_length, floor)
             if link:
@@ -539,7 +575,7 @@ def _evaluate_stretch(model, audio, stretch, n_fft, hop_length, frames, overlap_
     return res
 
 
-@_keyword_options(_evaluate_stretch, later={"link_channels": False}, newer={"transients": None})
+@_keyword_options(_evaluate_stretch, later={"link_channels": False}, newer={"transients": None}, newest={"formant_semitones": 0.0})
 def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
                      res_type="kaiser_best", clip_batch=64, phases=("unet", "vocoder", "zero"), reset_below=None, floor=1e-10,
                      return_audio=False):
@@ -558,7 +594,9 @@ def evaluate_stretch(model, audio, stretch, n_fft=2048, hop_length=512, frames=1
     plane of the channel mean of the input}, for every phase asked for: what the channels' sum to mono lost.  Without it the report
     has the keys above and no others.  ``transients=None`` (``evaluate_stretch.newer_options``): ``"ola"`` synthesises every phase
     as ``reconstruct_track(..., transients="ola")`` does and records "transients": "ola" in the report; the consistency is still
-    measured against the FULL plane's magnitudes on the output grid.
+    measured against the FULL plane's magnitudes on the output grid.  ``formant_semitones=0.0`` (``evaluate_stretch.newest_options``):
+    as in ``reconstruct_track``; a value other than 0 is recorded as "formant_semitones" and the consistency is measured against the
+    CORRECTED plane's magnitudes, the ones that were imposed.
     Every synthesis is finite-checked before it is measured: raises ValueError("Audio buffer is not finite everywhere"), as
     ``reconstruct_track`` does, and returns no report, when one of the round(a_len * stretch) samples of any of them is not finite."""
 
@@ -575,20 +613,26 @@ def pitch_ratio(semitones, max_denominator=1024):
 
 
 def pitch_shift(model, audio, semitones, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
-                res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True, *, link_channels=False, transients=None):
+                res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True, *, link_channels=False, transients=None, formants=None):
     """Pitch shift by ``semitones`` (within two octaves) without a change of tempo: the track is stretched by 2 ** (semitones / 12)
     through the spectral join (``reconstruct_track(join="spectral", stretch=...)``: same pitch, longer or shorter) and played back
     faster or slower by the same ratio (``preproc.resample`` by q / p, see ``pitch_ratio`` for the error in cents), then trimmed or
     zero-padded to the input's length at ``sr``.  ``phase``: "unet", "vocoder", "vocoder_locked", "spsi" or "zero", as in
-    ``reconstruct_track``; ``link_channels`` and ``transients`` (keyword only) are forwarded to it.
+    ``reconstruct_track``; ``link_channels`` and ``transients`` (keyword only) are forwarded to it.  ``formants`` (keyword only): None
+    lets the spectral envelope move with the partials (a voice shifted up sounds smaller); ``"keep"`` forwards
+    ``formant_semitones=-semitones``, so the envelope is moved the other way on the analysed plane and the resampling puts it back
+    where it was.
     -> float32 device tensor shaped like the input at ``sr``."""
+    if formants not in FORMANTS:
+        raise ValueError(f"pitch_shift: formants must be None or 'keep', got {formants!r}")
     stretch, ratio = pitch_ratio(semitones)
     _check_link("pitch_shift", link_channels, "spectral", (phase,))
     _check_transients("pitch_shift", transients, "spectral")
     a = preproc.resample(audio, osr, sr, res_type=res_type) if osr is not None else audio
     a_len = int(a.shape[-1])
     out = reconstruct_track(model, a, n_fft, hop_length, frames, overlap_frames, stats, None, sr, res_type, clip_batch, phase,
-                            normalize=False, join="spectral", stretch=stretch, link_channels=link_channels, transients=transients)
+                            normalize=False, join="spectral", stretch=stretch, link_channels=link_channels, transients=transients,
+                            formant_semitones=0.0 if formants is None else -float(semitones))
     if ratio != 1:
         out = preproc.resample(out, ratio.numerator, ratio.denominator, res_type=res_type)
     if out.shape[-1] >= a_len:

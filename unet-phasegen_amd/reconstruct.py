@@ -40,6 +40,11 @@ also holds ``mid_metrics``, the consistency of the channels' mean.
 magnitudes are split into a harmonic and a percussive part by median filtering (``phasegen.ops.hpss``), the harmonic part is
 stretched with the chosen phase and the percussive part is moved in the time domain by overlap-add of a 16 ms window
 (``phasegen.ops.ola_stretch``), which relocates clicks instead of stretching them.
+
+``--formants keep`` (with ``--pitch``) keeps the timbre where it was: the spectral envelope of every frame is estimated on the device
+(``phasegen.ops.formant_shift``) and moved against the shift before the resampling moves it along with the partials, so a voice
+shifted up does not turn into a smaller voice.  ``--formant_shift SEMITONES`` moves the envelope alone, at the same pitch and tempo
+(implies the spectral join; not with ``--pitch``, ``--formants`` or ``--report``).
 """
 import argparse
 import json
@@ -93,11 +98,26 @@ def main():
     parser.add_argument("--transients", choices=["ola"], default=None,
                         help="with --stretch or --pitch: split off the percussive part and move it in the time domain by overlap-add "
                              "(keeps onsets sharp)")
+    parser.add_argument("--formants", choices=["keep"], default=None,
+                        help="with --pitch: keep the spectral envelope (the formants) where it was instead of moving it with the partials")
+    parser.add_argument("--formant_shift", default=None, type=float, metavar="SEMITONES",
+                        help="move the spectral envelope alone, within +-24 semitones, at the same pitch (implies --join spectral)")
     args = parser.parse_args()
     if args.phase == "unet" and args.weight is None:
         parser.error("the following arguments are required: --weight")
     if args.stretch is not None and args.pitch is not None:
         parser.error("--stretch and --pitch exclude each other")
+    if args.formants is not None and args.pitch is None:
+        parser.error("--formants needs --pitch")
+    if args.formant_shift is not None and (args.pitch is not None or args.formants is not None):
+        parser.error("--formant_shift moves the formants alone: it excludes --pitch and --formants")
+    if args.formant_shift is not None and not -24.0 <= args.formant_shift <= 24.0:
+        parser.error("--formant_shift must be within +-24 semitones")
+    if args.formant_shift is not None and args.join == "waveform":
+        parser.error("--formant_shift needs --join spectral")
+    if args.formant_shift is not None and args.report is not None:
+        parser.error("--report compares against the input: it does not work with --formant_shift")
+    formant_shift = 0.0 if args.formant_shift is None else args.formant_shift
     modified = (args.stretch is not None and args.stretch != 1.0) or args.pitch is not None
     if modified and args.join == "waveform":
         parser.error("--stretch and --pitch need --join spectral")
@@ -121,7 +141,8 @@ def main():
         parser.error("--stretch_report measures the stretched track on the analysed frame grid: it does not work with --pitch")
     if args.stretch_report is not None and args.report is not None:
         parser.error("--report and --stretch_report exclude each other")
-    join = "spectral" if (modified or args.stretch is not None or args.phase in GRID_PHASES) and args.join is None else (args.join or "waveform")
+    join = ("spectral" if (modified or args.stretch is not None or args.formant_shift is not None or args.phase in GRID_PHASES) and args.join is None
+            else (args.join or "waveform"))
     if args.stretch_report is not None and join != "spectral":
         parser.error("--stretch_report needs --join spectral")
     n_fft = 2 * args.channels if args.n_fft is None else args.n_fft
@@ -163,16 +184,18 @@ def main():
     report = None
     stretch_report = None
     if args.pitch is not None:
-        out = track.pitch_shift(model, audio, args.pitch, phase=args.phase, link_channels=args.link_channels, transients=args.transients, **kw)
+        out = track.pitch_shift(model, audio, args.pitch, phase=args.phase, link_channels=args.link_channels, transients=args.transients,
+                                formants=args.formants, **kw)
     elif args.stretch_report is not None:
         # (the locked vocoder and spsi are reported when they are asked for; the other modes' reports stay as they were)
         others = [p for p in track.STRETCH_PHASES if p not in (args.phase, "vocoder_locked", "spsi") and (p != "unet" or model is not None)]
         stretch_report = track.evaluate_stretch(model, audio, args.stretch, phases=[args.phase] + others, return_audio=True,
-                                                link_channels=args.link_channels, transients=args.transients, **kw)
+                                                link_channels=args.link_channels, transients=args.transients,
+                                                formant_semitones=formant_shift, **kw)
         out = track.peak_normalize(stretch_report.pop("audio")[args.phase])
     elif args.report is None:
         out = track.reconstruct_track(model, audio, phase=args.phase, join=join, stretch=1.0 if args.stretch is None else args.stretch,
-                                      link_channels=args.link_channels, transients=args.transients, **kw)
+                                      link_channels=args.link_channels, transients=args.transients, formant_semitones=formant_shift, **kw)
     else:
         report = track.evaluate_track(model, audio, phases=phases, gl_iters=args.gl_iters, return_audio=True, join=join, gl_init=args.gl_init, **kw)
         out = track.peak_normalize(report.pop("audio")["unet"])
