@@ -269,6 +269,67 @@ VIEW_CASES = FIXUP_CASES + [_one_tile_per_workgroup(c) for c in FIXUP_CASES] + [
     ((F_, 24, 40, 7, 3, 2, 50, 2), "wgrad", 0, "conv_g", "G", "none"), ((T_, 24, 40, 7, 3, 2, 17, 2), "fwd", 0, "conv_t", "T", "none"),
     ((T_, 24, 40, 7, 3, 2, 17, 2), "dgrad", 0, "conv_f", "F", "none"), ((T_, 24, 40, 7, 3, 2, 17, 2), "wgrad", 0, "conv_g", "G", "none"),
 ]
+# ---- the raw-window wgrad's instantiations (tests/test_z_wgrad_cover_gpu.py runs every row) ------------------------------------------
+# conv_g_raw_kernel / conv_g_ps_kernel<KW, S, BF> exist for the network's five (k, s) pairs x three operand modes.  The tables above
+# reach the flat-K kernel of k = 4, k = 5 and (k, s) = (8, 1) at no bf16 mode (and at fp32 only through the packed module's 1e-5
+# bound): one geometry each, under one tile per workgroup and under stream-K.  Every row: p > 0 (the first and the last window leave
+# the row), 2-3 samples of 29 frames (LP = 29: every other slab runs over a sample end, and padding to 32 would cost 10 %, so the plan
+# keeps the flat K axis), one tile, K = 58 / 87.
+WGRAD_COVER_CASES = [
+    ((F_, 24, 40, 4, 2, 1, 58, 2), "wgrad", 1, "conv_g_raw", "G", "none"), ((F_, 24, 40, 4, 2, 1, 58, 2), "wgrad", 2, "conv_g_raw", "G", "plain"),
+    ((T_, 40, 31, 5, 2, 1, 29, 2), "wgrad", 1, "conv_g_raw", "G", "none"), ((T_, 40, 31, 5, 2, 1, 29, 2), "wgrad", 2, "conv_g_raw", "G", "plain"),
+    ((F_, 24, 40, 8, 1, 2, 32, 3), "wgrad", 1, "conv_g_raw", "G", "none"), ((F_, 24, 40, 8, 1, 2, 32, 3), "wgrad", 2, "conv_g_raw", "G", "plain"),
+]
+WGRAD_KS = ((32, 2), (8, 1), (8, 2), (5, 2), (4, 2))
+# instantiations no call reaches: pick_family (csrc/conv_igemm.hip) never takes per-sample slabs at k = 32
+WGRAD_UNREACHED = {("conv_g_ps", 32, 2, bf) for bf in (0, 1, 2)}
+
+
+def wgrad_instantiation(desc):
+    """(family, KW, S, BF) of a described raw-window wgrad, None for any other kernel"""
+    m = re.match(r"(conv_g_raw|conv_g_ps)_kernel<(\d+), (\d+), (\d+)>\|", desc)
+    return (m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4))) if m else None
+
+
+def wgrad_frames(geom):
+    """frames per sample of the wgrad's A operand (LP): dy's for a Conv1d, x's for a ConvTranspose1d"""
+    tr, Cin, Cout, k, s, p, Lin, B = geom
+    return Lin if tr else (Lin + 2 * p - k) // s + 1
+
+
+def test_value_rows_reach_every_raw_window_wgrad_instantiation():
+    """The wgrad rows of VIEW_CASES, SPLIT_CASES and WGRAD_COVER_CASES -- each run element by element against float64 at every operand
+    mode its family has -- reach 27 of the 30 conv_g_raw / conv_g_ps instantiations; the other three (per-sample slabs at k = 32) no
+    plan names at any frame count, so no row can.  On flat-K rows a slab crosses a sample end, every row's windows leave the row on
+    both sides, and every (k, s) has a per-sample row whose last slab is padded."""
+    from phasegen import _lib, ops
+    every = {(fam, k, s, bf) for fam in ("conv_g_raw", "conv_g_ps") for k, s in WGRAD_KS for bf in (0, 1, 2)}
+    reached, padded = set(), set()
+    for case in VIEW_CASES + SPLIT_CASES + WGRAD_COVER_CASES:
+        if case[1] != "wgrad":
+            continue
+        for prec in (0, 1, 2) if case[3] in BF16_FAMILIES else (0,):
+            inst = wgrad_instantiation(ops.conv_describe(_view_args(_lib, case, None, prec), _opcode(_lib, case)))
+            if inst:
+                reached.add(inst)
+                if inst[0] == "conv_g_ps" and wgrad_frames(case[0]) % 16:
+                    padded.add(inst[1:3])
+    assert reached == every - WGRAD_UNREACHED, sorted(every - reached)
+    assert padded == set(WGRAD_KS) - {(32, 2)}, padded
+    for L in range(16, 300):                                  # k = 32: the flat K axis whatever the frame count
+        for prec in (0, 1, 2):
+            d = ops.conv_describe(_args(_lib, 2, 40, 48, 2 * L, 32, 2, 16, False, precision=prec), _lib.OP_CONV1D_WGRAD)
+            assert wgrad_frames((False, 40, 48, 32, 2, 16, 2 * L, 2)) == L + 1 and wgrad_instantiation(d)[0] == "conv_g_raw", (L, d)
+    assert len(set(WGRAD_COVER_CASES)) == len(WGRAD_COVER_CASES) and not set(WGRAD_COVER_CASES) & set(VIEW_CASES + SPLIT_CASES)
+    for case in WGRAD_COVER_CASES:
+        geom, op, sched, fam, epi, form = case
+        tr, Cin, Cout, k, s, p, Lin, B = geom
+        assert max(Cin, Cout) <= 64 and Lin <= 258 and 2 <= B <= 3 and p > 0 and wgrad_frames(geom) % 16 and _gemm_k(geom, op) <= 512, case
+        for prec in (0, 1, 2):
+            d = ops.conv_describe(_view_args(_lib, case, None, prec), _opcode(_lib, case))
+            assert wgrad_instantiation(d) == (fam, k, s, prec) and _epilogue(d) == epi and _fields(d)["fixup"] == form, (case, d)
+
+
 # families with bf16 / bf16x3 operand modes of their own (conv_raw3 is fp32 only: its problems go to conv_raw at those precisions)
 BF16_FAMILIES = ("conv_f", "conv_t", "conv_g", "conv_raw(128x256)", "conv_raw(tall 256x128)", "conv_g_raw", "conv_g_ps")
 # (channel offset, further channels behind) of a view inside its buffer: 4 channels in front leave the view 16-byte aligned whatever
