@@ -794,6 +794,90 @@ typedef struct pg_ola_stretch_args {
 int     pg_ola_stretch(const pg_ola_stretch_args* a, void* stream);
 int     pg_ola_window(float* win_host, int32_t win_len);
 
+/* Tempo maps: the five stretch kernels over a TABLE of positions instead of one rate (phasegen/track.py, TimeMap).  Each entry
+ * point below is the twin of the one it is named after, with `pos`, a DEVICE table of doubles, in place of src_per_out: the kernels
+ * are the twins' own, instantiated on a second time grid (csrc/pg_track.h), and everything the twin's comment says holds word for
+ * word once "p = (double)g * src_per_out" is read as "p = pc(pos[g])".  Structs of their own, PG_VERSION unchanged; the reference has
+ * no counterpart; the arithmetic below is the contract.
+ *   A mapped position.  pc(p) = !(p >= 0) ? 0 : (p > 2^52 ? 2^52 : p): a NaN and a negative position count as 0, +inf and anything
+ *   beyond 2^52 as 2^52, where floor(p) == p.  From pc on everything is the twin's arithmetic: i0 = min((int64)floor(pc), F_src - 1),
+ *   i1 = min(i0 + 1, F_src - 1); in pg_spec_clips_map w = (float)(pc - floor(pc)) and out = a when w == 0 (so -0.0 survives),
+ *   otherwise fl(a + fl(w fl(b1 - a))); in the three phase kernels the advance into frame g lies between i1(g - 1) and i0(g).
+ *   Hence no read leaves a plane, whatever the table holds, and a NaN in `pos` reads source frame 0 (with w == 0).  Positions need
+ *   not be monotone: a frozen table holds a frame's magnitudes while its phase goes on advancing by the step measured there, and a
+ *   backward step or a jump takes the advance between i1(g-1) and i0(g) as it stands (a wrapped difference, whatever lies between;
+ *   the planner in phasegen/track.py restricts slopes, the kernels do not).  A table that holds (double)g * src_per_out reproduces the twin BIT
+ *   FOR BIT at any src_per_out, and the frames before a table's first departure from such a line have the twin's bits (the scans
+ *   are causal; pg_spec_clips_map cell by cell).
+ *   Tables.  pg_spec_clips_map: (n_clips - 1) sf + frames source-frame positions, one per global output frame.  pg_phase_vocoder_map,
+ *   pg_phase_lock_map, pg_phase_lock_linked_map: F_out source-frame positions.  pg_ola_stretch_map: one source CENTRE per grain, in
+ *   samples, (n_out + win_len / 2) / hop + 1 entries (grain g is centred on output sample g hop; no grain beyond the table covers an
+ *   output sample); c_g = (int64) rint(pos[g]), round half to even, and a centre that is NaN or beyond +-2^62 is outside every
+ *   signal: it counts in den and not in num.
+ *   Sizes.  Every size is an int32_t, a channel stride is a count of ROWS (p_ch_rows, a_ch_rows, m_ch_rows >= bins: channels
+ *   ch_rows F_src elements apart; 2 bins for a plane of a polar tensor) and a row stride of pg_ola_stretch_map a count of samples;
+ *   all index arithmetic inside is 64-bit.  The only 64-bit integer field is workspace_bytes.
+ *   NaN cells in A or M, the workspaces (pg_workspace_bytes_phase_lock_map / _linked_map return what the twins' queries return for
+ *   equal shapes), the kernels, the 16-byte store paths: the twins'.  pg_spec_clips_map has no 16-byte path (the twin's is rate 1's).
+ *   The library allocates nothing and keeps nothing.
+ *   Errors (host side, before any launch): the twin's rows in the twin's order, without the src_per_out row and the rows no int32
+ *   size can reach (a plane beyond 2^62 elements), with pos NULL in the PG_ERR_NULL row and pos not 8-byte aligned in the
+ *   PG_ERR_ALIGN row; a ch_rows < bins is the twin's "stride shorter than a plane" (PG_ERR_SHAPE). */
+typedef struct pg_spec_clips_map_args {
+    int32_t n_clips, n_ch, bins, frames;         /* output (n_clips, n_ch, bins, frames)                                */
+    int32_t sf, F_src;                           /* clip k begins at global output frame k sf; frames per row of P      */
+    int32_t p_ch_rows, _pad0;                    /* channels p_ch_rows F_src elements apart, p_ch_rows >= bins          */
+    const double* pos;                           /* DEVICE: (n_clips - 1) sf + frames source-frame positions            */
+    const float* P;                              /* (n_ch, bins, F_src)                                                 */
+    float* out;
+} pg_spec_clips_map_args;                        /* 56 bytes */
+int pg_spec_clips_map(const pg_spec_clips_map_args* a, void* stream);
+typedef struct pg_phase_vocoder_map_args {
+    int32_t n_ch, bins, F_src, F_out;
+    float   reset_below; int32_t a_ch_rows;      /* channels of A a_ch_rows F_src elements apart, a_ch_rows >= bins     */
+    int32_t m_ch_rows, _pad0;                    /* the same for M (unused when M is NULL)                              */
+    const double* pos;                           /* DEVICE: F_out source-frame positions                                */
+    const float* A;                              /* (n_ch, bins, F_src)                                                 */
+    const float* M;                              /* optional (NULL: no reset after frame 0)                             */
+    float* out;                                  /* (n_ch, bins, F_out), dense                                          */
+} pg_phase_vocoder_map_args;                     /* 64 bytes */
+int pg_phase_vocoder_map(const pg_phase_vocoder_map_args* a, void* stream);
+typedef struct pg_phase_lock_map_args {
+    int32_t n_ch, bins, F_src, F_out;            /* bins <= 4096                                                        */
+    float   reset_below; int32_t a_ch_rows;
+    int32_t m_ch_rows, _pad0;
+    const double* pos;                           /* DEVICE: F_out source-frame positions                                */
+    const float* A;
+    const float* M;                              /* required                                                            */
+    float* out;                                  /* (n_ch, bins, F_out), dense                                          */
+    void* workspace; int64_t workspace_bytes;
+} pg_phase_lock_map_args;                        /* 80 bytes */
+int64_t pg_workspace_bytes_phase_lock_map(const pg_phase_lock_map_args* a);   /* host function of n_ch, bins, F_out; negative = error code */
+int     pg_phase_lock_map(const pg_phase_lock_map_args* a, void* stream);
+typedef struct pg_phase_lock_linked_map_args {
+    int32_t n_ch, bins, F_src, F_out;            /* bins <= 4096                                                        */
+    float   reset_below; int32_t a_ch_rows;      /* channels of A a_ch_rows F_src elements apart, a_ch_rows >= bins     */
+    int32_t _pad0, _pad1;
+    const double* pos;                           /* DEVICE: F_out source-frame positions                                */
+    const float* A;                              /* (n_ch, bins, F_src): the channels' angle planes                     */
+    const float* Aref;                           /* (bins, F_src): angle plane of the reference                         */
+    const float* Mref;                           /* (bins, F_src): log-magnitude plane of the reference, required       */
+    float* out;                                  /* (n_ch, bins, F_out), dense                                          */
+    void* workspace; int64_t workspace_bytes;
+} pg_phase_lock_linked_map_args;                 /* 88 bytes */
+int64_t pg_workspace_bytes_phase_lock_linked_map(const pg_phase_lock_linked_map_args* a);   /* host function of bins, F_out; negative = error code */
+int     pg_phase_lock_linked_map(const pg_phase_lock_linked_map_args* a, void* stream);
+typedef struct pg_ola_stretch_map_args {
+    int32_t n_sig, win_len, hop, n_in;           /* win_len even, 2 <= win_len <= 4096; 1 <= hop <= win_len / 2         */
+    int32_t n_out, x_stride, base_stride, y_stride;   /* rows x_stride >= n_in, base_stride, y_stride >= n_out samples apart */
+    const double* pos;                           /* DEVICE: (n_out + win_len / 2) / hop + 1 source centres, in samples  */
+    const float* x;                              /* (n_sig, n_in)                                                       */
+    const float* win;                            /* DEVICE table of win_len floats, each finite and >= 0                */
+    const float* base;                           /* optional (NULL): (n_sig, n_out), added to the result                */
+    float* y;                                    /* (n_sig, n_out)                                                      */
+} pg_ola_stretch_map_args;                       /* 72 bytes */
+int     pg_ola_stretch_map(const pg_ola_stretch_map_args* a, void* stream);
+
 /* pg_formant_shift: the spectral envelope of every frame of a log1p-magnitude plane and, optionally, the plane with that envelope
  * re-imposed at `ratio` times each bin's frequency -- formant preservation for a pitch shift (phasegen/track.py, formant_semitones,
  * pitch_shift(formants="keep")): the resampling that moves the partials moves the envelope with them, and this moves it back.

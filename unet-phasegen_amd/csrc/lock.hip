@@ -17,6 +17,11 @@
 // serving all channels of a chunk from one map would save the recomputation of the maps; it needs n_ch planes of the window or a
 // pass per channel over stored maps, and is not done.)
 //
+// pg_phase_lock_map and pg_phase_lock_linked_map are the two above on pg_track.h's MappedGrid: the positions of the output frames
+// come from a table, pc(pos[g]), and need not grow with g.  Only LkArgs and the two loaders (lk_load, lk_fetch) know the grid: the
+// frame sources carry it as a type, LockSrc<Grid> / LinkSrc<Grid>, and the scan below is the same code for both (tests/_map_ref.py;
+// DESIGN.md section 4.19).
+//
 // The recurrence (q(), angle(), i0(g), i1(g) and the advance into frame g are pg_track.h's, shared with vocoder.hip).  Per channel,
 // T_g[b] (uint32, a fraction of a turn) is the rotation of bin b at output frame g against its analysis
 // phase: T_0 = 0 and T_g[b] = reset ? 0 : T_{g-1}[p] + e_g[p] with p = P_g(b) the peak bin b belongs to, e_g[p] = q(A[p][i1(g-1)]) -
@@ -71,7 +76,7 @@ static_assert(LK_CHUNK % 4 == 0, "16-byte stores need chunks of whole units");
 struct LkArgs {
     const float* A; const float* M; float* out;
     uint32_t* ws;                                           // per (channel, chunk): S[bins], C[bins], T[bins]
-    double src_per_out;
+    double src_per_out; const double* pos;                  // the time grid (pg_track.h): a frame source's Grid::of(args) takes its own
     long a_stride, m_stride, F_src, F_out, n_chunks;
     int bins, nb;                                           // nb = BPT * blockDim.x >= bins
     int wt_compose, wt_apply;                               // source frames in the staged window of either kernel (a power of two; 0: none)
@@ -86,9 +91,9 @@ struct LkArgs {
 template <int BPT>
 struct LkFrame { float m[BPT]; uint32_t qa[BPT]; uint32_t e[BPT]; };
 
-template <int BPT, bool LINKED>
+template <typename Grid, int BPT, bool LINKED>
 __device__ __forceinline__ void lk_load(const LkArgs& a, const float* Ac, const float* Mc, const float* Xc, long g, LkFrame<BPT>& f) {
-    const tk::Advance adv = tk::advance(g, a.src_per_out, a.F_src);
+    const tk::Advance adv = tk::advance(Grid::of(a), g, a.F_src);
     const long i0 = adv.i0, i1p = adv.i1p;
 #pragma unroll
     for (int j = 0; j < BPT; ++j) {
@@ -110,14 +115,15 @@ __device__ __forceinline__ void lk_load(const LkArgs& a, const float* Ac, const 
 // conflicts).  ws0: the window's first source frame, -1 before the first load; uniform over the workgroup, as is every branch here.
 // A frame whose two positions are further apart than a window (src_per_out >= wt), or a plane too wide for a window to fit into LDS
 // beside the maps (wt == 0), is read by every thread from its own rows instead.  LINKED: a third plane, q(X) of the workgroup's
-// channel, is staged beside the reference's two and is what f.qa holds.
-template <int BPT, bool LINKED>
+// channel, is staged beside the reference's two and is what f.qa holds.  Nothing here needs the positions to grow with g: under a
+// mapped grid a frame behind the window reloads it and a jump wider than the window reads the rows.
+template <typename Grid, int BPT, bool LINKED>
 __device__ __forceinline__ void lk_fetch(const LkArgs& a, const float* Ac, const float* Mc, const float* Xc, long g, uint32_t* win, int wt,
                                          long& ws0, LkFrame<BPT>& f) {
-    const tk::Advance adv = tk::advance(g, a.src_per_out, a.F_src);
+    const tk::Advance adv = tk::advance(Grid::of(a), g, a.F_src);
     const long i0 = adv.i0, i1p = adv.i1p;
     const long lo = i0 < i1p ? i0 : i1p, hi = i0 < i1p ? i1p : i0;
-    if (wt == 0 || hi - lo >= wt) { lk_load<BPT, LINKED>(a, Ac, Mc, Xc, g, f); return; }
+    if (wt == 0 || hi - lo >= wt) { lk_load<Grid, BPT, LINKED>(a, Ac, Mc, Xc, g, f); return; }
     const int pitch = wt + 1, tid = threadIdx.x, nt = blockDim.x;
     uint32_t* winM = win;
     uint32_t* winA = win + a.nb * pitch;
@@ -158,14 +164,16 @@ __device__ __forceinline__ void lk_fetch(const LkArgs& a, const float* Ac, const
 // when a region starts again from zero (reset) and what is added at the output (f.qa).  PLANES: planes in the staged window.
 // LINKED: every channel of the launch reads channel 0's T from the workspace and its own plane Xc beside the shared (Ac, Mc).
 
-// pg_phase_lock: the stretched time grid over M and q(A); the advance is measured on A; a quiet peak resets; q(A) is added.
+// pg_phase_lock: the time grid `Grid` (uniform, or pg_phase_lock_map's table) over M and q(A); the advance is measured on A; a quiet
+// peak resets; q(A) is added.
+template <typename Grid>
 struct LockSrc {
     static constexpr int PLANES = 2;
     static constexpr bool EARLY = true;
     static constexpr bool LINKED = false;
     template <int BPT>
     static __device__ __forceinline__ void fetch(const LkArgs& a, const float* Ac, const float* Mc, const float*, long g, uint32_t* win, int wt,
-                                                 long& ws0, LkFrame<BPT>& f) { lk_fetch<BPT, false>(a, Ac, Mc, nullptr, g, win, wt, ws0, f); }
+                                                 long& ws0, LkFrame<BPT>& f) { lk_fetch<Grid, BPT, false>(a, Ac, Mc, nullptr, g, win, wt, ws0, f); }
     static __device__ __forceinline__ uint32_t advance(const LkArgs&, const uint32_t*, int) { return 0u; }
     static __device__ __forceinline__ bool reset(const LkArgs& a, long g, const uint32_t* msf, int p) {
         return g == 0 || __uint_as_float(msf[p]) < a.reset_below;
@@ -175,12 +183,13 @@ struct LockSrc {
 // pg_phase_lock_linked, the apply launch alone: LockSrc on the reference's planes (Ac = Aref, Mc = Mref, shared by all channels:
 // the maps, the advances and the resets are pg_phase_lock's of the reference, and compose and carry ARE LockSrc's, run once), but
 // what is added at the output is q(X) of the workgroup's own channel, a third plane of the window.
-struct LinkSrc : LockSrc {
+template <typename Grid>
+struct LinkSrc : LockSrc<Grid> {
     static constexpr int PLANES = 3;
     static constexpr bool LINKED = true;
     template <int BPT>
     static __device__ __forceinline__ void fetch(const LkArgs& a, const float* Ac, const float* Mc, const float* Xc, long g, uint32_t* win,
-                                                 int wt, long& ws0, LkFrame<BPT>& f) { lk_fetch<BPT, true>(a, Ac, Mc, Xc, g, win, wt, ws0, f); }
+                                                 int wt, long& ws0, LkFrame<BPT>& f) { lk_fetch<Grid, BPT, true>(a, Ac, Mc, Xc, g, win, wt, ws0, f); }
 };
 
 // pg_phase_spsi: M on the output grid itself (frame g is column g; no A); the advance of bin p is its interpolated frequency times
@@ -559,12 +568,30 @@ extern "C" int pg_phase_lock(const pg_phase_lock_args* a, void* stream) {
     if (need < 0) return (int)need;
     if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_lock: workspace missing or smaller than pg_workspace_bytes_phase_lock()");
     k.bin0 = 0; k.hop_per_fft = 0.0; k.X = nullptr; k.x_stride = 0;
-    return lk_scan<LockSrc, LockSrc>("phase_lock", k, a->n_ch, a->n_ch, a->F_out, a->workspace, wide, stream);
+    return lk_scan<LockSrc<tk::UniformGrid>, LockSrc<tk::UniformGrid>>("phase_lock", k, a->n_ch, a->n_ch, a->F_out, a->workspace, wide, stream);
+}
+
+// pg_phase_lock over the positions of a table: the same three launches on LockSrc<tk::MappedGrid>, the same workspace
+extern "C" int64_t pg_workspace_bytes_phase_lock_map(const pg_phase_lock_map_args* a) {
+    if (!a) return pg_fail(PG_ERR_NULL, "phase_lock_map: args required");
+    return lk_workspace_bytes("phase_lock_map", a->n_ch, a->bins, a->F_out);
+}
+
+extern "C" int pg_phase_lock_map(const pg_phase_lock_map_args* a, void* stream) {
+    LkArgs k;
+    bool wide;
+    if (int e = pg_stretch_map_check("phase_lock_map", true, LK_MAX_BINS, a, k, wide)) return e;
+    if (((uintptr_t)a->workspace) & 3) return pg_fail(PG_ERR_ALIGN, "phase_lock_map: misaligned pointer");
+    const int64_t need = lk_workspace_bytes("phase_lock_map", a->n_ch, a->bins, a->F_out);
+    if (need < 0) return (int)need;
+    if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_lock_map: workspace missing or smaller than pg_workspace_bytes_phase_lock_map()");
+    k.bin0 = 0; k.hop_per_fft = 0.0; k.X = nullptr; k.x_stride = 0;
+    return lk_scan<LockSrc<tk::MappedGrid>, LockSrc<tk::MappedGrid>>("phase_lock_map", k, a->n_ch, a->n_ch, a->F_out, a->workspace, wide, stream);
 }
 
 // one channel's worth whatever n_ch: the scan is the reference's alone
-static int64_t lk_linked_workspace_bytes(int n_ch, int bins, int64_t F_out) {
-    const int64_t all = lk_workspace_bytes("phase_lock_linked", n_ch, bins, F_out);   // (n_ch > 0, and the apply grid's (channel, chunk) pairs)
+static int64_t lk_linked_workspace_bytes(int n_ch, int bins, int64_t F_out, const char* op = "phase_lock_linked") {
+    const int64_t all = lk_workspace_bytes(op, n_ch, bins, F_out);                    // (n_ch > 0, and the apply grid's (channel, chunk) pairs)
     return all < 0 ? all : all / n_ch;
 }
 
@@ -591,13 +618,43 @@ extern "C" int pg_phase_lock_linked(const pg_phase_lock_linked_args* a, void* st
     LkArgs k;
     k.A = a->Aref; k.M = a->Mref; k.out = a->out;           // the scan's planes, shared by every channel: strides 0
     k.X = a->A; k.x_stride = a->n_ch == 1 ? 0 : a->a_stride;
-    k.src_per_out = a->src_per_out;
+    k.src_per_out = a->src_per_out; k.pos = nullptr;
     k.a_stride = 0; k.m_stride = 0;
     k.F_src = a->F_src; k.F_out = a->F_out;
     k.bins = a->bins; k.reset_below = a->reset_below;
     k.bin0 = 0; k.hop_per_fft = 0.0;
     const bool wide = (a->F_out & 3) == 0 && pg_al16(a->out);
-    return lk_scan<LockSrc, LinkSrc>("phase_lock_linked", k, 1, a->n_ch, a->F_out, a->workspace, wide, stream);
+    return lk_scan<LockSrc<tk::UniformGrid>, LinkSrc<tk::UniformGrid>>("phase_lock_linked", k, 1, a->n_ch, a->F_out, a->workspace, wide, stream);
+}
+
+extern "C" int64_t pg_workspace_bytes_phase_lock_linked_map(const pg_phase_lock_linked_map_args* a) {
+    if (!a) return pg_fail(PG_ERR_NULL, "phase_lock_linked_map: args required");
+    return lk_linked_workspace_bytes(a->n_ch, a->bins, a->F_out, "phase_lock_linked_map");
+}
+
+// (pg_phase_lock_linked's checks in its order, without the src_per_out row and the rows no int32 size can reach, with `pos`)
+extern "C" int pg_phase_lock_linked_map(const pg_phase_lock_linked_map_args* a, void* stream) {
+    if (!a || !a->A || !a->Aref || !a->Mref || !a->out || !a->pos) return pg_fail(PG_ERR_NULL, "phase_lock_linked_map: args, A, Aref, Mref, out and pos required");
+    if (a->n_ch <= 0 || a->bins <= 0 || a->F_src <= 0 || a->F_out <= 0) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked_map: non-positive dimension");
+    if (a->bins > LK_MAX_BINS) return pg_failf(PG_ERR_SHAPE, "phase_lock_linked_map: more than %d bins", LK_MAX_BINS);
+    if (!(a->reset_below >= 0.0f) || !pg_finite(a->reset_below)) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked_map: reset_below must be finite and not negative");
+    if (a->a_ch_rows < a->bins) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked_map: a_ch_rows shorter than a plane");
+    if ((((uintptr_t)a->A) & 3) || (((uintptr_t)a->Aref) & 3) || (((uintptr_t)a->Mref) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->workspace) & 3)
+        || (((uintptr_t)a->pos) & 7))
+        return pg_fail(PG_ERR_ALIGN, "phase_lock_linked_map: misaligned pointer");
+    const int64_t need = lk_linked_workspace_bytes(a->n_ch, a->bins, a->F_out, "phase_lock_linked_map");
+    if (need < 0) return (int)need;
+    if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_lock_linked_map: workspace missing or smaller than pg_workspace_bytes_phase_lock_linked_map()");
+    LkArgs k;
+    k.A = a->Aref; k.M = a->Mref; k.out = a->out;           // the scan's planes, shared by every channel: strides 0
+    k.X = a->A; k.x_stride = a->n_ch == 1 ? 0 : (long)a->a_ch_rows * a->F_src;
+    k.src_per_out = 0.0; k.pos = a->pos;
+    k.a_stride = 0; k.m_stride = 0;
+    k.F_src = a->F_src; k.F_out = a->F_out;
+    k.bins = a->bins; k.reset_below = a->reset_below;
+    k.bin0 = 0; k.hop_per_fft = 0.0;
+    const bool wide = (a->F_out & 3) == 0 && pg_al16(a->out);
+    return lk_scan<LockSrc<tk::MappedGrid>, LinkSrc<tk::MappedGrid>>("phase_lock_linked_map", k, 1, a->n_ch, a->F_out, a->workspace, wide, stream);
 }
 
 extern "C" int64_t pg_workspace_bytes_phase_spsi(const pg_phase_spsi_args* a) {
@@ -621,7 +678,7 @@ extern "C" int pg_phase_spsi(const pg_phase_spsi_args* a, void* stream) {
     if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_spsi: workspace missing or smaller than pg_workspace_bytes_phase_spsi()");
     LkArgs k;
     k.A = nullptr; k.M = a->M; k.out = a->out;
-    k.src_per_out = 1.0;                                     // the identity grid: frame g of `out` is column g of M
+    k.src_per_out = 1.0; k.pos = nullptr;                    // the identity grid: frame g of `out` is column g of M
     k.a_stride = 0; k.m_stride = a->n_ch == 1 ? 0 : a->m_stride;
     k.F_src = a->F; k.F_out = a->F;
     k.bins = a->bins; k.reset_below = 0.0f;

@@ -27,10 +27,34 @@ __device__ __forceinline__ uint32_t q(float x) {
 
 __device__ __forceinline__ float angle(uint32_t acc) { return (float)((double)(int32_t)acc * R); }
 
-// ---- The stretched time grid: output frame g (>= 0) sits at p = (double)g * src_per_out of the source, between the source frames
-// i0 = min((int64)floor(p), F_src - 1) and i1 = min(i0 + 1, F_src - 1).
-__device__ __forceinline__ long i0(long g, double spo, long F_src) {
-    const double fl = floor((double)g * spo);
+// ---- The time grid: output frame g (>= 0) sits at position p of the source, between the source frames
+// i0 = min((int64)floor(p), F_src - 1) and i1 = min(i0 + 1, F_src - 1).  The grid is a TYPE, and every kernel that walks it is
+// instantiated on both:
+//   UniformGrid   p = (double)g * src_per_out: the stretched grid of pg_spec_clips, pg_phase_vocoder, pg_phase_lock(_linked).
+//   MappedGrid    p = pc(pos[g]), pos a device table of doubles with one entry per output frame (the *_map entry points), and
+//                 pc(p) = !(p >= 0) ? 0 : (p > 2^52 ? 2^52 : p): a NaN and a negative position count as 0, and beyond 2^52
+//                 floor(p) == p.  From pc on everything is the uniform grid's arithmetic, word for word, so a table that holds
+//                 (double)g * src_per_out gives the uniform grid's bits; whatever the table holds, 0 <= i0 <= i1 <= F_src - 1 and no
+//                 read leaves a plane.  Positions need not be monotone: a frozen or backward table is legal.
+// A kernel's argument struct holds both fields (src_per_out, pos) and Grid::of(args) picks its own.
+struct UniformGrid {
+    double spo;
+    template <typename Args> static __device__ __forceinline__ UniformGrid of(const Args& a) { return UniformGrid{a.src_per_out}; }
+    __device__ __forceinline__ double at(long g) const { return (double)g * spo; }
+};
+
+struct MappedGrid {
+    const double* pos;
+    template <typename Args> static __device__ __forceinline__ MappedGrid of(const Args& a) { return MappedGrid{a.pos}; }
+    __device__ __forceinline__ double at(long g) const {
+        const double p = pos[g];
+        return !(p >= 0.0) ? 0.0 : (p > 4503599627370496.0 ? 4503599627370496.0 : p);
+    }
+};
+
+template <typename Grid>
+__device__ __forceinline__ long i0(const Grid& gr, long g, long F_src) {
+    const double fl = floor(gr.at(g));
     return fl < (double)F_src ? (long)fl : F_src - 1;        // (also for a position beyond the int64 range)
 }
 
@@ -38,10 +62,11 @@ __device__ __forceinline__ long i1(long i0, long F_src) { return i0 + 1 < F_src 
 
 // the advance into frame g is measured between i1(g - 1) and i0(g); frame 0 has none (i1p == i0)
 struct Advance { long i0, i1p; };
-__device__ __forceinline__ Advance advance(long g, double spo, long F_src) {
+template <typename Grid>
+__device__ __forceinline__ Advance advance(const Grid& gr, long g, long F_src) {
     Advance s;
-    s.i0 = i0(g, spo, F_src);
-    s.i1p = g > 0 ? i1(i0(g - 1, spo, F_src), F_src) : s.i0;
+    s.i0 = i0(gr, g, F_src);
+    s.i1p = g > 0 ? i1(i0(gr, g - 1, F_src), F_src) : s.i0;
     return s;
 }
 
@@ -118,6 +143,29 @@ int pg_stretch_check(const char* op, bool need_M, int max_bins, const Args* a, K
     k.A = a->A; k.M = a->M; k.out = a->out;
     k.src_per_out = a->src_per_out;
     k.a_stride = a->n_ch == 1 ? 0 : a->a_stride; k.m_stride = a->n_ch == 1 ? 0 : a->m_stride;
+    k.F_src = a->F_src; k.F_out = a->F_out;
+    k.bins = a->bins; k.reset_below = a->reset_below;
+    k.pos = nullptr;
+    return PG_OK;
+}
+
+// The same for the mapped twins (pg_phase_vocoder_map_args, or pg_phase_lock_map_args, which begins with the same fields): the rows
+// of pg_stretch_check in its order, without the src_per_out row, with `pos` in the NULL row and its 8-byte alignment in the ALIGN
+// row.  Every size is an int32 and a channel stride is a count of rows, so no plane reaches 2^62 elements and those rows are gone.
+template <typename Args, typename KernelArgs>
+int pg_stretch_map_check(const char* op, bool need_M, int max_bins, const Args* a, KernelArgs& k, bool& wide) {
+    if (!a || !a->A || (need_M && !a->M) || !a->out || !a->pos) return pg_failf(PG_ERR_NULL, "%s: args, A%s, out and pos required", op, need_M ? ", M" : "");
+    if (a->n_ch <= 0 || a->bins <= 0 || a->F_src <= 0 || a->F_out <= 0) return pg_failf(PG_ERR_SHAPE, "%s: non-positive dimension", op);
+    if (a->bins > max_bins) return pg_failf(PG_ERR_SHAPE, "%s: more than %d bins", op, max_bins);
+    if (!(a->reset_below >= 0.0f) || !pg_finite(a->reset_below)) return pg_failf(PG_ERR_SHAPE, "%s: reset_below must be finite and not negative", op);
+    if (a->a_ch_rows < a->bins) return pg_failf(PG_ERR_SHAPE, "%s: a_ch_rows shorter than a plane", op);
+    if (a->M && a->m_ch_rows < a->bins) return pg_failf(PG_ERR_SHAPE, "%s: m_ch_rows shorter than a plane", op);
+    if ((((uintptr_t)a->A) & 3) || (((uintptr_t)a->M) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->pos) & 7))
+        return pg_failf(PG_ERR_ALIGN, "%s: misaligned pointer", op);
+    wide = (a->F_out & 3) == 0 && pg_al16(a->out);
+    k.A = a->A; k.M = a->M; k.out = a->out;
+    k.src_per_out = 0.0; k.pos = a->pos;
+    k.a_stride = a->n_ch == 1 ? 0 : (long)a->a_ch_rows * a->F_src; k.m_stride = a->n_ch == 1 ? 0 : (long)a->m_ch_rows * a->F_src;
     k.F_src = a->F_src; k.F_out = a->F_out;
     k.bins = a->bins; k.reset_below = a->reset_below;
     return PG_OK;

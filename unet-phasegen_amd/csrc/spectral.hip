@@ -10,7 +10,8 @@
 // source frames i0, i1 around it are pg_track.h's time grid (the one pg_phase_vocoder and pg_phase_lock read A and M on);
 // w = (float)(p - floor(p)); out = P[i0] bit for bit when w == 0, else fl(a + fl(w fl(b1 - a))) with a = P[i0], b1 = P[i1] in
 // fp32, nothing contracted (-ffp-contract=off).  src_per_out == 1.0 is therefore a copy (clamped at the last source frame), and
-// n_clips = 1 resamples a whole plane.
+// n_clips = 1 resamples a whole plane.  pg_spec_clips_map is the same kernel on pg_track.h's MappedGrid: p = pc(pos[g]) from a table
+// of (n_clips - 1) sf + frames doubles (tests/_map_ref.py); it has the frame-by-frame path alone.
 //
 // pg_phase_join.  Which clips cover a global frame and where the crossfade reads them is pg_track.h's join, the code pg_stitch cuts
 // its samples by; only the blend differs.  A shared frame, with a = ramp[Vf-1-j], b = ramp[j], lo = phi[k-1][j + sf], hi = phi[k][j]:
@@ -40,15 +41,16 @@ constexpr int SP_THREADS = 256;
 
 struct ScKernelArgs {
     const float* P; float* out;
-    double src_per_out;
+    double src_per_out; const double* pos;                        // the time grid (pg_track.h): Grid::of(args) takes its own
     long p_stride, F_src, sf, units_per_row, units;
     int n_ch, bins, frames;
 };
 
 // one output frame: global frame g of the source row `row`
-__device__ __forceinline__ float sc_one(const float* row, long g, double spo, long F_src) {
-    const double p = (double)g * spo;
-    const long i0 = tk::i0(g, spo, F_src), i1 = tk::i1(i0, F_src);
+template <typename Grid>
+__device__ __forceinline__ float sc_one(const float* row, long g, const Grid& grid, long F_src) {
+    const double p = grid.at(g);
+    const long i0 = tk::i0(grid, g, F_src), i1 = tk::i1(i0, F_src);
     const float w = (float)(p - floor(p));
     const float a = row[i0];
     if (w == 0.0f) return a;
@@ -57,8 +59,9 @@ __device__ __forceinline__ float sc_one(const float* row, long g, double spo, lo
     return a + m;
 }
 
-template <bool VEC>
+template <typename Grid, bool VEC>
 __global__ __launch_bounds__(SP_THREADS) void spec_clips_kernel(const ScKernelArgs a) {
+    const Grid grid = Grid::of(a);
     const long stride = (long)gridDim.x * SP_THREADS;
     for (long u = (long)blockIdx.x * SP_THREADS + threadIdx.x; u < a.units; u += stride) {
         const long r = u / a.units_per_row, f0 = (u - r * a.units_per_row) * 4;         // r = (k n_ch + c) bins + b
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(SP_THREADS) void spec_clips_kernel(const ScKernelAr
             *(f32x4*)op = v;
         } else {
             const int n = a.frames - f0 < 4 ? (int)(a.frames - f0) : 4;
-            for (int i = 0; i < n; ++i) op[i] = sc_one(row, g + i, a.src_per_out, a.F_src);
+            for (int i = 0; i < n; ++i) op[i] = sc_one(row, g + i, grid, a.F_src);
         }
     }
 }
@@ -129,15 +132,34 @@ extern "C" int pg_spec_clips(const pg_spec_clips_args* a, void* stream) {
     const bool wide = a->src_per_out == 1.0 && (a->sf & 3) == 0 && (a->frames & 3) == 0 && (a->F_src & 3) == 0
                       && (a->n_ch == 1 || (a->p_stride & 3) == 0) && pg_al16(a->P) && pg_al16(a->out);
     ScKernelArgs k;
-    k.P = a->P; k.out = a->out; k.src_per_out = a->src_per_out;
+    k.P = a->P; k.out = a->out; k.src_per_out = a->src_per_out; k.pos = nullptr;
     k.p_stride = a->n_ch == 1 ? 0 : a->p_stride; k.F_src = a->F_src; k.sf = a->sf;
     k.units_per_row = ((long)a->frames + 3) / 4; k.units = k.units_per_row * rows;
     k.n_ch = a->n_ch; k.bins = a->bins; k.frames = a->frames;
     const unsigned grid = pg_stream_grid(k.units, SP_THREADS);
     hipStream_t st = (hipStream_t)stream;
-    if (wide) hipLaunchKernelGGL(spec_clips_kernel<true>, dim3(grid), dim3(SP_THREADS), 0, st, k);
-    else hipLaunchKernelGGL(spec_clips_kernel<false>, dim3(grid), dim3(SP_THREADS), 0, st, k);
+    if (wide) hipLaunchKernelGGL((spec_clips_kernel<tk::UniformGrid, true>), dim3(grid), dim3(SP_THREADS), 0, st, k);
+    else hipLaunchKernelGGL((spec_clips_kernel<tk::UniformGrid, false>), dim3(grid), dim3(SP_THREADS), 0, st, k);
     return pg_launch_ok("spec_clips launch failed");
+}
+
+// pg_spec_clips over the positions of a table (tk::MappedGrid): the frame-by-frame path alone -- the 16-byte path is rate 1's
+extern "C" int pg_spec_clips_map(const pg_spec_clips_map_args* a, void* stream) {
+    if (!a || !a->P || !a->out || !a->pos) return pg_fail(PG_ERR_NULL, "spec_clips_map: args, P, out and pos required");
+    if (a->n_clips <= 0 || a->n_ch <= 0 || a->bins <= 0 || a->frames <= 0 || a->F_src <= 0) return pg_fail(PG_ERR_SHAPE, "spec_clips_map: non-positive dimension");
+    if (a->sf < 1) return pg_fail(PG_ERR_SHAPE, "spec_clips_map: sf must be at least 1");
+    if (a->p_ch_rows < a->bins) return pg_fail(PG_ERR_SHAPE, "spec_clips_map: p_ch_rows shorter than a plane");
+    const int64_t rows = (int64_t)a->n_clips * a->n_ch * a->bins;
+    if (rows > INT64_MAX / 2 / a->frames) return pg_fail(PG_ERR_SHAPE, "spec_clips_map: output beyond 2^62 elements");
+    if ((((uintptr_t)a->P) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->pos) & 7)) return pg_fail(PG_ERR_ALIGN, "spec_clips_map: misaligned pointer");
+    ScKernelArgs k;
+    k.P = a->P; k.out = a->out; k.src_per_out = 0.0; k.pos = a->pos;
+    k.p_stride = a->n_ch == 1 ? 0 : (long)a->p_ch_rows * a->F_src; k.F_src = a->F_src; k.sf = a->sf;
+    k.units_per_row = ((long)a->frames + 3) / 4; k.units = k.units_per_row * rows;
+    k.n_ch = a->n_ch; k.bins = a->bins; k.frames = a->frames;
+    const unsigned grid = pg_stream_grid(k.units, SP_THREADS);
+    hipLaunchKernelGGL((spec_clips_kernel<tk::MappedGrid, false>), dim3(grid), dim3(SP_THREADS), 0, (hipStream_t)stream, k);
+    return pg_launch_ok("spec_clips_map launch failed");
 }
 
 extern "C" int pg_phase_join(const pg_phase_join_args* a, void* stream) {

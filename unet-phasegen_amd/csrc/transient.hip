@@ -29,6 +29,8 @@
 // copied to LDS once per workgroup (at most 16 KiB).  16-byte stores where y and its row stride allow, sample by sample otherwise
 // and for the last, partial quadruple of a row; the same function forms every sample on both paths.  No atomics, no workspace.
 // Built with -ffp-contract=off like the rest; all index arithmetic is 64-bit.  Measurements: DESIGN.md section 4.15.
+// pg_ola_stretch_map is the same kernel with the centre read from a table, one double per frame (OlMapped below; tests/_map_ref.py;
+// DESIGN.md section 4.19).
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -183,16 +185,41 @@ constexpr int OL_MAX_WIN = 4096;
 
 struct OlKernelArgs {
     const float* x; const float* win; const float* base; float* y;
-    double src_per_out;
+    double src_per_out; const double* pos;                            // the grain grid below: Grid::of(args) takes its own
     long x_stride, base_stride, y_stride, n_in, n_out, units_per_row, units;
     int w, hop;
+};
+
+// The sample-grid twin of pg_track.h's time grid: where grain g, centred on output sample g hop, has its centre in the input.
+//   OlUniform   cd = rint((double)(g hop) * src_per_out); never negative, so "beyond 2^62" is one comparison.
+//   OlMapped    cd = rint(pos[g]), pos one double per grain: a centre that is NaN or beyond +-2^62 is outside every signal.  The
+//               table ends with the last grain that covers an output sample, (n_out + w/2) / hop; a thread's unit of four may
+//               reach one grain further, which covers only samples past the row's end, and last() stops there.
+struct OlUniform {
+    double spo;
+    static __device__ __forceinline__ OlUniform of(const OlKernelArgs& a) { return OlUniform{a.src_per_out}; }
+    __device__ __forceinline__ double centre(long g, long gh) const { return rint((double)gh * spo); }
+    static __device__ __forceinline__ bool inside(double cd) { return cd < 4611686018427387904.0; }
+    __device__ __forceinline__ long last(long g_hi, const OlKernelArgs&) const { return g_hi; }
+};
+
+struct OlMapped {
+    const double* pos;
+    static __device__ __forceinline__ OlMapped of(const OlKernelArgs& a) { return OlMapped{a.pos}; }
+    __device__ __forceinline__ double centre(long g, long) const { return rint(pos[g]); }
+    static __device__ __forceinline__ bool inside(double cd) { return fabs(cd) < 4611686018427387904.0; }   // (false for a NaN)
+    __device__ __forceinline__ long last(long g_hi, const OlKernelArgs& a) const {
+        const long end = (a.n_out + a.w / 2) / a.hop;
+        return g_hi < end ? g_hi : end;
+    }
 };
 
 // floor(a / b) for b > 0
 __device__ __forceinline__ long ol_floor_div(long a, long b) { const long q = a / b; return (a % b != 0 && a < 0) ? q - 1 : q; }
 
-template <bool VEC>
+template <typename Grid, bool VEC>
 __global__ __launch_bounds__(OL_THREADS) void ola_stretch_kernel(const OlKernelArgs a) {
+    const Grid grid = Grid::of(a);
     __shared__ float win[OL_MAX_WIN];
     for (int j = threadIdx.x; j < a.w; j += OL_THREADS) win[j] = a.win[j];
     __syncthreads();
@@ -205,12 +232,12 @@ __global__ __launch_bounds__(OL_THREADS) void ola_stretch_kernel(const OlKernelA
         // the frames that cover t: g hop - w/2 <= t <= g hop + w/2 - 1, g >= 0
         long g_lo = ol_floor_div(t0 - half + a.hop, a.hop);           // ceil((t0 - w/2 + 1) / hop)
         if (g_lo < 0) g_lo = 0;
-        const long g_hi = (t0 + 3 + half) / a.hop;
+        const long g_hi = grid.last((t0 + 3 + half) / a.hop, a);
         float den[4] = {0.0f, 0.0f, 0.0f, 0.0f}, num[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         for (long g = g_lo; g <= g_hi; ++g) {
             const long gh = g * a.hop;
-            const double cd = rint((double)gh * a.src_per_out);
-            const bool inside = cd < 4611686018427387904.0;           // a centre beyond 2^62 is outside every signal
+            const double cd = grid.centre(g, gh);
+            const bool inside = Grid::inside(cd);                     // a centre beyond 2^62 is outside every signal
             const long cg = inside ? (long)cd : 0;
             const long j0 = t0 - gh + half;
 #pragma unroll
@@ -294,7 +321,7 @@ extern "C" int pg_ola_stretch(const pg_ola_stretch_args* a, void* stream) {
         return pg_fail(PG_ERR_ALIGN, "ola_stretch: misaligned pointer");
     OlKernelArgs k;
     k.x = a->x; k.win = a->win; k.base = a->base; k.y = a->y;
-    k.src_per_out = a->src_per_out;
+    k.src_per_out = a->src_per_out; k.pos = nullptr;
     const bool one = a->n_sig == 1;                                   // (a stride that is never applied does not decide)
     k.x_stride = one ? 0 : a->x_stride; k.base_stride = one ? 0 : a->base_stride; k.y_stride = one ? 0 : a->y_stride;
     k.n_in = a->n_in; k.n_out = a->n_out;
@@ -303,7 +330,34 @@ extern "C" int pg_ola_stretch(const pg_ola_stretch_args* a, void* stream) {
     const bool wide = pg_al16(a->y) && (one || (a->y_stride & 3) == 0);
     const unsigned grid = pg_stream_grid(k.units, OL_THREADS);
     hipStream_t st = (hipStream_t)stream;
-    if (wide) hipLaunchKernelGGL(ola_stretch_kernel<true>, dim3(grid), dim3(OL_THREADS), 0, st, k);
-    else hipLaunchKernelGGL(ola_stretch_kernel<false>, dim3(grid), dim3(OL_THREADS), 0, st, k);
+    if (wide) hipLaunchKernelGGL((ola_stretch_kernel<OlUniform, true>), dim3(grid), dim3(OL_THREADS), 0, st, k);
+    else hipLaunchKernelGGL((ola_stretch_kernel<OlUniform, false>), dim3(grid), dim3(OL_THREADS), 0, st, k);
     return pg_launch_ok("ola_stretch launch failed");
+}
+
+// pg_ola_stretch with one source centre per grain (OlMapped)
+extern "C" int pg_ola_stretch_map(const pg_ola_stretch_map_args* a, void* stream) {
+    if (!a || !a->x || !a->win || !a->y || !a->pos) return pg_fail(PG_ERR_NULL, "ola_stretch_map: args, x, win, y and pos required");
+    if (a->n_sig <= 0 || a->n_in <= 0 || a->n_out <= 0) return pg_fail(PG_ERR_SHAPE, "ola_stretch_map: non-positive dimension");
+    if (!ol_window_ok(a->win_len)) return pg_failf(PG_ERR_SHAPE, "ola_stretch_map: win_len must be even and within 2 .. %d", OL_MAX_WIN);
+    if (a->hop < 1 || a->hop > a->win_len / 2) return pg_fail(PG_ERR_SHAPE, "ola_stretch_map: need 1 <= hop <= win_len / 2");
+    if (a->x_stride < a->n_in) return pg_fail(PG_ERR_SHAPE, "ola_stretch_map: x_stride shorter than a row");
+    if (a->y_stride < a->n_out) return pg_fail(PG_ERR_SHAPE, "ola_stretch_map: y_stride shorter than a row");
+    if (a->base && a->base_stride < a->n_out) return pg_fail(PG_ERR_SHAPE, "ola_stretch_map: base_stride shorter than a row");
+    if ((((uintptr_t)a->x) & 3) || (((uintptr_t)a->win) & 3) || (((uintptr_t)a->base) & 3) || (((uintptr_t)a->y) & 3) || (((uintptr_t)a->pos) & 7))
+        return pg_fail(PG_ERR_ALIGN, "ola_stretch_map: misaligned pointer");
+    OlKernelArgs k;
+    k.x = a->x; k.win = a->win; k.base = a->base; k.y = a->y;
+    k.src_per_out = 0.0; k.pos = a->pos;
+    const bool one = a->n_sig == 1;                                   // (a stride that is never applied does not decide)
+    k.x_stride = one ? 0 : a->x_stride; k.base_stride = one ? 0 : a->base_stride; k.y_stride = one ? 0 : a->y_stride;
+    k.n_in = a->n_in; k.n_out = a->n_out;
+    k.units_per_row = ((long)a->n_out + 3) / 4; k.units = k.units_per_row * a->n_sig;
+    k.w = a->win_len; k.hop = a->hop;
+    const bool wide = pg_al16(a->y) && (one || (a->y_stride & 3) == 0);
+    const unsigned grid = pg_stream_grid(k.units, OL_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (wide) hipLaunchKernelGGL((ola_stretch_kernel<OlMapped, true>), dim3(grid), dim3(OL_THREADS), 0, st, k);
+    else hipLaunchKernelGGL((ola_stretch_kernel<OlMapped, false>), dim3(grid), dim3(OL_THREADS), 0, st, k);
+    return pg_launch_ok("ola_stretch_map launch failed");
 }

@@ -19,6 +19,9 @@
 // register into the next chunk.  Source reads are gathers at i0 / i1, monotone in g: they coalesce and hit cache.  Stores are 16-byte
 // when `out` and F_out allow and frame by frame otherwise; both paths give the same bits.  All index arithmetic is 64-bit; q() is one
 // double multiply (nothing to contract; the file is built with -ffp-contract=off like the rest).  Measurements: DESIGN.md section 4.11.
+//
+// pg_phase_vocoder_map is the same kernel on pg_track.h's MappedGrid: i0(g) comes from pc(pos[g]), pos a table of F_out doubles, and
+// need not grow with g (the gathers are then no longer monotone; nothing else depends on it).  tests/_map_ref.py; DESIGN.md 4.19.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -36,14 +39,15 @@ constexpr int PV_WAVES = PV_THREADS / 64;
 
 struct PvKernelArgs {
     const float* A; const float* M; float* out;
-    double src_per_out;
+    double src_per_out; const double* pos;                    // the grid: Grid::of(args) takes its own
     long a_stride, m_stride, F_src, F_out, rows;
     int bins;
     float reset_below;
 };
 
-template <bool VEC>
+template <typename Grid, bool VEC>
 __global__ __launch_bounds__(PV_THREADS) void phase_vocoder_kernel(const PvKernelArgs a) {
+    const Grid grid = Grid::of(a);
     __shared__ uint32_t wave_v[2][PV_WAVES];
     __shared__ uint32_t wave_f[2][PV_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -66,7 +70,7 @@ __global__ __launch_bounds__(PV_THREADS) void phase_vocoder_kernel(const PvKerne
             for (int j = 0; j <= PV_PER_THREAD; ++j) {
                 long g = g0 - 1 + j;
                 g = g < 0 ? 0 : (g < a.F_out ? g : a.F_out - 1);
-                i0[j] = tk::i0(g, a.src_per_out, a.F_src);
+                i0[j] = tk::i0(grid, g, a.F_src);
                 q0[j] = tk::q(ar[i0[j]]);
             }
             uint32_t v[PV_PER_THREAD];
@@ -132,16 +136,29 @@ __global__ __launch_bounds__(PV_THREADS) void phase_vocoder_kernel(const PvKerne
     }
 }
 
+template <typename Grid>
+int pv_launch(PvKernelArgs& k, int n_ch, bool wide, void* stream, const char* failed) {
+    k.rows = (long)n_ch * k.bins;
+    const unsigned grid = pg_stream_grid(k.rows, 1);          // a workgroup per row
+    hipStream_t st = (hipStream_t)stream;
+    if (wide) hipLaunchKernelGGL((phase_vocoder_kernel<Grid, true>), dim3(grid), dim3(PV_THREADS), 0, st, k);
+    else hipLaunchKernelGGL((phase_vocoder_kernel<Grid, false>), dim3(grid), dim3(PV_THREADS), 0, st, k);
+    return pg_launch_ok(failed);
+}
+
 }  // namespace
 
 extern "C" int pg_phase_vocoder(const pg_phase_vocoder_args* a, void* stream) {
     PvKernelArgs k;
     bool wide;
     if (int e = pg_stretch_check("phase_vocoder", false, INT32_MAX, a, k, wide)) return e;
-    k.rows = (long)a->n_ch * a->bins;
-    const unsigned grid = pg_stream_grid(k.rows, 1);          // a workgroup per row
-    hipStream_t st = (hipStream_t)stream;
-    if (wide) hipLaunchKernelGGL(phase_vocoder_kernel<true>, dim3(grid), dim3(PV_THREADS), 0, st, k);
-    else hipLaunchKernelGGL(phase_vocoder_kernel<false>, dim3(grid), dim3(PV_THREADS), 0, st, k);
-    return pg_launch_ok("phase_vocoder launch failed");
+    return pv_launch<tk::UniformGrid>(k, a->n_ch, wide, stream, "phase_vocoder launch failed");
+}
+
+// the same scan over the positions of a table (tk::MappedGrid)
+extern "C" int pg_phase_vocoder_map(const pg_phase_vocoder_map_args* a, void* stream) {
+    PvKernelArgs k;
+    bool wide;
+    if (int e = pg_stretch_map_check("phase_vocoder_map", false, INT32_MAX, a, k, wide)) return e;
+    return pv_launch<tk::MappedGrid>(k, a->n_ch, wide, stream, "phase_vocoder_map launch failed");
 }

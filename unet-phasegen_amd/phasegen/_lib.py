@@ -241,6 +241,41 @@ class FormantArgs(C.Structure):
                 ("M", C.c_void_p), ("basis", C.c_void_p), ("env", C.c_void_p), ("out", C.c_void_p)]
 
 
+class SpecClipsMapArgs(C.Structure):
+    """pg_spec_clips_map_args: pg_spec_clips over a table of source-frame positions (include/phasegen.h).  No 64-bit integer field:
+    every size is an int32 and the channel stride is a count of rows."""
+    _fields_ = [("n_clips", C.c_int32), ("n_ch", C.c_int32), ("bins", C.c_int32), ("frames", C.c_int32),
+                ("sf", C.c_int32), ("F_src", C.c_int32), ("p_ch_rows", C.c_int32), ("_pad0", C.c_int32),
+                ("pos", C.c_void_p), ("P", C.c_void_p), ("out", C.c_void_p)]
+
+
+class PhaseVocoderMapArgs(C.Structure):
+    """pg_phase_vocoder_map_args: pg_phase_vocoder over a table of source-frame positions (include/phasegen.h)."""
+    _fields_ = [("n_ch", C.c_int32), ("bins", C.c_int32), ("F_src", C.c_int32), ("F_out", C.c_int32),
+                ("reset_below", C.c_float), ("a_ch_rows", C.c_int32), ("m_ch_rows", C.c_int32), ("_pad0", C.c_int32),
+                ("pos", C.c_void_p), ("A", C.c_void_p), ("M", C.c_void_p), ("out", C.c_void_p)]
+
+
+class PhaseLockMapArgs(C.Structure):
+    """pg_phase_lock_map_args: pg_phase_lock over a table of source-frame positions (include/phasegen.h)."""
+    _fields_ = PhaseVocoderMapArgs._fields_ + [("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class PhaseLockLinkedMapArgs(C.Structure):
+    """pg_phase_lock_linked_map_args: pg_phase_lock_linked over a table of source-frame positions (include/phasegen.h)."""
+    _fields_ = [("n_ch", C.c_int32), ("bins", C.c_int32), ("F_src", C.c_int32), ("F_out", C.c_int32),
+                ("reset_below", C.c_float), ("a_ch_rows", C.c_int32), ("_pad0", C.c_int32), ("_pad1", C.c_int32),
+                ("pos", C.c_void_p), ("A", C.c_void_p), ("Aref", C.c_void_p), ("Mref", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class OlaStretchMapArgs(C.Structure):
+    """pg_ola_stretch_map_args: pg_ola_stretch with one source centre per grain (include/phasegen.h)."""
+    _fields_ = [("n_sig", C.c_int32), ("win_len", C.c_int32), ("hop", C.c_int32), ("n_in", C.c_int32),
+                ("n_out", C.c_int32), ("x_stride", C.c_int32), ("base_stride", C.c_int32), ("y_stride", C.c_int32),
+                ("pos", C.c_void_p), ("x", C.c_void_p), ("win", C.c_void_p), ("base", C.c_void_p), ("y", C.c_void_p)]
+
+
 class WaveCompareArgs(C.Structure):
     """pg_wave_compare_args: six sums per signal of a reference / estimate pair of waveforms (include/phasegen.h)."""
     _fields_ = [("n_signals", C.c_int32), ("_pad0", C.c_int32), ("n", C.c_int64),
@@ -317,6 +352,13 @@ SYMBOLS = {
     "pg_formant_shift": (C.c_int, [C.POINTER(FormantArgs), C.c_void_p]),
     "pg_formant_basis_elems": (C.c_int64, [C.c_int32, C.c_int32]),
     "pg_formant_basis": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "pg_spec_clips_map": (C.c_int, [C.POINTER(SpecClipsMapArgs), C.c_void_p]),
+    "pg_phase_vocoder_map": (C.c_int, [C.POINTER(PhaseVocoderMapArgs), C.c_void_p]),
+    "pg_workspace_bytes_phase_lock_map": (C.c_int64, [C.POINTER(PhaseLockMapArgs)]),
+    "pg_phase_lock_map": (C.c_int, [C.POINTER(PhaseLockMapArgs), C.c_void_p]),
+    "pg_workspace_bytes_phase_lock_linked_map": (C.c_int64, [C.POINTER(PhaseLockLinkedMapArgs)]),
+    "pg_phase_lock_linked_map": (C.c_int, [C.POINTER(PhaseLockLinkedMapArgs), C.c_void_p]),
+    "pg_ola_stretch_map": (C.c_int, [C.POINTER(OlaStretchMapArgs), C.c_void_p]),
     "pg_workspace_bytes_wave_compare": (C.c_int64, [C.POINTER(WaveCompareArgs)]),
     "pg_wave_compare": (C.c_int, [C.POINTER(WaveCompareArgs), C.c_void_p]),
     "pg_workspace_bytes_spec_compare": (C.c_int64, [C.POINTER(SpecCompareArgs)]),

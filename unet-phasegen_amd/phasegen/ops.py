@@ -7,6 +7,8 @@ as plain slices ``buf[:, :n]`` / ``buf[:, n:]`` without a copy.
 """
 import contextlib
 import ctypes as C
+import functools
+import inspect
 import threading
 
 import torch
@@ -848,12 +850,57 @@ def stitch(clips, step, n_out, normalize=False, out=None, return_status=False):
     return (out, status[0], status[1]) if return_status else out
 
 
-def spec_clips(plane, n_clips, frames, sf, src_per_out=1.0, out=None):
+def _pos_keyword(fn):
+    """Decorator of the five stretch wrappers: ``fn`` takes ``pos=None`` as its last parameter, by keyword.  ``inspect.signature``
+    of the result reports the parameter list callers have always seen, without it (as phasegen.track's ``_keyword_options`` does for
+    the track functions), and ``fn.options`` lists the keyword."""
+    sig = inspect.signature(fn)
+    assert list(sig.parameters)[-1] == "pos"
+
+    @functools.wraps(fn)
+    def call(*args, pos=None, **kw):
+        return fn(*args, pos=pos, **kw)
+    call.__signature__ = sig.replace(parameters=[p for p in sig.parameters.values() if p.name != "pos"])
+    call.options = {"pos": None}
+    return call
+
+
+def _pos_table(pos, n, who, src_per_out, what):
+    """``pos`` of a mapped call: a 1-D float64 device tensor of exactly ``n`` entries (``what``), dense; a ``src_per_out`` other than
+    the default beside it is a contradiction."""
+    if src_per_out != 1.0:
+        raise ValueError(f"{who}: pos and src_per_out {src_per_out} are two time grids: pass one")
+    if not (torch.is_tensor(pos) and pos.is_cuda and pos.dtype == torch.float64 and pos.dim() == 1):
+        raise ValueError(f"{who}: pos must be a 1-D float64 device tensor")
+    if pos.shape[0] != n:
+        raise ValueError(f"{who}: pos must hold {n} entries ({what}), got {pos.shape[0]}")
+    return _dense_as(pos, torch.float64, "pos")
+
+
+def _int32_sizes(who, **sizes):
+    """the mapped entry points take int32 sizes"""
+    for name, v in sizes.items():
+        if v > 0x7fffffff:
+            raise ValueError(f"{who}: {name} = {v} does not fit the int32 sizes of a mapped call")
+
+
+def _ch_rows(stride, F_src, bins, n_ch, who, name):
+    """a channel stride in elements as the count of rows a mapped call takes"""
+    if n_ch == 1:
+        return bins
+    if stride % F_src:
+        raise ValueError(f"{who}: channels of {name} must be a whole number of rows apart for a mapped call (stride {stride}, rows of {F_src})")
+    return stride // F_src
+
+
+@_pos_keyword
+def spec_clips(plane, n_clips, frames, sf, src_per_out=1.0, out=None, pos=None):
     """Clip windows of a spectrogram plane, optionally resampled along time (pg_spec_clips): plane (n_ch, bins, F_src) float32 on the
     device, frames contiguous, rows F_src apart, the channel stride free (``pol[:, 0]`` of a (n_ch, 2, bins, F) polar tensor is read in
     place) -> (n_clips, n_ch, bins, frames), dense.  Frame f of clip k is the plane at position (k * sf + f) * src_per_out, linearly
     interpolated between its two neighbours and clamped at the last frame; src_per_out == 1.0 copies.  n_clips = 1, frames = F_out
-    resamples the whole plane."""
+    resamples the whole plane.  ``pos`` (pg_spec_clips_map): a float64 device tensor of (n_clips - 1) * sf + frames source-frame
+    positions, one per global output frame, in place of the line g * src_per_out (NaN and negatives count as 0)."""
     if not (torch.is_tensor(plane) and plane.is_cuda and plane.dtype == torch.float32 and plane.dim() == 3):
         raise ValueError("spec_clips: plane must be a 3-D float32 device tensor (n_ch, bins, F_src)")
     _on_current_device(plane, "plane")
@@ -868,6 +915,17 @@ def spec_clips(plane, n_clips, frames, sf, src_per_out=1.0, out=None):
     p_stride = plane.stride(0) if n_ch > 1 else bins * F_src
     if p_stride < bins * F_src:
         raise ValueError(f"spec_clips: channels overlap in memory (strides {plane.stride()})")
+    if pos is not None:
+        who = "spec_clips"
+        p = _pos_table(pos, (n_clips - 1) * sf + frames, who, src_per_out, "(n_clips - 1) * sf + frames")
+        _int32_sizes(who, F_src=F_src, n_clips=n_clips, frames=frames, sf=sf)
+        out = _out(out, (n_clips, n_ch, bins, frames), plane.device, who)
+        m = _lib.SpecClipsMapArgs()
+        m.n_clips, m.n_ch, m.bins, m.frames, m.sf, m.F_src = n_clips, n_ch, bins, frames, sf, F_src
+        m.p_ch_rows = _ch_rows(p_stride, F_src, bins, n_ch, who, "plane")
+        m.pos, m.P, m.out = p, plane.data_ptr(), _dense(out, "out")
+        _lib.check(_lib.load().pg_spec_clips_map(C.byref(m), _stream()), "spec_clips_map")
+        return out
     out = _out(out, (n_clips, n_ch, bins, frames), plane.device, "spec_clips")
     a = _lib.SpecClipsArgs()
     a.n_clips, a.n_ch, a.bins, a.frames, a.sf, a.F_src, a.src_per_out = n_clips, n_ch, bins, frames, sf, F_src, src_per_out
@@ -955,14 +1013,43 @@ def _stretch_args(a, who, angle, F_out, src_per_out, logmag, reset_below, out):
     return out
 
 
-def phase_vocoder(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=None):
+def _stretch_map_args(a, who, angle, F_out, src_per_out, pos, logmag, reset_below, out):
+    """``_stretch_args`` for the mapped twins (PhaseVocoderMapArgs / PhaseLockMapArgs): ``pos`` holds F_out source-frame positions."""
+    a_stride = _vocoder_plane(angle, "angle", who=who)
+    n_ch, bins, F_src = angle.shape
+    F_out, reset_below = int(F_out), float(reset_below)
+    if F_out < 1:
+        raise ValueError(f"{who}: F_out must be positive, got {F_out}")
+    a.pos = _pos_table(pos, F_out, who, float(src_per_out), "F_out")
+    if not 0.0 <= reset_below < float("inf"):
+        raise ValueError(f"{who}: reset_below must be finite and not negative, got {reset_below}")
+    _int32_sizes(who, F_src=F_src, F_out=F_out)
+    if logmag is not None:
+        a.m_ch_rows = _ch_rows(_vocoder_plane(logmag, "logmag", angle.shape, who=who), F_src, bins, n_ch, who, "logmag")
+        a.M = logmag.data_ptr()
+    out = _out(out, (n_ch, bins, F_out), angle.device, who)
+    a.n_ch, a.bins, a.F_src, a.F_out, a.reset_below = n_ch, bins, F_src, F_out, reset_below
+    a.A, a.a_ch_rows = angle.data_ptr(), _ch_rows(a_stride, F_src, bins, n_ch, who, "angle")
+    a.out = _dense(out, "out")
+    return out
+
+
+@_pos_keyword
+def phase_vocoder(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=None, pos=None):
     """The phase-vocoder phase of a time-stretched spectrogram (pg_phase_vocoder): angle (n_ch, bins, F_src) float32 on the device,
     frames contiguous, rows F_src apart, the channel stride free (``pol[:, 1]`` of a (n_ch, 2, bins, F) polar tensor is read in place)
     -> (n_ch, bins, F_out), dense, in [-pi, pi].  Output frame g sits at source position g * src_per_out (src_per_out = 1 / stretch);
     every bin's phase advances from frame to frame by the wrapped difference of the two analysis phases around that position, summed
     exactly on a 2^32 grid of the turn.  ``logmag`` (same shape, ``pol[:, 0]``) and ``reset_below``: a frame whose log-magnitude is
     below the floor takes the analysis phase itself (the transient / silence reset); without either nothing resets after frame 0.
-    src_per_out == 1.0 returns the analysis phase (to 2 pi / 2^33 and one rounding)."""
+    src_per_out == 1.0 returns the analysis phase (to 2 pi / 2^33 and one rounding).  ``pos`` (pg_phase_vocoder_map): a float64
+    device tensor of F_out source-frame positions in place of the line g * src_per_out (NaN and negatives count as 0; the positions
+    need not grow)."""
+    if pos is not None:
+        m = _lib.PhaseVocoderMapArgs()
+        out = _stretch_map_args(m, "phase_vocoder", angle, F_out, src_per_out, pos, logmag, reset_below, out)
+        _lib.check(_lib.load().pg_phase_vocoder_map(C.byref(m), _stream()), "phase_vocoder_map")
+        return out
     a = _lib.PhaseVocoderArgs()
     out = _stretch_args(a, "phase_vocoder", angle, F_out, src_per_out, logmag, reset_below, out)
     _lib.check(_lib.load().pg_phase_vocoder(C.byref(a), _stream()), "phase_vocoder")
@@ -974,15 +1061,24 @@ _lock_ws = _StreamCache()
 _caches.append(_lock_ws)
 
 
-def phase_lock(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=None):
+@_pos_keyword
+def phase_lock(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=None, pos=None):
     """The phase-vocoder phase with identity phase locking (pg_phase_lock): ``angle`` and ``logmag`` (required) as in
     ``phase_vocoder``, (n_ch, bins <= 4096, F_src) float32 on the device, read in place from a polar tensor -> (n_ch, bins, F_out),
     dense, in [-pi, pi].  In every output frame the peaks of the log-magnitude (larger than the two bins below, not smaller than the
     two above) advance by their own measured phase advance and every other bin takes the rotation of its nearest peak, so the
     analysis' phase relations inside a sinusoid's lobe survive; a peak below ``reset_below`` resets its whole region to the analysis
-    phase.  Exact on a 2^32 grid of the turn, like ``phase_vocoder``; src_per_out == 1.0 returns the analysis phase."""
+    phase.  Exact on a 2^32 grid of the turn, like ``phase_vocoder``; src_per_out == 1.0 returns the analysis phase.  ``pos``
+    (pg_phase_lock_map): F_out source-frame positions, as in ``phase_vocoder``."""
     if logmag is None:
         raise ValueError("phase_lock: logmag is required (the peaks are those of the log-magnitude)")
+    if pos is not None:
+        m = _lib.PhaseLockMapArgs()
+        out = _stretch_map_args(m, "phase_lock", angle, F_out, src_per_out, pos, logmag, reset_below, out)
+        lib = _lib.load()
+        m.workspace, m.workspace_bytes = _workspace(_lock_ws, angle.device, lib.pg_workspace_bytes_phase_lock_map(C.byref(m)), "workspace_bytes_phase_lock_map")
+        _lib.check(lib.pg_phase_lock_map(C.byref(m), _stream()), "phase_lock_map")
+        return out
     a = _lib.PhaseLockArgs()
     out = _stretch_args(a, "phase_lock", angle, F_out, src_per_out, logmag, reset_below, out)
     lib = _lib.load()
@@ -991,14 +1087,16 @@ def phase_lock(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=
     return out
 
 
-def phase_lock_linked(angle, ref_angle, ref_logmag, F_out, src_per_out=1.0, reset_below=0.0, out=None):
+@_pos_keyword
+def phase_lock_linked(angle, ref_angle, ref_logmag, F_out, src_per_out=1.0, reset_below=0.0, out=None, pos=None):
     """``phase_lock`` with the channels linked (pg_phase_lock_linked): ``angle`` (n_ch, bins <= 4096, F_src) as in ``phase_lock``, read
     in place from a polar tensor; ``ref_angle`` and ``ref_logmag``: the planes of ONE reference channel (the channel mean, in
     phasegen.track), (bins, F_src) or (1, bins, F_src), dense -> (n_ch, bins, F_out), dense, in [-pi, pi].  The peaks, the regions
     and the rotation are those ``phase_lock(ref_angle, ..., logmag=ref_logmag)`` forms, once, and every channel adds its own
     analysis phase to that one rotation: the phase difference between any two channels is the analysis' own in every cell, so the
     stereo image and the mono sum survive the stretch.  A channel equal to the reference gets ``phase_lock``'s bits;
-    src_per_out == 1.0 returns the analysis phase."""
+    src_per_out == 1.0 returns the analysis phase.  ``pos`` (pg_phase_lock_linked_map): F_out source-frame positions, as in
+    ``phase_vocoder``."""
     who = "phase_lock_linked"
     a_stride = _vocoder_plane(angle, "angle", who=who)
     n_ch, bins, F_src = angle.shape
@@ -1017,6 +1115,20 @@ def phase_lock_linked(angle, ref_angle, ref_logmag, F_out, src_per_out=1.0, rese
         raise ValueError(f"{who}: src_per_out must be finite and positive, got {src_per_out}")
     if not 0.0 <= reset_below < float("inf"):
         raise ValueError(f"{who}: reset_below must be finite and not negative, got {reset_below}")
+    if pos is not None:
+        m = _lib.PhaseLockLinkedMapArgs()
+        m.pos = _pos_table(pos, F_out, who, src_per_out, "F_out")
+        _int32_sizes(who, F_src=F_src, F_out=F_out)
+        out = _out(out, (n_ch, bins, F_out), angle.device, who)
+        m.n_ch, m.bins, m.F_src, m.F_out, m.reset_below = n_ch, bins, F_src, F_out, reset_below
+        m.A, m.a_ch_rows = angle.data_ptr(), _ch_rows(a_stride, F_src, bins, n_ch, who, "angle")
+        m.Aref, m.Mref = refs[0].data_ptr(), refs[1].data_ptr()
+        m.out = _dense(out, "out")
+        lib = _lib.load()
+        m.workspace, m.workspace_bytes = _workspace(_lock_ws, angle.device, lib.pg_workspace_bytes_phase_lock_linked_map(C.byref(m)),
+                                                    "workspace_bytes_phase_lock_linked_map")
+        _lib.check(lib.pg_phase_lock_linked_map(C.byref(m), _stream()), "phase_lock_linked_map")
+        return out
     out = _out(out, (n_ch, bins, F_out), angle.device, who)
     a = _lib.PhaseLockLinkedArgs()
     a.n_ch, a.bins, a.F_src, a.F_out, a.src_per_out, a.reset_below = n_ch, bins, F_src, F_out, src_per_out, reset_below
@@ -1113,13 +1225,21 @@ def _ola_rows(t, name, who):
     return t2
 
 
-def ola_stretch(x, n_out, src_per_out=1.0, win_len=256, hop=64, base=None, out=None):
+def ola_grains(n_out, win_len=256, hop=64):
+    """How many grains cover the ``n_out`` output samples of ``ola_stretch``: the entries of its ``pos`` table."""
+    return (int(n_out) + int(win_len) // 2) // int(hop) + 1
+
+
+@_pos_keyword
+def ola_stretch(x, n_out, src_per_out=1.0, win_len=256, hop=64, base=None, out=None, pos=None):
     """Time-domain overlap-add at a time ratio (pg_ola_stretch): x (n_in,) or (n_sig, n_in) float32 on the device, samples
     contiguous, the row stride free -> (..., n_out).  Output frame g, ``win_len`` samples of a periodic Hann window around output
     sample g * hop, is the input around sample rint(g * hop * src_per_out) (src_per_out = 1 / stretch), weighted, and every output
     sample is the weighted sum over the frames that cover it divided by the sum of their weights: the frames are moved, not
     stretched, so a click stays a click.  src_per_out == 1.0 returns x to a few ulps.  ``base`` (shaped like the result, rows free):
-    added to the result in the same launch.  The window table is built once per (device, win_len)."""
+    added to the result in the same launch.  The window table is built once per (device, win_len).  ``pos`` (pg_ola_stretch_map): a
+    float64 device tensor of ``ola_grains(n_out, win_len, hop)`` source centres in samples, one per grain, in place of the line
+    g * hop * src_per_out (a NaN centre is outside the signal)."""
     who = "ola_stretch"
     x2 = _ola_rows(x, "x", who)
     n_sig, n_in = x2.shape
@@ -1134,19 +1254,30 @@ def ola_stretch(x, n_out, src_per_out=1.0, win_len=256, hop=64, base=None, out=N
         raise ValueError(f"{who}: hop must be within 1 .. win_len / 2 = {win_len // 2}, got {hop}")
     want = (n_out,) if x.dim() == 1 else (n_sig, n_out)
     a = _lib.OlaStretchArgs()
+    if pos is not None:
+        a = _lib.OlaStretchMapArgs()
+        a.pos = _pos_table(pos, ola_grains(n_out, win_len, hop), who, src_per_out, "ola_grains(n_out, win_len, hop)")
+        _int32_sizes(who, n_in=n_in, n_out=n_out, x_stride=x2.stride(0) if n_sig > 1 else 0)
     if base is not None:
         if not torch.is_tensor(base) or tuple(base.shape) != want:
             raise ValueError(f"{who}: base must be shaped like the result, {want}")
         b2 = _ola_rows(base, "base", who)
+        if pos is not None:
+            _int32_sizes(who, base_stride=b2.stride(0) if n_sig > 1 else 0)
         a.base, a.base_stride = b2.data_ptr(), (b2.stride(0) if n_sig > 1 else n_out)
     out = _out(out, want, x.device, who, rows=True)
     o2 = out[None] if out.dim() == 1 else out
     if n_sig > 1 and o2.stride(0) < n_out:
         raise ValueError(f"{who}: rows of out overlap (strides {out.stride()})")
-    a.n_sig, a.win_len, a.hop, a.n_in, a.n_out, a.src_per_out = n_sig, win_len, hop, n_in, n_out, src_per_out
+    a.n_sig, a.win_len, a.hop, a.n_in, a.n_out = n_sig, win_len, hop, n_in, n_out
     a.x, a.x_stride = x2.data_ptr(), (x2.stride(0) if n_sig > 1 else n_in)
     a.win = _ola_window(win_len, x.device).data_ptr()
     a.y, a.y_stride = o2.data_ptr(), (o2.stride(0) if n_sig > 1 else n_out)
+    if pos is not None:
+        _int32_sizes(who, y_stride=o2.stride(0) if n_sig > 1 else 0)
+        _lib.check(_lib.load().pg_ola_stretch_map(C.byref(a), _stream()), "ola_stretch_map")
+        return out
+    a.src_per_out = src_per_out
     _lib.check(_lib.load().pg_ola_stretch(C.byref(a), _stream()), who)
     return out
 

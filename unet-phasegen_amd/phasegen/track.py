@@ -44,6 +44,11 @@ option the log-magnitude plane is split by median filtering into a harmonic and 
 harmonic plane goes through the chosen phase source exactly as the whole plane does without the option, the percussive plane is
 inverted on the SOURCE grid with the analysis' own phase and moved to the output grid in the time domain by overlap-add of a short
 window (ops.ola_stretch, ``TRANSIENT_WINDOW`` / ``TRANSIENT_HOP``), which relocates transients instead of stretching them.
+
+``stretch`` may be a ``TimeMap`` wherever it may be a number: a tempo map, a time-varying stretch given by anchors (source seconds,
+output seconds) and piecewise linear between them.  ``TimeMap.plan`` is ``spectral_plan`` for it and holds one source position per
+output frame (and one source centre per overlap-add grain); the tables go to the device once per call and every stretch kernel
+reads them instead of the one rate (``pos=`` of ops.spec_clips, phase_vocoder, phase_lock, phase_lock_linked, ola_stretch).
 """
 import collections
 import fractions
@@ -82,7 +87,7 @@ GL_INITS = ("noise", "spsi")
 
 class _Analysis:
     """What every phase source shares: the track at ``sr`` (a2: (channels, a_len)), the clip plan and the clips' [log1p|z| ; angle]."""
-    __slots__ = ("a2", "mono", "n_ch", "a_len", "T", "step", "n_clips", "bins", "pol", "plan", "stretch", "link")
+    __slots__ = ("a2", "mono", "n_ch", "a_len", "T", "step", "n_clips", "bins", "pol", "plan", "stretch", "link", "pos", "grains")
 
 
 def _load(audio, osr, sr, res_type):
@@ -98,6 +103,7 @@ def _load(audio, osr, sr, res_type):
     an = _Analysis()
     an.mono = a.dim() == 1
     an.link = False
+    an.pos = an.grains = None
     an.a2 = (a[None] if an.mono else a).contiguous()
     an.n_ch, an.a_len = an.a2.shape
     return an
@@ -191,6 +197,133 @@ def spectral_plan(a_len, frames, hop_length, overlap_frames, stretch=1.0):
     return SpectralPlan(sf, Vf, a_out, n_clips, F_out, F_src, hop_length * (F_src - 1))
 
 
+MappedPlan = collections.namedtuple("MappedPlan", SpectralPlan._fields + ("pos", "grains"))
+
+
+class TimeMap:
+    """A tempo map: a time-varying stretch, piecewise linear between anchors (host only, float64).  ``anchors``: a sequence of
+    (source_seconds, output_seconds) that begins with (0, 0), has at least two entries, is finite and strictly increasing in both
+    columns; every segment's stretch (output per source) must lie within [0.25, 4], the domain of a uniform stretch.  Past the last
+    anchor the last segment's line continues, so ``TimeMap([(0, 0), (1, R)])`` is the uniform stretch R.  ValueError otherwise.
+    ``stretch=`` takes one wherever it takes a number (``reconstruct_track``, ``evaluate_stretch``)."""
+
+    def __init__(self, anchors):
+        try:
+            a = np.array([[float(v) for v in row] for row in anchors], dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"TimeMap: anchors must be (source_seconds, output_seconds) pairs ({e})")
+        if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 2:
+            raise ValueError("TimeMap: at least two anchors (source_seconds, output_seconds)")
+        if not np.isfinite(a).all():
+            raise ValueError("TimeMap: anchors must be finite")
+        if a[0, 0] != 0.0 or a[0, 1] != 0.0:
+            raise ValueError(f"TimeMap: the first anchor must be (0, 0), got ({a[0, 0]}, {a[0, 1]})")
+        d = np.diff(a, axis=0)
+        if not (d > 0.0).all():
+            raise ValueError("TimeMap: anchors must increase strictly in both columns")
+        slopes = d[:, 1] / d[:, 0]
+        if not ((slopes >= 0.25) & (slopes <= 4.0)).all():
+            raise ValueError(f"TimeMap: every segment's stretch must lie within [0.25, 4], got {slopes.min():g} .. {slopes.max():g}")
+        self.src, self.out = a[:, 0].copy(), a[:, 1].copy()
+        self.src.setflags(write=False)
+        self.out.setflags(write=False)
+
+    @property
+    def anchors(self):
+        return [(float(s), float(o)) for s, o in zip(self.src, self.out)]
+
+    @property
+    def stretches(self):
+        """every segment's stretch, output seconds per source second"""
+        return np.diff(self.out) / np.diff(self.src)
+
+    def __repr__(self):
+        return f"TimeMap({self.anchors!r})"
+
+    @staticmethod
+    def _eval(x, xs, ys):
+        """y on the segment of x: y_k + (x - x_k) * ((y_{k+1} - y_k) / (x_{k+1} - x_k)): one division per segment, so every anchor
+        is hit exactly; from the last anchor on, k is the last anchor and the slope the last segment's"""
+        x = np.asarray(x, np.float64)
+        k = np.clip(np.searchsorted(xs, x, side="right") - 1, 0, len(xs) - 1)
+        slope = (ys[1:] - ys[:-1]) / (xs[1:] - xs[:-1])
+        y = ys[k] + (x - xs[k]) * slope[np.minimum(k, len(xs) - 2)]
+        return float(y) if y.ndim == 0 else y
+
+    def src_of_out(self, t, sr=16000):
+        """the source position, in samples at ``sr``, that plays at output sample ``t`` (a number or an array)"""
+        return self._eval(t, self.out * float(sr), self.src * float(sr))
+
+    def out_of_src(self, s, sr=16000):
+        """the output position, in samples at ``sr``, at which source sample ``s`` plays"""
+        return self._eval(s, self.src * float(sr), self.out * float(sr))
+
+    @classmethod
+    def ramp(cls, duration_s, r0, r1, n=64):
+        """A stretch that goes linearly from ``r0`` to ``r1`` over ``duration_s`` seconds of source: ``n`` equal segments, each at
+        the stretch of its midpoint (past the end the last one continues)."""
+        duration_s, r0, r1, n = float(duration_s), float(r0), float(r1), int(n)
+        if not (duration_s > 0.0 and duration_s < math.inf) or n < 1:
+            raise ValueError(f"TimeMap.ramp: duration_s {duration_s} must be positive and finite and n {n} at least 1")
+        if not (0.25 <= r0 <= 4.0 and 0.25 <= r1 <= 4.0):
+            raise ValueError(f"TimeMap.ramp: r0 {r0} and r1 {r1} must lie within [0.25, 4]")
+        src = duration_s * (np.arange(n + 1, dtype=np.float64) / n)
+        r = r0 + (r1 - r0) * ((np.arange(n, dtype=np.float64) + 0.5) / n)
+        out = np.concatenate([[0.0], np.cumsum(np.diff(src) * r)])
+        return cls(list(zip(src, out)))
+
+    @classmethod
+    def load(cls, path):
+        """A text file of two columns per line, source seconds and output seconds, separated by blanks or a comma; ``#`` begins a
+        comment; empty lines are skipped."""
+        anchors = []
+        with open(path) as f:
+            for n, line in enumerate(f, 1):
+                cols = line.split("#", 1)[0].replace(",", " ").split()
+                if not cols:
+                    continue
+                if len(cols) != 2:
+                    raise ValueError(f"TimeMap.load: {path}:{n}: expected two columns, got {len(cols)}")
+                try:
+                    anchors.append((float(cols[0]), float(cols[1])))
+                except ValueError:
+                    raise ValueError(f"TimeMap.load: {path}:{n}: not two numbers: {line.strip()!r}")
+        return cls(anchors)
+
+    def save(self, path):
+        with open(path, "w") as f:
+            f.write("# source_seconds output_seconds\n")
+            for s, o in zip(self.src, self.out):
+                f.write(f"{float(s)!r} {float(o)!r}\n")
+
+    def plan(self, a_len, frames, hop_length, overlap_frames, sr=16000):
+        """``spectral_plan`` for this map (host only): a ``MappedPlan`` with ``spectral_plan``'s fields and two position tables,
+          a_out = round(out_of_src(a_len));  n_clips, F_out: ``track_plan(a_out, ...)``'s, as for a uniform stretch
+          pos[g] = src_of_out(g * hop) / hop         the source-frame position of output frame g (float64, F_out entries)
+          F_src = floor(max(pos)) + 2;  n_src = hop * (F_src - 1)
+          grains[g] = src_of_out(g * TRANSIENT_HOP)  the source centre, in samples, of every grain of ``transients="ola"``
+        so ``TimeMap([(0, 0), (1, R)])`` with a dyadic R gives ``spectral_plan(stretch=R)`` and pos == arange * (1 / R) exactly."""
+        a_len, frames, hop_length, overlap_frames = int(a_len), int(frames), int(hop_length), int(overlap_frames)
+        if a_len < 1:
+            raise ValueError(f"TimeMap.plan: a_len {a_len} must be positive")
+        a_out = int(round(self.out_of_src(a_len, sr)))
+        _T, _step, n_clips = track_plan(a_out, frames, hop_length, overlap_frames)
+        sf, Vf = frames - 1 - overlap_frames, overlap_frames + 1
+        if 2 * Vf > frames:
+            raise ValueError(f"TimeMap.plan: overlap_frames {overlap_frames} + 1 shared frames exceed half a clip of {frames} frames")
+        F_out = (n_clips - 1) * sf + frames
+        pos = self.src_of_out(np.arange(F_out, dtype=np.float64) * hop_length, sr) / hop_length
+        F_src = int(math.floor(pos.max())) + 2
+        grains = self.src_of_out(np.arange(ops.ola_grains(hop_length * (F_out - 1), TRANSIENT_WINDOW, TRANSIENT_HOP), dtype=np.float64)
+                                 * TRANSIENT_HOP, sr)
+        return MappedPlan(sf, Vf, a_out, n_clips, F_out, F_src, hop_length * (F_src - 1), pos, grains)
+
+
+def _grid(an):
+    """how a kernel is told the time grid of this analysis: the keyword of ops.spec_clips / phase_vocoder / phase_lock(_linked)"""
+    return {"src_per_out": 1.0 / an.stretch} if an.pos is None else {"pos": an.pos}
+
+
 def _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch, link=False):
     """resample -> ONE whole-track STFT per channel -> standardise -> polar: an.pol (n_ch, 2, bins, F_src) on the global frame grid.
     ``link``: one more row is analysed, the channel mean (the reference of ops.phase_lock_linked), standardised with the SAME
@@ -201,10 +334,17 @@ def _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, o
     n_ch, a_len = an.n_ch, an.a_len
     a2 = torch.cat([an.a2, an.a2.mean(0, keepdim=True)]) if an.link else an.a2      # (rows, a_len); one channel: the mean is the channel
     rows = a2.shape[0]
-    an.stretch = float(stretch)
-    an.plan = pl = spectral_plan(a_len, frames, hop_length, overlap_frames, stretch)
-    an.n_clips, an.bins = pl.n_clips, n_fft // 2
     dev = a2.device
+    if isinstance(stretch, TimeMap):
+        # a tempo map: the plan's two position tables go to the device once, and every kernel below reads them (``_grid``)
+        an.stretch = stretch
+        an.plan = pl = stretch.plan(a_len, frames, hop_length, overlap_frames, sr)
+        an.pos, an.grains = torch.from_numpy(pl.pos).to(dev), torch.from_numpy(pl.grains).to(dev)
+    else:
+        an.stretch = float(stretch)
+        an.plan = pl = spectral_plan(a_len, frames, hop_length, overlap_frames, stretch)
+        an.pos = an.grains = None
+    an.n_clips, an.bins = pl.n_clips, n_fft // 2
     with torch.cuda.device(dev), torch.no_grad():
         if stats is not None:
             # channel c is the region [c a_len, (c + 1) a_len) of the flat buffer; the crop is zero past its end (pg_stft_crops)
@@ -250,7 +390,7 @@ def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_bel
     envelope moved by that many semitones (ONE ops.formant_shift call), so the split, every phase source, the ISTFT magnitudes and
     ``mag`` see the corrected plane."""
     pl, n_ch, bins = an.plan, an.n_ch, an.bins
-    spo = 1.0 / an.stretch
+    grid = _grid(an)
     pol = an.pol[:n_ch]                                                                       # (linked: row n_ch is the channel mean)
     plane = an.pol[:, 0]
     if formant_semitones != 0.0:
@@ -262,7 +402,7 @@ def _invert_spectral(an, model, phase, hop_length, frames, clip_batch, reset_bel
         harm, perc = ops.hpss(plane, *HPSS_WIN)
         mag, audio = _invert_plane(an, model, phase, hop_length, frames, clip_batch, reset_below, pol, harm[:n_ch], harm[n_ch:])
         audio = _add_transients(an, hop_length, pol, perc[:n_ch], audio)                      # ("ola": the one way there is)
-        return ops.spec_clips(plane[:n_ch], 1, pl.F_out, pl.F_out, spo)[0], audio
+        return ops.spec_clips(plane[:n_ch], 1, pl.F_out, pl.F_out, **grid)[0], audio
     return _invert_plane(an, model, phase, hop_length, frames, clip_batch, reset_below, pol, plane[:n_ch], plane[n_ch:])
 
 
@@ -270,6 +410,8 @@ def _add_transients(an, hop_length, pol, perc, audio):
     """The percussive plane (n_ch, bins, F_src) under the analysis' own phase, inverted on the source grid and moved onto the output
     grid by overlap-add of a short window, added to the harmonic ``audio`` (n_ch, hop * (F_out - 1)) in the same launch."""
     p_audio = ops.istft(perc, pol[:, 1], hop_length, mode=0, normalize=False)                 # (n_ch, hop * (F_src - 1))
+    if an.grains is not None:                                                                 # (a tempo map: one source centre per grain)
+        return ops.ola_stretch(p_audio, audio.shape[1], 1.0, TRANSIENT_WINDOW, TRANSIENT_HOP, base=audio, pos=an.grains)
     return ops.ola_stretch(p_audio, audio.shape[1], 1.0 / an.stretch, TRANSIENT_WINDOW, TRANSIENT_HOP, base=audio)
 
 
@@ -277,30 +419,30 @@ def _invert_plane(an, model, phase, hop_length, frames, clip_batch, reset_below,
     """``_invert_spectral`` for one log-magnitude plane ``logmag`` (n_ch, bins, F_src) -- the analysis' own, read in place, or its
     harmonic part -- and, linked, the plane of the channel mean ``ref_logmag`` (1, bins, F_src)."""
     pl, n_ch, bins = an.plan, an.n_ch, an.bins
-    spo = 1.0 / an.stretch
+    grid = _grid(an)
     if phase == "zero":
         ph = torch.zeros(n_ch, bins, pl.F_out, device=logmag.device)                          # (the join of zeros is zero)
     elif phase == "original":
-        ph = ops.phase_join(ops.spec_clips(pol[:, 1], pl.n_clips, frames, pl.sf, spo), pl.sf)
+        ph = ops.phase_join(ops.spec_clips(pol[:, 1], pl.n_clips, frames, pl.sf, **grid), pl.sf)
     elif phase == "vocoder":
         # the analysis' own phase, propagated along the output grid by its measured advance (no model, no clips)
-        ph = ops.phase_vocoder(pol[:, 1], pl.F_out, spo, logmag=logmag,
-                               reset_below=VOCODER_RESET_BELOW if reset_below is None else reset_below)
+        ph = ops.phase_vocoder(pol[:, 1], pl.F_out, logmag=logmag,
+                               reset_below=VOCODER_RESET_BELOW if reset_below is None else reset_below, **grid)
     elif phase == "vocoder_locked":
         # ... with identity phase locking: only the peaks of a frame advance, every other bin takes its peak's rotation
         # (linked: ONE rotation for all channels, the channel mean's, so the analysis' inter-channel phase differences survive)
         floor = VOCODER_RESET_BELOW if reset_below is None else reset_below
         if an.link:
-            ph = ops.phase_lock_linked(pol[:, 1], an.pol[n_ch, 1], ref_logmag[0], pl.F_out, spo, reset_below=floor)
+            ph = ops.phase_lock_linked(pol[:, 1], an.pol[n_ch, 1], ref_logmag[0], pl.F_out, reset_below=floor, **grid)
         else:
-            ph = ops.phase_lock(pol[:, 1], pl.F_out, spo, logmag=logmag, reset_below=floor)
+            ph = ops.phase_lock(pol[:, 1], pl.F_out, logmag=logmag, reset_below=floor, **grid)
     elif phase == "spsi":
         # from the magnitudes on the output grid alone: they come first, and nothing of the analysis' phase is read
-        mag = ops.spec_clips(logmag, 1, pl.F_out, pl.F_out, spo)[0]
+        mag = ops.spec_clips(logmag, 1, pl.F_out, pl.F_out, **grid)[0]
         ph = ops.phase_spsi(mag, 2 * bins, hop_length)
         return mag, ops.istft(mag, ph, hop_length, mode=0, normalize=False)
     else:
-        x = ops.spec_clips(logmag, pl.n_clips, frames, pl.sf, spo).view(pl.n_clips * n_ch, bins, frames)   # (clip, channel) order
+        x = ops.spec_clips(logmag, pl.n_clips, frames, pl.sf, **grid).view(pl.n_clips * n_ch, bins, frames)   # (clip, channel) order
         n_sig = x.shape[0]
         if n_sig <= clip_batch:       # one forward: the phase half of its (n_sig, 2 bins, frames) output is joined in place
             phi = model.forward(x, per_clip=True).view(pl.n_clips, n_ch, 2 * bins, frames)[:, :, :bins]
@@ -311,7 +453,7 @@ def _invert_plane(an, model, phase, hop_length, frames, clip_batch, reset_below,
                 flat[i:i + clip_batch] = model.forward(x[i:i + clip_batch], per_clip=True)[:, :bins]
         ph = ops.phase_join(phi, pl.sf)
     # the magnitudes on the output grid: the plane itself, cut (or time-resampled) to F_out frames by the same kernel
-    mag = ops.spec_clips(logmag, 1, pl.F_out, pl.F_out, spo)[0]
+    mag = ops.spec_clips(logmag, 1, pl.F_out, pl.F_out, **grid)[0]
     return mag, ops.istft(mag, ph, hop_length, mode=0, normalize=False)                       # (n_ch, hop * (F_out - 1))
 
 
@@ -336,6 +478,13 @@ def _synthesise_spectral(an, model, phase, hop_length, frames, clip_batch, norma
 def _check_join(who, join, stretch, phase_list):
     if join not in JOINS:
         raise ValueError(f"{who}: join must be 'waveform' or 'spectral', got {join!r}")
+    if isinstance(stretch, TimeMap):                             # a tempo map is a stretch other than 1, whatever its slopes
+        if join != "spectral":
+            raise ValueError(f"{who}: a TimeMap needs join='spectral'")
+        for p in phase_list:
+            if p not in STRETCH_PHASES:
+                raise ValueError(f"{who}: a TimeMap needs phase 'unet', 'vocoder', 'vocoder_locked', 'spsi' or 'zero', got {p!r} (the analysis' own phase does not fit a resampled spectrogram)")
+        return stretch
     stretch = float(stretch)
     if stretch != 1.0 and join != "spectral":
         raise ValueError(f"{who}: stretch {stretch} needs join='spectral'")
@@ -451,7 +600,8 @@ def reconstruct_track(model, audio, n_fft=2048, hop_length=512, frames=128, over
     ``join="waveform"`` inverts every clip and crossfades the waveforms (ops.stitch); ``join="spectral"`` joins the clips' PHASES on
     the track's frame grid (ops.phase_join: one phase per frame, the circular mean where two clips overlap) and inverts the whole
     track once with its exact magnitudes.  ``stretch=1.0`` (spectral join, phase "unet", "vocoder" or "zero"): the magnitudes are
-    resampled along time and the result has round(a_len * stretch) samples per channel at the same pitch.  phase="vocoder" (spectral
+    resampled along time and the result has round(a_len * stretch) samples per channel at the same pitch; a ``TimeMap`` in place of
+    the number stretches every part of the track at its own rate (round(out_of_src(a_len)) samples).  phase="vocoder" (spectral
     join only, ``model`` may be None) is the phase vocoder: the analysis' own phase, propagated along the output frames by its
     measured advance (ops.phase_vocoder, floor ``VOCODER_RESET_BELOW``) -- the standard comparator of a time stretch.
     phase="vocoder_locked" (the same conditions) is that vocoder with identity phase locking (ops.phase_lock): only the spectral peaks
@@ -551,7 +701,9 @@ def _evaluate_stretch(model, audio, stretch, n_fft, hop_length, frames, overlap_
     transients = _check_transients("evaluate_stretch", transients, "spectral")
     formant_semitones = _check_formants("evaluate_stretch", formant_semitones, "spectral")
     an = _analyse_spectral(audio, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, stretch, link)
-    res = {"n_samples": int(an.a_len), "n_out": int(an.plan.a_out), "sr": int(sr), "stretch": stretch, "n_clips": int(an.n_clips),
+    # (under a TimeMap "stretch" is the mean one, n_out / n_samples: the report keeps its keys and stays a plain JSON object)
+    res = {"n_samples": int(an.a_len), "n_out": int(an.plan.a_out), "sr": int(sr),
+           "stretch": an.plan.a_out / an.a_len if an.pos is not None else stretch, "n_clips": int(an.n_clips),
            "reset_below": reset_below, "metrics": {}}
     if link:
         res["link_channels"], res["mid_metrics"] = True, {}
@@ -563,7 +715,7 @@ def _evaluate_stretch(model, audio, stretch, n_fft, hop_length, frames, overlap_
         res["audio"] = {}
     with torch.cuda.device(an.a2.device), torch.no_grad():
         if link:        # the mid signal's imposed magnitudes: the mean row's plane, resampled as the channels' are
-            mid_mag = ops.spec_clips(an.pol[an.n_ch:, 0], 1, an.plan.F_out, an.plan.F_out, 1.0 / an.stretch)[0]
+            mid_mag = ops.spec_clips(an.pol[an.n_ch:, 0], 1, an.plan.F_out, an.plan.F_out, **_grid(an))[0]
         for p in phases:
             mag, full = _invert_spectral(an, model, p, hop_length, frames, clip_batch, reset_below, transients, formant_semitones)
             out = _trim_spectral(an, full, False)
@@ -625,6 +777,8 @@ def pitch_shift(model, audio, semitones, n_fft=2048, hop_length=512, frames=128,
     -> float32 device tensor shaped like the input at ``sr``."""
     if formants not in FORMANTS:
         raise ValueError(f"pitch_shift: formants must be None or 'keep', got {formants!r}")
+    if isinstance(semitones, TimeMap):
+        raise ValueError("pitch_shift: a TimeMap is not a pitch (a pitch curve would need a variable-rate resampler, which is not built)")
     stretch, ratio = pitch_ratio(semitones)
     _check_link("pitch_shift", link_channels, "spectral", (phase,))
     _check_transients("pitch_shift", transients, "spectral")

@@ -45,6 +45,11 @@ stretched with the chosen phase and the percussive part is moved in the time dom
 (``phasegen.ops.formant_shift``) and moved against the shift before the resampling moves it along with the partials, so a voice
 shifted up does not turn into a smaller voice.  ``--formant_shift SEMITONES`` moves the envelope alone, at the same pitch and tempo
 (implies the spectral join; not with ``--pitch``, ``--formants`` or ``--report``).
+
+``--tempo_map FILE`` (instead of ``--stretch``; not with ``--pitch``) stretches every part of the track at its own rate: the file
+holds two columns per line, source seconds and output seconds (``#`` begins a comment), the map is piecewise linear between these
+anchors and every segment's stretch must lie within [0.25, 4] (``phasegen.track.TimeMap``).  It implies what ``--stretch`` implies
+and works with ``--phase``, ``--link_channels``, ``--transients``, ``--formant_shift`` and ``--stretch_report``.
 """
 import argparse
 import json
@@ -86,6 +91,9 @@ def main():
                              "on the track's frame grid and invert once with the exact magnitudes")
     parser.add_argument("--stretch", default=None, type=float, metavar="R",
                         help="play R times as long at the same pitch, 0.25 <= R <= 4 (implies --join spectral)")
+    parser.add_argument("--tempo_map", default=None, metavar="FILE",
+                        help="a time-varying stretch: a text file of two columns per line, source seconds and output seconds, piecewise "
+                             "linear between them (phasegen.track.TimeMap; instead of --stretch, implies --join spectral)")
     parser.add_argument("--pitch", default=None, type=float, metavar="SEMITONES",
                         help="shift the pitch at the same tempo, within +-24 semitones (implies --join spectral)")
     parser.add_argument("--phase", choices=["unet", "vocoder", "vocoder_locked", "spsi", "zero"], default="unet",
@@ -107,6 +115,9 @@ def main():
         parser.error("the following arguments are required: --weight")
     if args.stretch is not None and args.pitch is not None:
         parser.error("--stretch and --pitch exclude each other")
+    if args.tempo_map is not None and (args.stretch is not None or args.pitch is not None):
+        parser.error("--tempo_map is a stretch of its own: it excludes --stretch and --pitch")
+    stretched = args.stretch is not None or args.tempo_map is not None
     if args.formants is not None and args.pitch is None:
         parser.error("--formants needs --pitch")
     if args.formant_shift is not None and (args.pitch is not None or args.formants is not None):
@@ -118,7 +129,7 @@ def main():
     if args.formant_shift is not None and args.report is not None:
         parser.error("--report compares against the input: it does not work with --formant_shift")
     formant_shift = 0.0 if args.formant_shift is None else args.formant_shift
-    modified = (args.stretch is not None and args.stretch != 1.0) or args.pitch is not None
+    modified = (args.stretch is not None and args.stretch != 1.0) or args.pitch is not None or args.tempo_map is not None
     if modified and args.join == "waveform":
         parser.error("--stretch and --pitch need --join spectral")
     if modified and args.report is not None:
@@ -129,19 +140,19 @@ def main():
         parser.error("--report measures the model's phase: it needs --phase unet")
     if args.link_channels and args.phase != "vocoder_locked":
         parser.error("--link_channels needs --phase vocoder_locked")
-    if args.transients is not None and args.stretch is None and args.pitch is None:
+    if args.transients is not None and not stretched and args.pitch is None:
         parser.error("--transients needs --stretch or --pitch")
     if args.transients is not None and args.report is not None:
         parser.error("--report compares against the input: it does not work with --transients")
     if args.transients is not None and args.join == "waveform":
         parser.error("--transients needs --join spectral")
-    if args.stretch_report is not None and args.stretch is None:
+    if args.stretch_report is not None and not stretched:
         parser.error("--stretch_report needs --stretch")
     if args.stretch_report is not None and args.pitch is not None:
         parser.error("--stretch_report measures the stretched track on the analysed frame grid: it does not work with --pitch")
     if args.stretch_report is not None and args.report is not None:
         parser.error("--report and --stretch_report exclude each other")
-    join = ("spectral" if (modified or args.stretch is not None or args.formant_shift is not None or args.phase in GRID_PHASES) and args.join is None
+    join = ("spectral" if (modified or stretched or args.formant_shift is not None or args.phase in GRID_PHASES) and args.join is None
             else (args.join or "waveform"))
     if args.stretch_report is not None and join != "spectral":
         parser.error("--stretch_report needs --join spectral")
@@ -168,6 +179,9 @@ def main():
     else:
         print("reconstruct: no --stats given, normalising with this track's own mean and std", file=sys.stderr)
     audio, file_sr = preproc.load_audio(args.input, mono=not args.stereo)
+    stretch = 1.0 if args.stretch is None else args.stretch
+    if args.tempo_map is not None:
+        stretch = track.TimeMap.load(args.tempo_map)
 
     phases = [p.strip() for p in args.report_phases.split(",") if p.strip()]
     if args.report is not None:
@@ -189,12 +203,12 @@ def main():
     elif args.stretch_report is not None:
         # (the locked vocoder and spsi are reported when they are asked for; the other modes' reports stay as they were)
         others = [p for p in track.STRETCH_PHASES if p not in (args.phase, "vocoder_locked", "spsi") and (p != "unet" or model is not None)]
-        stretch_report = track.evaluate_stretch(model, audio, args.stretch, phases=[args.phase] + others, return_audio=True,
+        stretch_report = track.evaluate_stretch(model, audio, stretch, phases=[args.phase] + others, return_audio=True,
                                                 link_channels=args.link_channels, transients=args.transients,
                                                 formant_semitones=formant_shift, **kw)
         out = track.peak_normalize(stretch_report.pop("audio")[args.phase])
     elif args.report is None:
-        out = track.reconstruct_track(model, audio, phase=args.phase, join=join, stretch=1.0 if args.stretch is None else args.stretch,
+        out = track.reconstruct_track(model, audio, phase=args.phase, join=join, stretch=stretch,
                                       link_channels=args.link_channels, transients=args.transients, formant_semitones=formant_shift, **kw)
     else:
         report = track.evaluate_track(model, audio, phases=phases, gl_iters=args.gl_iters, return_audio=True, join=join, gl_init=args.gl_init, **kw)
