@@ -52,12 +52,12 @@ def _args(_lib):
 
 
 def test_argument_errors_are_reported_before_any_launch():
-    """The table pg_phase_lock shares with pg_phase_vocoder (tests/_stretch_args.py), run through both: same codes, same words;
+    """The table pg_phase_lock shares with pg_phase_vocoder, pg_phase_lock_linked and the mapped twins (tests/_stretch_args.py), run through all six: same codes, same words;
     then what is pg_phase_lock's own."""
     from phasegen import _lib
     lib = _lib.load()
     f = lib.pg_phase_lock
-    shared.run_both(_lib)
+    shared.run_all(_lib)
     a = _args(_lib)                                                                 # M is required here: the one documented difference
     a.M = None
     assert f(ctypes.byref(a), None) == _lib.ERR_NULL and b"required" in lib.pg_last_error_string()

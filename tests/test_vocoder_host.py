@@ -52,11 +52,11 @@ def _args(_lib):
 
 
 def test_argument_errors_are_reported_before_any_launch():
-    """The table pg_phase_vocoder shares with pg_phase_lock (tests/_stretch_args.py: null fields, non-positive sizes, the bad
-    src_per_out and reset_below, short strides, misaligned pointers, the 2^62 overflow), run through both: same codes, same words."""
+    """The table pg_phase_vocoder shares with pg_phase_lock, pg_phase_lock_linked and the mapped twins of all three (tests/_stretch_args.py: null fields, non-positive sizes, the bad
+    src_per_out and reset_below, short strides, misaligned pointers, the 2^62 overflow), run through all six: same codes, same words."""
     from phasegen import _lib
     lib = _lib.load()
-    shared.run_both(_lib)
+    shared.run_all(_lib)
     a = _args(_lib)                                                                 # without M its stride is not looked at
     a.M, a.m_stride, a.n_ch, a.bins, a.F_out = None, 0, 1 << 30, 1 << 30, 1 << 62
     a.a_stride = (1 << 30) * 19

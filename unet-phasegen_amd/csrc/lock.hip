@@ -20,7 +20,9 @@
 // pg_phase_lock_map and pg_phase_lock_linked_map are the two above on pg_track.h's MappedGrid: the positions of the output frames
 // come from a table, pc(pos[g]), and need not grow with g.  Only LkArgs and the two loaders (lk_load, lk_fetch) know the grid: the
 // frame sources carry it as a type, LockSrc<Grid> / LinkSrc<Grid>, and the scan below is the same code for both (tests/_map_ref.py;
-// DESIGN.md section 4.19).
+// DESIGN.md section 4.19).  On the host the four are ONE function, lk_stretch: pg_track.h reads each ABI struct into a PgStretchCall
+// and checks it (the checker pg_phase_vocoder and its twin go through), the workspace rows are lk_workspace_check's -- pg_phase_spsi's
+// too -- and the entry points only name their struct's reader, their grid and their frame sources.
 //
 // The recurrence (q(), angle(), i0(g), i1(g) and the advance into frame g are pg_track.h's, shared with vocoder.hip).  Per channel,
 // T_g[b] (uint32, a fraction of a turn) is the rotation of bin b at output frame g against its analysis
@@ -525,13 +527,24 @@ hipError_t lk_run(LkArgs& k, int n_scan, int n_ch, int threads, bool wide, hipSt
     return lk_launch(lock_apply_kernel<Src, BPT, false>, (long)n_ch * k.n_chunks, threads, lds_apply, st, k);
 }
 
-// shapes the workspace depends on -> bytes, or a negative error code
-int64_t lk_workspace_bytes(const char* op, int n_ch, int bins, int64_t F_out) {
+// shapes the workspace depends on -> bytes, or a negative error code.  linked: one channel's worth whatever n_ch -- the scan is the
+// reference's alone (n_ch still has to be positive, and the apply grid's (channel, chunk) pairs to fit).
+int64_t lk_workspace_bytes(const char* op, int64_t n_ch, int64_t bins, int64_t F_out, bool linked = false) {
     if (n_ch <= 0 || bins <= 0 || F_out <= 0) return pg_failf(PG_ERR_SHAPE, "%s: non-positive dimension", op);
     if (bins > LK_MAX_BINS) return pg_failf(PG_ERR_SHAPE, "%s: more than %d bins", op, LK_MAX_BINS);
     const int64_t n_chunks = (F_out - 1) / LK_CHUNK + 1;
     if (n_chunks > (int64_t)0x7fffffff / n_ch) return pg_failf(PG_ERR_SHAPE, "%s: more than 2^31 - 1 (channel, chunk) pairs", op);
-    return (int64_t)n_ch * n_chunks * 3 * bins * 4;            // < 2^31 * 3 * 2^12 * 4
+    return (linked ? 1 : n_ch) * n_chunks * 3 * bins * 4;      // < 2^31 * 3 * 2^12 * 4
+}
+
+// The workspace rows of every entry point, after its own checks: alignment, then the size the query pg_workspace_bytes_<op>() states
+// (which may refuse the shapes), then presence and size.
+int lk_workspace_check(const char* op, int64_t n_ch, int64_t bins, int64_t F_out, bool linked, const void* workspace, int64_t workspace_bytes) {
+    if (((uintptr_t)workspace) & 3) return pg_failf(PG_ERR_ALIGN, "%s: misaligned pointer", op);
+    const int64_t need = lk_workspace_bytes(op, n_ch, bins, F_out, linked);
+    if (need < 0) return (int)need;
+    if (!workspace || workspace_bytes < need) return pg_failf(PG_ERR_WORKSPACE, "%s: workspace missing or smaller than pg_workspace_bytes_%s()", op, op);
+    return PG_OK;
 }
 
 // the three launches for the sources Scan (compose, carry: n_scan channels) and Src (apply: n_ch); k holds everything but the plan
@@ -552,6 +565,23 @@ int lk_scan(const char* op, LkArgs& k, int n_scan, int n_ch, int64_t F_out, void
     return e == hipSuccess ? PG_OK : pg_failf((int)e, "%s launch failed", op);
 }
 
+// pg_phase_lock and pg_phase_lock_linked on either grid (Scan, Src: as in lk_scan): the checked call (pg_track.h), the workspace of
+// `a`, the scan.  A linked call scans the reference's planes once, as one channel (strides 0), and hands the channels' own planes to
+// apply as X.
+template <typename Scan, typename Src, typename Args>
+int lk_stretch(const char* op, const PgStretchCall& c, const Args* a, void* stream) {
+    LkArgs k;
+    bool wide;
+    if (int e = pg_stretch_check(op, LK_MAX_BINS, c, k, wide)) return e;
+    if (int e = lk_workspace_check(op, c.n_ch, c.bins, c.F_out, Src::LINKED, a->workspace, a->workspace_bytes)) return e;
+    k.bin0 = 0; k.hop_per_fft = 0.0; k.X = nullptr; k.x_stride = 0;
+    if (Src::LINKED) {
+        k.X = k.A; k.x_stride = k.a_stride;
+        k.A = c.Aref; k.M = c.Mref; k.a_stride = 0;
+    }
+    return lk_scan<Scan, Src>(op, k, Src::LINKED ? 1 : (int)c.n_ch, (int)c.n_ch, c.F_out, a->workspace, wide, stream);
+}
+
 }  // namespace
 
 extern "C" int64_t pg_workspace_bytes_phase_lock(const pg_phase_lock_args* a) {
@@ -560,15 +590,7 @@ extern "C" int64_t pg_workspace_bytes_phase_lock(const pg_phase_lock_args* a) {
 }
 
 extern "C" int pg_phase_lock(const pg_phase_lock_args* a, void* stream) {
-    LkArgs k;
-    bool wide;
-    if (int e = pg_stretch_check("phase_lock", true, LK_MAX_BINS, a, k, wide)) return e;
-    if (((uintptr_t)a->workspace) & 3) return pg_fail(PG_ERR_ALIGN, "phase_lock: misaligned pointer");
-    const int64_t need = lk_workspace_bytes("phase_lock", a->n_ch, a->bins, a->F_out);
-    if (need < 0) return (int)need;
-    if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_lock: workspace missing or smaller than pg_workspace_bytes_phase_lock()");
-    k.bin0 = 0; k.hop_per_fft = 0.0; k.X = nullptr; k.x_stride = 0;
-    return lk_scan<LockSrc<tk::UniformGrid>, LockSrc<tk::UniformGrid>>("phase_lock", k, a->n_ch, a->n_ch, a->F_out, a->workspace, wide, stream);
+    return lk_stretch<LockSrc<tk::UniformGrid>, LockSrc<tk::UniformGrid>>("phase_lock", pg_stretch_uniform<PG_M_REQUIRED>(a), a, stream);
 }
 
 // pg_phase_lock over the positions of a table: the same three launches on LockSrc<tk::MappedGrid>, the same workspace
@@ -578,83 +600,25 @@ extern "C" int64_t pg_workspace_bytes_phase_lock_map(const pg_phase_lock_map_arg
 }
 
 extern "C" int pg_phase_lock_map(const pg_phase_lock_map_args* a, void* stream) {
-    LkArgs k;
-    bool wide;
-    if (int e = pg_stretch_map_check("phase_lock_map", true, LK_MAX_BINS, a, k, wide)) return e;
-    if (((uintptr_t)a->workspace) & 3) return pg_fail(PG_ERR_ALIGN, "phase_lock_map: misaligned pointer");
-    const int64_t need = lk_workspace_bytes("phase_lock_map", a->n_ch, a->bins, a->F_out);
-    if (need < 0) return (int)need;
-    if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_lock_map: workspace missing or smaller than pg_workspace_bytes_phase_lock_map()");
-    k.bin0 = 0; k.hop_per_fft = 0.0; k.X = nullptr; k.x_stride = 0;
-    return lk_scan<LockSrc<tk::MappedGrid>, LockSrc<tk::MappedGrid>>("phase_lock_map", k, a->n_ch, a->n_ch, a->F_out, a->workspace, wide, stream);
-}
-
-// one channel's worth whatever n_ch: the scan is the reference's alone
-static int64_t lk_linked_workspace_bytes(int n_ch, int bins, int64_t F_out, const char* op = "phase_lock_linked") {
-    const int64_t all = lk_workspace_bytes(op, n_ch, bins, F_out);                    // (n_ch > 0, and the apply grid's (channel, chunk) pairs)
-    return all < 0 ? all : all / n_ch;
+    return lk_stretch<LockSrc<tk::MappedGrid>, LockSrc<tk::MappedGrid>>("phase_lock_map", pg_stretch_mapped<PG_M_REQUIRED>(a), a, stream);
 }
 
 extern "C" int64_t pg_workspace_bytes_phase_lock_linked(const pg_phase_lock_linked_args* a) {
     if (!a) return pg_fail(PG_ERR_NULL, "phase_lock_linked: args required");
-    return lk_linked_workspace_bytes(a->n_ch, a->bins, a->F_out);
+    return lk_workspace_bytes("phase_lock_linked", a->n_ch, a->bins, a->F_out, true);
 }
 
-// (the checks in the order of pg_stretch_check and pg_phase_lock: NULL, shapes, alignment, then the workspace)
 extern "C" int pg_phase_lock_linked(const pg_phase_lock_linked_args* a, void* stream) {
-    if (!a || !a->A || !a->Aref || !a->Mref || !a->out) return pg_fail(PG_ERR_NULL, "phase_lock_linked: args, A, Aref, Mref and out required");
-    if (a->n_ch <= 0 || a->bins <= 0 || a->F_src <= 0 || a->F_out <= 0) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: non-positive dimension");
-    if (a->bins > LK_MAX_BINS) return pg_failf(PG_ERR_SHAPE, "phase_lock_linked: more than %d bins", LK_MAX_BINS);
-    if (!(a->src_per_out > 0.0) || !(a->src_per_out <= DBL_MAX)) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: src_per_out must be finite and positive");
-    if (!(a->reset_below >= 0.0f) || !pg_finite(a->reset_below)) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: reset_below must be finite and not negative");
-    if (a->F_src > INT64_MAX / 2 / a->bins) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: plane beyond 2^62 elements");
-    if (a->a_stride < (int64_t)a->bins * a->F_src) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: a_stride shorter than a plane");
-    if ((int64_t)a->n_ch * a->bins > INT64_MAX / 2 / a->F_out) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked: output beyond 2^62 elements");
-    if ((((uintptr_t)a->A) & 3) || (((uintptr_t)a->Aref) & 3) || (((uintptr_t)a->Mref) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->workspace) & 3))
-        return pg_fail(PG_ERR_ALIGN, "phase_lock_linked: misaligned pointer");
-    const int64_t need = lk_linked_workspace_bytes(a->n_ch, a->bins, a->F_out);
-    if (need < 0) return (int)need;
-    if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_lock_linked: workspace missing or smaller than pg_workspace_bytes_phase_lock_linked()");
-    LkArgs k;
-    k.A = a->Aref; k.M = a->Mref; k.out = a->out;           // the scan's planes, shared by every channel: strides 0
-    k.X = a->A; k.x_stride = a->n_ch == 1 ? 0 : a->a_stride;
-    k.src_per_out = a->src_per_out; k.pos = nullptr;
-    k.a_stride = 0; k.m_stride = 0;
-    k.F_src = a->F_src; k.F_out = a->F_out;
-    k.bins = a->bins; k.reset_below = a->reset_below;
-    k.bin0 = 0; k.hop_per_fft = 0.0;
-    const bool wide = (a->F_out & 3) == 0 && pg_al16(a->out);
-    return lk_scan<LockSrc<tk::UniformGrid>, LinkSrc<tk::UniformGrid>>("phase_lock_linked", k, 1, a->n_ch, a->F_out, a->workspace, wide, stream);
+    return lk_stretch<LockSrc<tk::UniformGrid>, LinkSrc<tk::UniformGrid>>("phase_lock_linked", pg_stretch_uniform<PG_REFERENCE>(a), a, stream);
 }
 
 extern "C" int64_t pg_workspace_bytes_phase_lock_linked_map(const pg_phase_lock_linked_map_args* a) {
     if (!a) return pg_fail(PG_ERR_NULL, "phase_lock_linked_map: args required");
-    return lk_linked_workspace_bytes(a->n_ch, a->bins, a->F_out, "phase_lock_linked_map");
+    return lk_workspace_bytes("phase_lock_linked_map", a->n_ch, a->bins, a->F_out, true);
 }
 
-// (pg_phase_lock_linked's checks in its order, without the src_per_out row and the rows no int32 size can reach, with `pos`)
 extern "C" int pg_phase_lock_linked_map(const pg_phase_lock_linked_map_args* a, void* stream) {
-    if (!a || !a->A || !a->Aref || !a->Mref || !a->out || !a->pos) return pg_fail(PG_ERR_NULL, "phase_lock_linked_map: args, A, Aref, Mref, out and pos required");
-    if (a->n_ch <= 0 || a->bins <= 0 || a->F_src <= 0 || a->F_out <= 0) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked_map: non-positive dimension");
-    if (a->bins > LK_MAX_BINS) return pg_failf(PG_ERR_SHAPE, "phase_lock_linked_map: more than %d bins", LK_MAX_BINS);
-    if (!(a->reset_below >= 0.0f) || !pg_finite(a->reset_below)) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked_map: reset_below must be finite and not negative");
-    if (a->a_ch_rows < a->bins) return pg_fail(PG_ERR_SHAPE, "phase_lock_linked_map: a_ch_rows shorter than a plane");
-    if ((((uintptr_t)a->A) & 3) || (((uintptr_t)a->Aref) & 3) || (((uintptr_t)a->Mref) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->workspace) & 3)
-        || (((uintptr_t)a->pos) & 7))
-        return pg_fail(PG_ERR_ALIGN, "phase_lock_linked_map: misaligned pointer");
-    const int64_t need = lk_linked_workspace_bytes(a->n_ch, a->bins, a->F_out, "phase_lock_linked_map");
-    if (need < 0) return (int)need;
-    if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_lock_linked_map: workspace missing or smaller than pg_workspace_bytes_phase_lock_linked_map()");
-    LkArgs k;
-    k.A = a->Aref; k.M = a->Mref; k.out = a->out;           // the scan's planes, shared by every channel: strides 0
-    k.X = a->A; k.x_stride = a->n_ch == 1 ? 0 : (long)a->a_ch_rows * a->F_src;
-    k.src_per_out = 0.0; k.pos = a->pos;
-    k.a_stride = 0; k.m_stride = 0;
-    k.F_src = a->F_src; k.F_out = a->F_out;
-    k.bins = a->bins; k.reset_below = a->reset_below;
-    k.bin0 = 0; k.hop_per_fft = 0.0;
-    const bool wide = (a->F_out & 3) == 0 && pg_al16(a->out);
-    return lk_scan<LockSrc<tk::MappedGrid>, LinkSrc<tk::MappedGrid>>("phase_lock_linked_map", k, 1, a->n_ch, a->F_out, a->workspace, wide, stream);
+    return lk_stretch<LockSrc<tk::MappedGrid>, LinkSrc<tk::MappedGrid>>("phase_lock_linked_map", pg_stretch_mapped<PG_REFERENCE>(a), a, stream);
 }
 
 extern "C" int64_t pg_workspace_bytes_phase_spsi(const pg_phase_spsi_args* a) {
@@ -672,10 +636,8 @@ extern "C" int pg_phase_spsi(const pg_phase_spsi_args* a, void* stream) {
     if (a->F > INT64_MAX / 2 / a->bins) return pg_fail(PG_ERR_SHAPE, "phase_spsi: plane beyond 2^62 elements");
     if (a->m_stride < (int64_t)a->bins * a->F) return pg_fail(PG_ERR_SHAPE, "phase_spsi: m_stride shorter than a plane");
     if ((int64_t)a->n_ch * a->bins > INT64_MAX / 2 / a->F) return pg_fail(PG_ERR_SHAPE, "phase_spsi: output beyond 2^62 elements");
-    if ((((uintptr_t)a->M) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->workspace) & 3)) return pg_fail(PG_ERR_ALIGN, "phase_spsi: misaligned pointer");
-    const int64_t need = lk_workspace_bytes("phase_spsi", a->n_ch, a->bins, a->F);
-    if (need < 0) return (int)need;
-    if (!a->workspace || a->workspace_bytes < need) return pg_fail(PG_ERR_WORKSPACE, "phase_spsi: workspace missing or smaller than pg_workspace_bytes_phase_spsi()");
+    if ((((uintptr_t)a->M) & 3) || (((uintptr_t)a->out) & 3)) return pg_fail(PG_ERR_ALIGN, "phase_spsi: misaligned pointer");
+    if (int e = lk_workspace_check("phase_spsi", a->n_ch, a->bins, a->F, false, a->workspace, a->workspace_bytes)) return e;
     LkArgs k;
     k.A = nullptr; k.M = a->M; k.out = a->out;
     k.src_per_out = 1.0; k.pos = nullptr;                    // the identity grid: frame g of `out` is column g of M

@@ -123,50 +123,76 @@ inline unsigned pg_stream_grid(long units, int threads) {
     return (unsigned)(grid > cap ? cap : grid);
 }
 
-// The host checks of a stretched-plane call (pg_phase_vocoder_args, or pg_phase_lock_args, which begins with the same fields), in
-// the order that decides which error a doubly-bad call reports, and the kernel arguments both take: k.A .. k.reset_below, with the
-// stride of a single channel 0.  `op` prefixes every message; need_M: M may not be NULL; max_bins: the op's own limit.  wide: `out`
-// takes 16-byte stores.
-template <typename Args, typename KernelArgs>
-int pg_stretch_check(const char* op, bool need_M, int max_bins, const Args* a, KernelArgs& k, bool& wide) {
-    if (!a || !a->A || (need_M && !a->M) || !a->out) return pg_failf(PG_ERR_NULL, "%s: args, A%s and out required", op, need_M ? ", M" : "");
-    if (a->n_ch <= 0 || a->bins <= 0 || a->F_src <= 0 || a->F_out <= 0) return pg_failf(PG_ERR_SHAPE, "%s: non-positive dimension", op);
-    if (a->bins > max_bins) return pg_failf(PG_ERR_SHAPE, "%s: more than %d bins", op, max_bins);
-    if (!(a->src_per_out > 0.0) || !(a->src_per_out <= DBL_MAX)) return pg_failf(PG_ERR_SHAPE, "%s: src_per_out must be finite and positive", op);
-    if (!(a->reset_below >= 0.0f) || !pg_finite(a->reset_below)) return pg_failf(PG_ERR_SHAPE, "%s: reset_below must be finite and not negative", op);
-    if (a->F_src > INT64_MAX / 2 / a->bins) return pg_failf(PG_ERR_SHAPE, "%s: plane beyond 2^62 elements", op);
-    if (a->a_stride < (int64_t)a->bins * a->F_src) return pg_failf(PG_ERR_SHAPE, "%s: a_stride shorter than a plane", op);
-    if (a->M && a->m_stride < (int64_t)a->bins * a->F_src) return pg_failf(PG_ERR_SHAPE, "%s: m_stride shorter than a plane", op);
-    if ((int64_t)a->n_ch * a->bins > INT64_MAX / 2 / a->F_out) return pg_failf(PG_ERR_SHAPE, "%s: output beyond 2^62 elements", op);
-    if ((((uintptr_t)a->A) & 3) || (((uintptr_t)a->M) & 3) || (((uintptr_t)a->out) & 3)) return pg_failf(PG_ERR_ALIGN, "%s: misaligned pointer", op);
-    wide = (a->F_out & 3) == 0 && pg_al16(a->out);
-    k.A = a->A; k.M = a->M; k.out = a->out;
-    k.src_per_out = a->src_per_out;
-    k.a_stride = a->n_ch == 1 ? 0 : a->a_stride; k.m_stride = a->n_ch == 1 ? 0 : a->m_stride;
-    k.F_src = a->F_src; k.F_out = a->F_out;
-    k.bins = a->bins; k.reset_below = a->reset_below;
-    k.pos = nullptr;
-    return PG_OK;
+// ---- The host side of a stretched-plane call: pg_phase_vocoder, pg_phase_lock, pg_phase_lock_linked and their *_map twins.  Six ABI
+// structs, ONE description of the call and ONE list of checks.  A reader (pg_stretch_uniform / pg_stretch_mapped) turns a struct
+// into a PgStretchCall: the sizes as int64, the channel strides in elements (a mapped struct's count of rows times F_src), the
+// grid (src_per_out, or the table `pos`) and the names a message has to quote.  A NULL struct reads as a call without planes, so
+// the NULL row answers for it.
+enum PgStretchPlanes { PG_M_OPTIONAL, PG_M_REQUIRED, PG_REFERENCE };   // vocoder: M may be NULL; lock: M; linked: (Aref, Mref), no M
+struct PgStretchCall {
+    PgStretchPlanes planes;
+    bool mapped;                                             // the grid: `pos` (8-byte aligned, required), else src_per_out
+    double src_per_out; const double* pos;
+    int64_t n_ch, bins, F_src, F_out, a_stride, m_stride;
+    const char *a_name, *m_name;                             // the strides as the struct names them: a_stride or a_ch_rows
+    float reset_below;
+    const float *A, *M, *Aref, *Mref; float* out;
+};
+
+template <PgStretchPlanes P, typename Args>
+void pg_stretch_planes(PgStretchCall& c, const Args* a) {   // the fields every one of the six names alike
+    c.n_ch = a->n_ch; c.bins = a->bins; c.F_src = a->F_src; c.F_out = a->F_out; c.reset_below = a->reset_below;
+    c.A = a->A; c.out = a->out;
+    if constexpr (P == PG_REFERENCE) { c.Aref = a->Aref; c.Mref = a->Mref; } else c.M = a->M;
 }
 
-// The same for the mapped twins (pg_phase_vocoder_map_args, or pg_phase_lock_map_args, which begins with the same fields): the rows
-// of pg_stretch_check in its order, without the src_per_out row, with `pos` in the NULL row and its 8-byte alignment in the ALIGN
-// row.  Every size is an int32 and a channel stride is a count of rows, so no plane reaches 2^62 elements and those rows are gone.
-template <typename Args, typename KernelArgs>
-int pg_stretch_map_check(const char* op, bool need_M, int max_bins, const Args* a, KernelArgs& k, bool& wide) {
-    if (!a || !a->A || (need_M && !a->M) || !a->out || !a->pos) return pg_failf(PG_ERR_NULL, "%s: args, A%s, out and pos required", op, need_M ? ", M" : "");
-    if (a->n_ch <= 0 || a->bins <= 0 || a->F_src <= 0 || a->F_out <= 0) return pg_failf(PG_ERR_SHAPE, "%s: non-positive dimension", op);
-    if (a->bins > max_bins) return pg_failf(PG_ERR_SHAPE, "%s: more than %d bins", op, max_bins);
-    if (!(a->reset_below >= 0.0f) || !pg_finite(a->reset_below)) return pg_failf(PG_ERR_SHAPE, "%s: reset_below must be finite and not negative", op);
-    if (a->a_ch_rows < a->bins) return pg_failf(PG_ERR_SHAPE, "%s: a_ch_rows shorter than a plane", op);
-    if (a->M && a->m_ch_rows < a->bins) return pg_failf(PG_ERR_SHAPE, "%s: m_ch_rows shorter than a plane", op);
-    if ((((uintptr_t)a->A) & 3) || (((uintptr_t)a->M) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->pos) & 7))
+template <PgStretchPlanes P, typename Args>
+PgStretchCall pg_stretch_uniform(const Args* a) {
+    PgStretchCall c = {};
+    c.planes = P; c.a_name = "a_stride"; c.m_name = "m_stride";
+    if (!a) return c;
+    pg_stretch_planes<P>(c, a);
+    c.src_per_out = a->src_per_out; c.a_stride = a->a_stride;
+    if constexpr (P != PG_REFERENCE) c.m_stride = a->m_stride;
+    return c;
+}
+
+template <PgStretchPlanes P, typename Args>
+PgStretchCall pg_stretch_mapped(const Args* a) {
+    PgStretchCall c = {};
+    c.planes = P; c.mapped = true; c.a_name = "a_ch_rows"; c.m_name = "m_ch_rows";
+    if (!a) return c;
+    pg_stretch_planes<P>(c, a);
+    c.pos = a->pos; c.a_stride = (int64_t)a->a_ch_rows * a->F_src;
+    if constexpr (P != PG_REFERENCE) c.m_stride = (int64_t)a->m_ch_rows * a->F_src;
+    return c;
+}
+
+// The checks, each row once, in the order that decides which error a doubly-bad call reports -- NULL, shapes, ranges, strides, 2^62,
+// alignment -- and the kernel arguments every such kernel takes: k.A .. k.reset_below and the grid, with the stride of a single
+// channel 0.  `op` prefixes every message; max_bins: the op's own limit.  A mapped call has no src_per_out row, and `pos` in the
+// NULL and the ALIGN row; its sizes are int32, so the 2^62 rows cannot answer for it.  wide: `out` takes 16-byte stores.
+template <typename KernelArgs>
+int pg_stretch_check(const char* op, int max_bins, const PgStretchCall& c, KernelArgs& k, bool& wide) {
+    const bool planes = c.A && (c.planes != PG_M_REQUIRED || c.M) && (c.planes != PG_REFERENCE || (c.Aref && c.Mref));
+    if (!planes || !c.out || (c.mapped && !c.pos))
+        return pg_failf(PG_ERR_NULL, "%s: args, A%s%s required", op, c.planes == PG_M_REQUIRED ? ", M" : c.planes == PG_REFERENCE ? ", Aref, Mref" : "",
+                        c.mapped ? ", out and pos" : " and out");
+    if (c.n_ch <= 0 || c.bins <= 0 || c.F_src <= 0 || c.F_out <= 0) return pg_failf(PG_ERR_SHAPE, "%s: non-positive dimension", op);
+    if (c.bins > max_bins) return pg_failf(PG_ERR_SHAPE, "%s: more than %d bins", op, max_bins);
+    if (!c.mapped && (!(c.src_per_out > 0.0) || !(c.src_per_out <= DBL_MAX))) return pg_failf(PG_ERR_SHAPE, "%s: src_per_out must be finite and positive", op);
+    if (!(c.reset_below >= 0.0f) || !pg_finite(c.reset_below)) return pg_failf(PG_ERR_SHAPE, "%s: reset_below must be finite and not negative", op);
+    if (c.F_src > INT64_MAX / 2 / c.bins) return pg_failf(PG_ERR_SHAPE, "%s: plane beyond 2^62 elements", op);
+    if (c.a_stride < c.bins * c.F_src) return pg_failf(PG_ERR_SHAPE, "%s: %s shorter than a plane", op, c.a_name);
+    if (c.M && c.m_stride < c.bins * c.F_src) return pg_failf(PG_ERR_SHAPE, "%s: %s shorter than a plane", op, c.m_name);
+    if (c.n_ch * c.bins > INT64_MAX / 2 / c.F_out) return pg_failf(PG_ERR_SHAPE, "%s: output beyond 2^62 elements", op);
+    if (((uintptr_t)c.A | (uintptr_t)c.M | (uintptr_t)c.Aref | (uintptr_t)c.Mref | (uintptr_t)c.out) & 3 || ((uintptr_t)c.pos) & 7)
         return pg_failf(PG_ERR_ALIGN, "%s: misaligned pointer", op);
-    wide = (a->F_out & 3) == 0 && pg_al16(a->out);
-    k.A = a->A; k.M = a->M; k.out = a->out;
-    k.src_per_out = 0.0; k.pos = a->pos;
-    k.a_stride = a->n_ch == 1 ? 0 : (long)a->a_ch_rows * a->F_src; k.m_stride = a->n_ch == 1 ? 0 : (long)a->m_ch_rows * a->F_src;
-    k.F_src = a->F_src; k.F_out = a->F_out;
-    k.bins = a->bins; k.reset_below = a->reset_below;
+    wide = (c.F_out & 3) == 0 && pg_al16(c.out);
+    k.A = c.A; k.M = c.M; k.out = c.out;
+    k.src_per_out = c.src_per_out; k.pos = c.pos;
+    k.a_stride = c.n_ch == 1 ? 0 : c.a_stride; k.m_stride = c.n_ch == 1 ? 0 : c.m_stride;
+    k.F_src = c.F_src; k.F_out = c.F_out;
+    k.bins = (int)c.bins; k.reset_below = c.reset_below;
     return PG_OK;
 }

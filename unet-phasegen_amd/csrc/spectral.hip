@@ -117,49 +117,57 @@ __global__ __launch_bounds__(SP_THREADS) void phase_join_kernel(const PjKernelAr
     }
 }
 
+// What the two ABI structs of pg_spec_clips say differently: the grid, and the channel stride (in elements) under its own name.
+struct ScGrid { double src_per_out; const double* pos; int64_t p_stride; const char* p_name; };
+ScGrid sc_grid(const pg_spec_clips_args& a) { return ScGrid{a.src_per_out, nullptr, a.p_stride, "p_stride"}; }
+ScGrid sc_grid(const pg_spec_clips_map_args& a) { return ScGrid{0.0, a.pos, (int64_t)a.p_ch_rows * a.F_src, "p_ch_rows"}; }
+
+// The checks of pg_spec_clips and pg_spec_clips_map, each row once, and the kernel's arguments.  MAPPED: no src_per_out row, `pos` in
+// the NULL and the ALIGN row (8 bytes), and never the 16-byte path, which is rate 1's.
+template <bool MAPPED, typename Args>
+int sc_plan(const char* op, const Args* a, ScKernelArgs& k, bool& wide) {
+    if (!a || !a->P || !a->out || (MAPPED && !sc_grid(*a).pos)) return pg_failf(PG_ERR_NULL, "%s: args, P%s required", op, MAPPED ? ", out and pos" : " and out");
+    const ScGrid g = sc_grid(*a);
+    if (a->n_clips <= 0 || a->n_ch <= 0 || a->bins <= 0 || a->frames <= 0 || a->F_src <= 0) return pg_failf(PG_ERR_SHAPE, "%s: non-positive dimension", op);
+    if (a->sf < 1) return pg_failf(PG_ERR_SHAPE, "%s: sf must be at least 1", op);
+    if (!MAPPED && (!(g.src_per_out > 0.0) || !(g.src_per_out <= 1.7976931348623157e308))) return pg_failf(PG_ERR_SHAPE, "%s: src_per_out must be finite and positive", op);
+    if (g.p_stride < (int64_t)a->bins * a->F_src) return pg_failf(PG_ERR_SHAPE, "%s: %s shorter than a plane", op, g.p_name);
+    const int64_t rows = (int64_t)a->n_clips * a->n_ch * a->bins;
+    if (rows > INT64_MAX / 2 / a->frames) return pg_failf(PG_ERR_SHAPE, "%s: output beyond 2^62 elements", op);
+    if ((((uintptr_t)a->P) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)g.pos) & 7)) return pg_failf(PG_ERR_ALIGN, "%s: misaligned pointer", op);
+    // (a stride that is never applied -- one channel -- does not decide)
+    wide = !MAPPED && g.src_per_out == 1.0 && (a->sf & 3) == 0 && (a->frames & 3) == 0 && (a->F_src & 3) == 0
+           && (a->n_ch == 1 || (g.p_stride & 3) == 0) && pg_al16(a->P) && pg_al16(a->out);
+    k.P = a->P; k.out = a->out; k.src_per_out = g.src_per_out; k.pos = g.pos;
+    k.p_stride = a->n_ch == 1 ? 0 : g.p_stride; k.F_src = a->F_src; k.sf = a->sf;
+    k.units_per_row = ((long)a->frames + 3) / 4; k.units = k.units_per_row * rows;
+    k.n_ch = a->n_ch; k.bins = a->bins; k.frames = a->frames;
+    return PG_OK;
+}
+
+template <typename Kernel>
+int sc_launch(const char* op, Kernel kernel, const ScKernelArgs& k, void* stream) {
+    hipLaunchKernelGGL(kernel, dim3(pg_stream_grid(k.units, SP_THREADS)), dim3(SP_THREADS), 0, (hipStream_t)stream, k);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? PG_OK : pg_failf((int)e, "%s launch failed", op);
+}
+
 }  // namespace
 
 extern "C" int pg_spec_clips(const pg_spec_clips_args* a, void* stream) {
-    if (!a || !a->P || !a->out) return pg_fail(PG_ERR_NULL, "spec_clips: args, P and out required");
-    if (a->n_clips <= 0 || a->n_ch <= 0 || a->bins <= 0 || a->frames <= 0 || a->F_src <= 0) return pg_fail(PG_ERR_SHAPE, "spec_clips: non-positive dimension");
-    if (a->sf < 1) return pg_fail(PG_ERR_SHAPE, "spec_clips: sf must be at least 1");
-    if (!(a->src_per_out > 0.0) || !(a->src_per_out <= 1.7976931348623157e308)) return pg_fail(PG_ERR_SHAPE, "spec_clips: src_per_out must be finite and positive");
-    if (a->p_stride < (int64_t)a->bins * a->F_src) return pg_fail(PG_ERR_SHAPE, "spec_clips: p_stride shorter than a plane");
-    const int64_t rows = (int64_t)a->n_clips * a->n_ch * a->bins;
-    if (rows > INT64_MAX / 2 / a->frames) return pg_fail(PG_ERR_SHAPE, "spec_clips: output beyond 2^62 elements");
-    if ((((uintptr_t)a->P) & 3) || (((uintptr_t)a->out) & 3)) return pg_fail(PG_ERR_ALIGN, "spec_clips: misaligned pointer");
-    // (a stride that is never applied -- one channel -- does not decide)
-    const bool wide = a->src_per_out == 1.0 && (a->sf & 3) == 0 && (a->frames & 3) == 0 && (a->F_src & 3) == 0
-                      && (a->n_ch == 1 || (a->p_stride & 3) == 0) && pg_al16(a->P) && pg_al16(a->out);
     ScKernelArgs k;
-    k.P = a->P; k.out = a->out; k.src_per_out = a->src_per_out; k.pos = nullptr;
-    k.p_stride = a->n_ch == 1 ? 0 : a->p_stride; k.F_src = a->F_src; k.sf = a->sf;
-    k.units_per_row = ((long)a->frames + 3) / 4; k.units = k.units_per_row * rows;
-    k.n_ch = a->n_ch; k.bins = a->bins; k.frames = a->frames;
-    const unsigned grid = pg_stream_grid(k.units, SP_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (wide) hipLaunchKernelGGL((spec_clips_kernel<tk::UniformGrid, true>), dim3(grid), dim3(SP_THREADS), 0, st, k);
-    else hipLaunchKernelGGL((spec_clips_kernel<tk::UniformGrid, false>), dim3(grid), dim3(SP_THREADS), 0, st, k);
-    return pg_launch_ok("spec_clips launch failed");
+    bool wide;
+    if (int e = sc_plan<false>("spec_clips", a, k, wide)) return e;
+    if (wide) return sc_launch("spec_clips", spec_clips_kernel<tk::UniformGrid, true>, k, stream);
+    return sc_launch("spec_clips", spec_clips_kernel<tk::UniformGrid, false>, k, stream);
 }
 
-// pg_spec_clips over the positions of a table (tk::MappedGrid): the frame-by-frame path alone -- the 16-byte path is rate 1's
+// pg_spec_clips over the positions of a table (tk::MappedGrid): the frame-by-frame path alone
 extern "C" int pg_spec_clips_map(const pg_spec_clips_map_args* a, void* stream) {
-    if (!a || !a->P || !a->out || !a->pos) return pg_fail(PG_ERR_NULL, "spec_clips_map: args, P, out and pos required");
-    if (a->n_clips <= 0 || a->n_ch <= 0 || a->bins <= 0 || a->frames <= 0 || a->F_src <= 0) return pg_fail(PG_ERR_SHAPE, "spec_clips_map: non-positive dimension");
-    if (a->sf < 1) return pg_fail(PG_ERR_SHAPE, "spec_clips_map: sf must be at least 1");
-    if (a->p_ch_rows < a->bins) return pg_fail(PG_ERR_SHAPE, "spec_clips_map: p_ch_rows shorter than a plane");
-    const int64_t rows = (int64_t)a->n_clips * a->n_ch * a->bins;
-    if (rows > INT64_MAX / 2 / a->frames) return pg_fail(PG_ERR_SHAPE, "spec_clips_map: output beyond 2^62 elements");
-    if ((((uintptr_t)a->P) & 3) || (((uintptr_t)a->out) & 3) || (((uintptr_t)a->pos) & 7)) return pg_fail(PG_ERR_ALIGN, "spec_clips_map: misaligned pointer");
     ScKernelArgs k;
-    k.P = a->P; k.out = a->out; k.src_per_out = 0.0; k.pos = a->pos;
-    k.p_stride = a->n_ch == 1 ? 0 : (long)a->p_ch_rows * a->F_src; k.F_src = a->F_src; k.sf = a->sf;
-    k.units_per_row = ((long)a->frames + 3) / 4; k.units = k.units_per_row * rows;
-    k.n_ch = a->n_ch; k.bins = a->bins; k.frames = a->frames;
-    const unsigned grid = pg_stream_grid(k.units, SP_THREADS);
-    hipLaunchKernelGGL((spec_clips_kernel<tk::MappedGrid, false>), dim3(grid), dim3(SP_THREADS), 0, (hipStream_t)stream, k);
-    return pg_launch_ok("spec_clips_map launch failed");
+    bool wide;
+    if (int e = sc_plan<true>("spec_clips_map", a, k, wide)) return e;
+    return sc_launch("spec_clips_map", spec_clips_kernel<tk::MappedGrid, false>, k, stream);
 }
 
 extern "C" int pg_phase_join(const pg_phase_join_args* a, void* stream) {

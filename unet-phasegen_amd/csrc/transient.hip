@@ -274,6 +274,45 @@ __global__ __launch_bounds__(OL_THREADS) void ola_stretch_kernel(const OlKernelA
 
 bool ol_window_ok(int32_t w) { return w >= 2 && w <= OL_MAX_WIN && (w & 1) == 0; }
 
+// What the two ABI structs of pg_ola_stretch say differently: the grid (every other field has one name; the sizes and strides are
+// int64 in the one and int32 in the other).
+struct OlGrid { double src_per_out; const double* pos; };
+OlGrid ol_grid(const pg_ola_stretch_args& a) { return OlGrid{a.src_per_out, nullptr}; }
+OlGrid ol_grid(const pg_ola_stretch_map_args& a) { return OlGrid{0.0, a.pos}; }
+
+// The checks of pg_ola_stretch and pg_ola_stretch_map, each row once, the kernel's arguments and the launch on Grid.  MAPPED: no
+// src_per_out row, `pos` in the NULL and the ALIGN row (8 bytes); no int32 size reaches the 2^62 row.
+template <typename Grid, bool MAPPED, typename Args>
+int ol_plan(const char* op, const Args* a, void* stream) {
+    if (!a || !a->x || !a->win || !a->y || (MAPPED && !ol_grid(*a).pos)) return pg_failf(PG_ERR_NULL, "%s: args, x, win%s required", op, MAPPED ? ", y and pos" : " and y");
+    const OlGrid g = ol_grid(*a);
+    if (a->n_sig <= 0 || a->n_in <= 0 || a->n_out <= 0) return pg_failf(PG_ERR_SHAPE, "%s: non-positive dimension", op);
+    if (!ol_window_ok(a->win_len)) return pg_failf(PG_ERR_SHAPE, "%s: win_len must be even and within 2 .. %d", op, OL_MAX_WIN);
+    if (a->hop < 1 || a->hop > a->win_len / 2) return pg_failf(PG_ERR_SHAPE, "%s: need 1 <= hop <= win_len / 2", op);
+    if (!MAPPED && (!(g.src_per_out > 0.0) || !(g.src_per_out <= DBL_MAX))) return pg_failf(PG_ERR_SHAPE, "%s: src_per_out must be finite and positive", op);
+    if (a->n_in > INT64_MAX / 2 || a->n_out > INT64_MAX / 2 / a->n_sig) return pg_failf(PG_ERR_SHAPE, "%s: signals beyond 2^62 elements", op);
+    if (a->x_stride < a->n_in) return pg_failf(PG_ERR_SHAPE, "%s: x_stride shorter than a row", op);
+    if (a->y_stride < a->n_out) return pg_failf(PG_ERR_SHAPE, "%s: y_stride shorter than a row", op);
+    if (a->base && a->base_stride < a->n_out) return pg_failf(PG_ERR_SHAPE, "%s: base_stride shorter than a row", op);
+    if ((((uintptr_t)a->x) & 3) || (((uintptr_t)a->win) & 3) || (((uintptr_t)a->base) & 3) || (((uintptr_t)a->y) & 3) || (((uintptr_t)g.pos) & 7))
+        return pg_failf(PG_ERR_ALIGN, "%s: misaligned pointer", op);
+    OlKernelArgs k;
+    k.x = a->x; k.win = a->win; k.base = a->base; k.y = a->y;
+    k.src_per_out = g.src_per_out; k.pos = g.pos;
+    const bool one = a->n_sig == 1;                                   // (a stride that is never applied does not decide)
+    k.x_stride = one ? 0 : a->x_stride; k.base_stride = one ? 0 : a->base_stride; k.y_stride = one ? 0 : a->y_stride;
+    k.n_in = a->n_in; k.n_out = a->n_out;
+    k.units_per_row = ((long)a->n_out + 3) / 4; k.units = k.units_per_row * a->n_sig;
+    k.w = a->win_len; k.hop = a->hop;
+    const bool wide = pg_al16(a->y) && (one || (a->y_stride & 3) == 0);
+    const unsigned grid = pg_stream_grid(k.units, OL_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (wide) hipLaunchKernelGGL((ola_stretch_kernel<Grid, true>), dim3(grid), dim3(OL_THREADS), 0, st, k);
+    else hipLaunchKernelGGL((ola_stretch_kernel<Grid, false>), dim3(grid), dim3(OL_THREADS), 0, st, k);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? PG_OK : pg_failf((int)e, "%s launch failed", op);
+}
+
 }  // namespace
 
 extern "C" int pg_hpss(const pg_hpss_args* a, void* stream) {
@@ -307,57 +346,7 @@ extern "C" int pg_ola_window(float* win_host, int32_t win_len) {
     return PG_OK;
 }
 
-extern "C" int pg_ola_stretch(const pg_ola_stretch_args* a, void* stream) {
-    if (!a || !a->x || !a->win || !a->y) return pg_fail(PG_ERR_NULL, "ola_stretch: args, x, win and y required");
-    if (a->n_sig <= 0 || a->n_in <= 0 || a->n_out <= 0) return pg_fail(PG_ERR_SHAPE, "ola_stretch: non-positive dimension");
-    if (!ol_window_ok(a->win_len)) return pg_failf(PG_ERR_SHAPE, "ola_stretch: win_len must be even and within 2 .. %d", OL_MAX_WIN);
-    if (a->hop < 1 || a->hop > a->win_len / 2) return pg_fail(PG_ERR_SHAPE, "ola_stretch: need 1 <= hop <= win_len / 2");
-    if (!(a->src_per_out > 0.0) || !(a->src_per_out <= DBL_MAX)) return pg_fail(PG_ERR_SHAPE, "ola_stretch: src_per_out must be finite and positive");
-    if (a->n_in > INT64_MAX / 2 || a->n_out > INT64_MAX / 2 / a->n_sig) return pg_fail(PG_ERR_SHAPE, "ola_stretch: signals beyond 2^62 elements");
-    if (a->x_stride < a->n_in) return pg_fail(PG_ERR_SHAPE, "ola_stretch: x_stride shorter than a row");
-    if (a->y_stride < a->n_out) return pg_fail(PG_ERR_SHAPE, "ola_stretch: y_stride shorter than a row");
-    if (a->base && a->base_stride < a->n_out) return pg_fail(PG_ERR_SHAPE, "ola_stretch: base_stride shorter than a row");
-    if ((((uintptr_t)a->x) & 3) || (((uintptr_t)a->win) & 3) || (((uintptr_t)a->base) & 3) || (((uintptr_t)a->y) & 3))
-        return pg_fail(PG_ERR_ALIGN, "ola_stretch: misaligned pointer");
-    OlKernelArgs k;
-    k.x = a->x; k.win = a->win; k.base = a->base; k.y = a->y;
-    k.src_per_out = a->src_per_out; k.pos = nullptr;
-    const bool one = a->n_sig == 1;                                   // (a stride that is never applied does not decide)
-    k.x_stride = one ? 0 : a->x_stride; k.base_stride = one ? 0 : a->base_stride; k.y_stride = one ? 0 : a->y_stride;
-    k.n_in = a->n_in; k.n_out = a->n_out;
-    k.units_per_row = (a->n_out + 3) / 4; k.units = k.units_per_row * a->n_sig;
-    k.w = a->win_len; k.hop = a->hop;
-    const bool wide = pg_al16(a->y) && (one || (a->y_stride & 3) == 0);
-    const unsigned grid = pg_stream_grid(k.units, OL_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (wide) hipLaunchKernelGGL((ola_stretch_kernel<OlUniform, true>), dim3(grid), dim3(OL_THREADS), 0, st, k);
-    else hipLaunchKernelGGL((ola_stretch_kernel<OlUniform, false>), dim3(grid), dim3(OL_THREADS), 0, st, k);
-    return pg_launch_ok("ola_stretch launch failed");
-}
+extern "C" int pg_ola_stretch(const pg_ola_stretch_args* a, void* stream) { return ol_plan<OlUniform, false>("ola_stretch", a, stream); }
 
 // pg_ola_stretch with one source centre per grain (OlMapped)
-extern "C" int pg_ola_stretch_map(const pg_ola_stretch_map_args* a, void* stream) {
-    if (!a || !a->x || !a->win || !a->y || !a->pos) return pg_fail(PG_ERR_NULL, "ola_stretch_map: args, x, win, y and pos required");
-    if (a->n_sig <= 0 || a->n_in <= 0 || a->n_out <= 0) return pg_fail(PG_ERR_SHAPE, "ola_stretch_map: non-positive dimension");
-    if (!ol_window_ok(a->win_len)) return pg_failf(PG_ERR_SHAPE, "ola_stretch_map: win_len must be even and within 2 .. %d", OL_MAX_WIN);
-    if (a->hop < 1 || a->hop > a->win_len / 2) return pg_fail(PG_ERR_SHAPE, "ola_stretch_map: need 1 <= hop <= win_len / 2");
-    if (a->x_stride < a->n_in) return pg_fail(PG_ERR_SHAPE, "ola_stretch_map: x_stride shorter than a row");
-    if (a->y_stride < a->n_out) return pg_fail(PG_ERR_SHAPE, "ola_stretch_map: y_stride shorter than a row");
-    if (a->base && a->base_stride < a->n_out) return pg_fail(PG_ERR_SHAPE, "ola_stretch_map: base_stride shorter than a row");
-    if ((((uintptr_t)a->x) & 3) || (((uintptr_t)a->win) & 3) || (((uintptr_t)a->base) & 3) || (((uintptr_t)a->y) & 3) || (((uintptr_t)a->pos) & 7))
-        return pg_fail(PG_ERR_ALIGN, "ola_stretch_map: misaligned pointer");
-    OlKernelArgs k;
-    k.x = a->x; k.win = a->win; k.base = a->base; k.y = a->y;
-    k.src_per_out = 0.0; k.pos = a->pos;
-    const bool one = a->n_sig == 1;                                   // (a stride that is never applied does not decide)
-    k.x_stride = one ? 0 : a->x_stride; k.base_stride = one ? 0 : a->base_stride; k.y_stride = one ? 0 : a->y_stride;
-    k.n_in = a->n_in; k.n_out = a->n_out;
-    k.units_per_row = ((long)a->n_out + 3) / 4; k.units = k.units_per_row * a->n_sig;
-    k.w = a->win_len; k.hop = a->hop;
-    const bool wide = pg_al16(a->y) && (one || (a->y_stride & 3) == 0);
-    const unsigned grid = pg_stream_grid(k.units, OL_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (wide) hipLaunchKernelGGL((ola_stretch_kernel<OlMapped, true>), dim3(grid), dim3(OL_THREADS), 0, st, k);
-    else hipLaunchKernelGGL((ola_stretch_kernel<OlMapped, false>), dim3(grid), dim3(OL_THREADS), 0, st, k);
-    return pg_launch_ok("ola_stretch_map launch failed");
-}
+extern "C" int pg_ola_stretch_map(const pg_ola_stretch_map_args* a, void* stream) { return ol_plan<OlMapped, true>("ola_stretch_map", a, stream); }

@@ -136,29 +136,28 @@ __global__ __launch_bounds__(PV_THREADS) void phase_vocoder_kernel(const PvKerne
     }
 }
 
+// the checked call (pg_track.h) on the grid it names
 template <typename Grid>
-int pv_launch(PvKernelArgs& k, int n_ch, bool wide, void* stream, const char* failed) {
-    k.rows = (long)n_ch * k.bins;
+int pv_run(const char* op, const PgStretchCall& c, void* stream) {
+    PvKernelArgs k;
+    bool wide;
+    if (int e = pg_stretch_check(op, INT32_MAX, c, k, wide)) return e;
+    k.rows = c.n_ch * c.bins;
     const unsigned grid = pg_stream_grid(k.rows, 1);          // a workgroup per row
     hipStream_t st = (hipStream_t)stream;
     if (wide) hipLaunchKernelGGL((phase_vocoder_kernel<Grid, true>), dim3(grid), dim3(PV_THREADS), 0, st, k);
     else hipLaunchKernelGGL((phase_vocoder_kernel<Grid, false>), dim3(grid), dim3(PV_THREADS), 0, st, k);
-    return pg_launch_ok(failed);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? PG_OK : pg_failf((int)e, "%s launch failed", op);
 }
 
 }  // namespace
 
 extern "C" int pg_phase_vocoder(const pg_phase_vocoder_args* a, void* stream) {
-    PvKernelArgs k;
-    bool wide;
-    if (int e = pg_stretch_check("phase_vocoder", false, INT32_MAX, a, k, wide)) return e;
-    return pv_launch<tk::UniformGrid>(k, a->n_ch, wide, stream, "phase_vocoder launch failed");
+    return pv_run<tk::UniformGrid>("phase_vocoder", pg_stretch_uniform<PG_M_OPTIONAL>(a), stream);
 }
 
 // the same scan over the positions of a table (tk::MappedGrid)
 extern "C" int pg_phase_vocoder_map(const pg_phase_vocoder_map_args* a, void* stream) {
-    PvKernelArgs k;
-    bool wide;
-    if (int e = pg_stretch_map_check("phase_vocoder_map", false, INT32_MAX, a, k, wide)) return e;
-    return pv_launch<tk::MappedGrid>(k, a->n_ch, wide, stream, "phase_vocoder_map launch failed");
+    return pv_run<tk::MappedGrid>("phase_vocoder_map", pg_stretch_mapped<PG_M_OPTIONAL>(a), stream);
 }

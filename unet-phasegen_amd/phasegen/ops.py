@@ -901,36 +901,26 @@ def spec_clips(plane, n_clips, frames, sf, src_per_out=1.0, out=None, pos=None):
     interpolated between its two neighbours and clamped at the last frame; src_per_out == 1.0 copies.  n_clips = 1, frames = F_out
     resamples the whole plane.  ``pos`` (pg_spec_clips_map): a float64 device tensor of (n_clips - 1) * sf + frames source-frame
     positions, one per global output frame, in place of the line g * src_per_out (NaN and negatives count as 0)."""
-    if not (torch.is_tensor(plane) and plane.is_cuda and plane.dtype == torch.float32 and plane.dim() == 3):
-        raise ValueError("spec_clips: plane must be a 3-D float32 device tensor (n_ch, bins, F_src)")
-    _on_current_device(plane, "plane")
+    who = "spec_clips"
+    p_stride = _vocoder_plane(plane, "plane", who=who)
     n_ch, bins, F_src = plane.shape
     n_clips, frames, sf, src_per_out = int(n_clips), int(frames), int(sf), float(src_per_out)
-    if min(n_ch, bins, F_src, n_clips, frames) < 1 or sf < 1:
-        raise ValueError(f"spec_clips: sizes must be positive (plane {tuple(plane.shape)}, n_clips {n_clips}, frames {frames}, sf {sf})")
+    if min(n_clips, frames, sf) < 1:
+        raise ValueError(f"{who}: sizes must be positive (plane {tuple(plane.shape)}, n_clips {n_clips}, frames {frames}, sf {sf})")
     if not 0.0 < src_per_out < float("inf"):
-        raise ValueError(f"spec_clips: src_per_out must be finite and positive, got {src_per_out}")
-    if (F_src > 1 and plane.stride(2) != 1) or (bins > 1 and plane.stride(1) != F_src):
-        raise ValueError(f"spec_clips: frames must be contiguous and rows F_src apart (strides {plane.stride()})")
-    p_stride = plane.stride(0) if n_ch > 1 else bins * F_src
-    if p_stride < bins * F_src:
-        raise ValueError(f"spec_clips: channels overlap in memory (strides {plane.stride()})")
-    if pos is not None:
-        who = "spec_clips"
-        p = _pos_table(pos, (n_clips - 1) * sf + frames, who, src_per_out, "(n_clips - 1) * sf + frames")
+        raise ValueError(f"{who}: src_per_out must be finite and positive, got {src_per_out}")
+    if pos is None:
+        name, a = who, _lib.SpecClipsArgs()
+        a.src_per_out, a.p_stride = src_per_out, p_stride
+    else:
+        name, a = "spec_clips_map", _lib.SpecClipsMapArgs()
+        a.pos = _pos_table(pos, (n_clips - 1) * sf + frames, who, src_per_out, "(n_clips - 1) * sf + frames")
         _int32_sizes(who, F_src=F_src, n_clips=n_clips, frames=frames, sf=sf)
-        out = _out(out, (n_clips, n_ch, bins, frames), plane.device, who)
-        m = _lib.SpecClipsMapArgs()
-        m.n_clips, m.n_ch, m.bins, m.frames, m.sf, m.F_src = n_clips, n_ch, bins, frames, sf, F_src
-        m.p_ch_rows = _ch_rows(p_stride, F_src, bins, n_ch, who, "plane")
-        m.pos, m.P, m.out = p, plane.data_ptr(), _dense(out, "out")
-        _lib.check(_lib.load().pg_spec_clips_map(C.byref(m), _stream()), "spec_clips_map")
-        return out
-    out = _out(out, (n_clips, n_ch, bins, frames), plane.device, "spec_clips")
-    a = _lib.SpecClipsArgs()
-    a.n_clips, a.n_ch, a.bins, a.frames, a.sf, a.F_src, a.src_per_out = n_clips, n_ch, bins, frames, sf, F_src, src_per_out
-    a.P, a.p_stride, a.out = plane.data_ptr(), p_stride, _dense(out, "out")
-    _lib.check(_lib.load().pg_spec_clips(C.byref(a), _stream()), "spec_clips")
+        a.p_ch_rows = _ch_rows(p_stride, F_src, bins, n_ch, who, "plane")
+    out = _out(out, (n_clips, n_ch, bins, frames), plane.device, who)
+    a.n_clips, a.n_ch, a.bins, a.frames, a.sf, a.F_src = n_clips, n_ch, bins, frames, sf, F_src
+    a.P, a.out = plane.data_ptr(), _dense(out, "out")
+    _lib.check(getattr(_lib.load(), "pg_" + name)(C.byref(a), _stream()), name)
     return out
 
 
@@ -991,11 +981,21 @@ def _vocoder_plane(t, name, shape=None, who="phase_vocoder"):
     return stride
 
 
-def _stretch_args(a, who, angle, F_out, src_per_out, logmag, reset_below, out):
-    """Checks the arguments ``phase_vocoder`` and ``phase_lock`` share and fills the fields PhaseLockArgs has in common with
-    PhaseVocoderArgs (everything but the workspace) -> ``out``, allocated when None."""
+def _stretch_args(a, who, angle, F_out, src_per_out, pos, logmag, reset_below, out, refs=None):
+    """Checks the arguments ``phase_vocoder``, ``phase_lock`` and ``phase_lock_linked`` share and fills everything but the workspace
+    of ``a``, one of their six structs: with ``pos`` (F_out source-frame positions) a mapped one, which takes the table and channel
+    strides in rows, else a uniform one, which takes ``src_per_out`` and strides in elements.  ``refs``: (ref_angle, ref_logmag) of
+    a linked call.  The scalars are range-checked first, ``src_per_out`` too when ``pos`` is given; then a ``pos`` beside a
+    ``src_per_out`` other than 1.0 is refused.  -> ``out``, allocated when None."""
     a_stride = _vocoder_plane(angle, "angle", who=who)
     n_ch, bins, F_src = angle.shape
+    if refs is not None:
+        refs = [t[None] if torch.is_tensor(t) and t.dim() == 2 else t for t in refs]
+        for t, name in zip(refs, ("ref_angle", "ref_logmag")):
+            _vocoder_plane(t, name, who=who)
+            if tuple(t.shape) != (1, bins, F_src):
+                raise ValueError(f"{who}: {name} must be (bins, F_src) or (1, bins, F_src) = {(1, bins, F_src)}, got {tuple(t.shape)}")
+        a.Aref, a.Mref = refs[0].data_ptr(), refs[1].data_ptr()
     F_out, src_per_out, reset_below = int(F_out), float(src_per_out), float(reset_below)
     if F_out < 1:
         raise ValueError(f"{who}: F_out must be positive, got {F_out}")
@@ -1003,35 +1003,39 @@ def _stretch_args(a, who, angle, F_out, src_per_out, logmag, reset_below, out):
         raise ValueError(f"{who}: src_per_out must be finite and positive, got {src_per_out}")
     if not 0.0 <= reset_below < float("inf"):
         raise ValueError(f"{who}: reset_below must be finite and not negative, got {reset_below}")
+    mapped = pos is not None
+    if mapped:
+        a.pos = _pos_table(pos, F_out, who, src_per_out, "F_out")
+        _int32_sizes(who, F_src=F_src, F_out=F_out)
+    else:
+        a.src_per_out = src_per_out
     if logmag is not None:
-        a.m_stride = _vocoder_plane(logmag, "logmag", angle.shape, who=who)
-        a.M = logmag.data_ptr()
-    out = _out(out, (n_ch, bins, F_out), angle.device, who)
-    a.n_ch, a.bins, a.F_src, a.F_out, a.src_per_out, a.reset_below = n_ch, bins, F_src, F_out, src_per_out, reset_below
-    a.A, a.a_stride = angle.data_ptr(), a_stride
-    a.out = _dense(out, "out")
-    return out
-
-
-def _stretch_map_args(a, who, angle, F_out, src_per_out, pos, logmag, reset_below, out):
-    """``_stretch_args`` for the mapped twins (PhaseVocoderMapArgs / PhaseLockMapArgs): ``pos`` holds F_out source-frame positions."""
-    a_stride = _vocoder_plane(angle, "angle", who=who)
-    n_ch, bins, F_src = angle.shape
-    F_out, reset_below = int(F_out), float(reset_below)
-    if F_out < 1:
-        raise ValueError(f"{who}: F_out must be positive, got {F_out}")
-    a.pos = _pos_table(pos, F_out, who, float(src_per_out), "F_out")
-    if not 0.0 <= reset_below < float("inf"):
-        raise ValueError(f"{who}: reset_below must be finite and not negative, got {reset_below}")
-    _int32_sizes(who, F_src=F_src, F_out=F_out)
-    if logmag is not None:
-        a.m_ch_rows = _ch_rows(_vocoder_plane(logmag, "logmag", angle.shape, who=who), F_src, bins, n_ch, who, "logmag")
+        m_stride = _vocoder_plane(logmag, "logmag", angle.shape, who=who)
+        if mapped:
+            a.m_ch_rows = _ch_rows(m_stride, F_src, bins, n_ch, who, "logmag")
+        else:
+            a.m_stride = m_stride
         a.M = logmag.data_ptr()
     out = _out(out, (n_ch, bins, F_out), angle.device, who)
     a.n_ch, a.bins, a.F_src, a.F_out, a.reset_below = n_ch, bins, F_src, F_out, reset_below
-    a.A, a.a_ch_rows = angle.data_ptr(), _ch_rows(a_stride, F_src, bins, n_ch, who, "angle")
-    a.out = _dense(out, "out")
+    if mapped:
+        a.a_ch_rows = _ch_rows(a_stride, F_src, bins, n_ch, who, "angle")
+    else:
+        a.a_stride = a_stride
+    a.A, a.out = angle.data_ptr(), _dense(out, "out")
     return out
+
+
+PHASE_LOCK_CHUNK = 32          # output frames per chunk of pg_phase_lock's scan (csrc/lock.hip: LK_CHUNK)
+_lock_ws = _StreamCache()
+_caches.append(_lock_ws)
+
+
+def _lock_call(name, a, device):
+    """pg_<name>, one of the five entry points of csrc/lock.hip, on the workspace its own query asks for."""
+    lib, query = _lib.load(), "workspace_bytes_" + name
+    a.workspace, a.workspace_bytes = _workspace(_lock_ws, device, getattr(lib, "pg_" + query)(C.byref(a)), query)
+    _lib.check(getattr(lib, "pg_" + name)(C.byref(a), _stream()), name)
 
 
 @_pos_keyword
@@ -1045,20 +1049,10 @@ def phase_vocoder(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, o
     src_per_out == 1.0 returns the analysis phase (to 2 pi / 2^33 and one rounding).  ``pos`` (pg_phase_vocoder_map): a float64
     device tensor of F_out source-frame positions in place of the line g * src_per_out (NaN and negatives count as 0; the positions
     need not grow)."""
-    if pos is not None:
-        m = _lib.PhaseVocoderMapArgs()
-        out = _stretch_map_args(m, "phase_vocoder", angle, F_out, src_per_out, pos, logmag, reset_below, out)
-        _lib.check(_lib.load().pg_phase_vocoder_map(C.byref(m), _stream()), "phase_vocoder_map")
-        return out
-    a = _lib.PhaseVocoderArgs()
-    out = _stretch_args(a, "phase_vocoder", angle, F_out, src_per_out, logmag, reset_below, out)
-    _lib.check(_lib.load().pg_phase_vocoder(C.byref(a), _stream()), "phase_vocoder")
+    name, a = ("phase_vocoder", _lib.PhaseVocoderArgs()) if pos is None else ("phase_vocoder_map", _lib.PhaseVocoderMapArgs())
+    out = _stretch_args(a, "phase_vocoder", angle, F_out, src_per_out, pos, logmag, reset_below, out)
+    _lib.check(getattr(_lib.load(), "pg_" + name)(C.byref(a), _stream()), name)
     return out
-
-
-PHASE_LOCK_CHUNK = 32          # output frames per chunk of pg_phase_lock's scan (csrc/lock.hip: LK_CHUNK)
-_lock_ws = _StreamCache()
-_caches.append(_lock_ws)
 
 
 @_pos_keyword
@@ -1072,18 +1066,9 @@ def phase_lock(angle, F_out, src_per_out=1.0, logmag=None, reset_below=0.0, out=
     (pg_phase_lock_map): F_out source-frame positions, as in ``phase_vocoder``."""
     if logmag is None:
         raise ValueError("phase_lock: logmag is required (the peaks are those of the log-magnitude)")
-    if pos is not None:
-        m = _lib.PhaseLockMapArgs()
-        out = _stretch_map_args(m, "phase_lock", angle, F_out, src_per_out, pos, logmag, reset_below, out)
-        lib = _lib.load()
-        m.workspace, m.workspace_bytes = _workspace(_lock_ws, angle.device, lib.pg_workspace_bytes_phase_lock_map(C.byref(m)), "workspace_bytes_phase_lock_map")
-        _lib.check(lib.pg_phase_lock_map(C.byref(m), _stream()), "phase_lock_map")
-        return out
-    a = _lib.PhaseLockArgs()
-    out = _stretch_args(a, "phase_lock", angle, F_out, src_per_out, logmag, reset_below, out)
-    lib = _lib.load()
-    a.workspace, a.workspace_bytes = _workspace(_lock_ws, angle.device, lib.pg_workspace_bytes_phase_lock(C.byref(a)), "workspace_bytes_phase_lock")
-    _lib.check(lib.pg_phase_lock(C.byref(a), _stream()), "phase_lock")
+    name, a = ("phase_lock", _lib.PhaseLockArgs()) if pos is None else ("phase_lock_map", _lib.PhaseLockMapArgs())
+    out = _stretch_args(a, "phase_lock", angle, F_out, src_per_out, pos, logmag, reset_below, out)
+    _lock_call(name, a, angle.device)
     return out
 
 
@@ -1097,47 +1082,9 @@ def phase_lock_linked(angle, ref_angle, ref_logmag, F_out, src_per_out=1.0, rese
     stereo image and the mono sum survive the stretch.  A channel equal to the reference gets ``phase_lock``'s bits;
     src_per_out == 1.0 returns the analysis phase.  ``pos`` (pg_phase_lock_linked_map): F_out source-frame positions, as in
     ``phase_vocoder``."""
-    who = "phase_lock_linked"
-    a_stride = _vocoder_plane(angle, "angle", who=who)
-    n_ch, bins, F_src = angle.shape
-    refs = []
-    for t, name in ((ref_angle, "ref_angle"), (ref_logmag, "ref_logmag")):
-        if torch.is_tensor(t) and t.dim() == 2:
-            t = t[None]
-        _vocoder_plane(t, name, who=who)
-        if tuple(t.shape) != (1, bins, F_src):
-            raise ValueError(f"{who}: {name} must be (bins, F_src) or (1, bins, F_src) = {(1, bins, F_src)}, got {tuple(t.shape)}")
-        refs.append(t)
-    F_out, src_per_out, reset_below = int(F_out), float(src_per_out), float(reset_below)
-    if F_out < 1:
-        raise ValueError(f"{who}: F_out must be positive, got {F_out}")
-    if not 0.0 < src_per_out < float("inf"):
-        raise ValueError(f"{who}: src_per_out must be finite and positive, got {src_per_out}")
-    if not 0.0 <= reset_below < float("inf"):
-        raise ValueError(f"{who}: reset_below must be finite and not negative, got {reset_below}")
-    if pos is not None:
-        m = _lib.PhaseLockLinkedMapArgs()
-        m.pos = _pos_table(pos, F_out, who, src_per_out, "F_out")
-        _int32_sizes(who, F_src=F_src, F_out=F_out)
-        out = _out(out, (n_ch, bins, F_out), angle.device, who)
-        m.n_ch, m.bins, m.F_src, m.F_out, m.reset_below = n_ch, bins, F_src, F_out, reset_below
-        m.A, m.a_ch_rows = angle.data_ptr(), _ch_rows(a_stride, F_src, bins, n_ch, who, "angle")
-        m.Aref, m.Mref = refs[0].data_ptr(), refs[1].data_ptr()
-        m.out = _dense(out, "out")
-        lib = _lib.load()
-        m.workspace, m.workspace_bytes = _workspace(_lock_ws, angle.device, lib.pg_workspace_bytes_phase_lock_linked_map(C.byref(m)),
-                                                    "workspace_bytes_phase_lock_linked_map")
-        _lib.check(lib.pg_phase_lock_linked_map(C.byref(m), _stream()), "phase_lock_linked_map")
-        return out
-    out = _out(out, (n_ch, bins, F_out), angle.device, who)
-    a = _lib.PhaseLockLinkedArgs()
-    a.n_ch, a.bins, a.F_src, a.F_out, a.src_per_out, a.reset_below = n_ch, bins, F_src, F_out, src_per_out, reset_below
-    a.A, a.a_stride = angle.data_ptr(), a_stride
-    a.Aref, a.Mref = refs[0].data_ptr(), refs[1].data_ptr()
-    a.out = _dense(out, "out")
-    lib = _lib.load()
-    a.workspace, a.workspace_bytes = _workspace(_lock_ws, angle.device, lib.pg_workspace_bytes_phase_lock_linked(C.byref(a)), "workspace_bytes_phase_lock_linked")
-    _lib.check(lib.pg_phase_lock_linked(C.byref(a), _stream()), who)
+    name, a = ("phase_lock_linked", _lib.PhaseLockLinkedArgs()) if pos is None else ("phase_lock_linked_map", _lib.PhaseLockLinkedMapArgs())
+    out = _stretch_args(a, "phase_lock_linked", angle, F_out, src_per_out, pos, None, reset_below, out, refs=(ref_angle, ref_logmag))
+    _lock_call(name, a, angle.device)
     return out
 
 
@@ -1161,9 +1108,7 @@ def phase_spsi(logmag, n_fft, hop, bin0=1, out=None):
     a.n_ch, a.bins, a.F, a.n_fft, a.hop, a.bin0 = n_ch, bins, F, n_fft, hop, bin0
     a.M, a.m_stride = logmag.data_ptr(), m_stride
     a.out = _dense(out, "out")
-    lib = _lib.load()
-    a.workspace, a.workspace_bytes = _workspace(_lock_ws, logmag.device, lib.pg_workspace_bytes_phase_spsi(C.byref(a)), "workspace_bytes_phase_spsi")
-    _lib.check(lib.pg_phase_spsi(C.byref(a), _stream()), "phase_spsi")
+    _lock_call("phase_spsi", a, logmag.device)
     return out
 
 
@@ -1253,32 +1198,32 @@ def ola_stretch(x, n_out, src_per_out=1.0, win_len=256, hop=64, base=None, out=N
     if not 1 <= hop <= win_len // 2:
         raise ValueError(f"{who}: hop must be within 1 .. win_len / 2 = {win_len // 2}, got {hop}")
     want = (n_out,) if x.dim() == 1 else (n_sig, n_out)
-    a = _lib.OlaStretchArgs()
-    if pos is not None:
-        a = _lib.OlaStretchMapArgs()
-        a.pos = _pos_table(pos, ola_grains(n_out, win_len, hop), who, src_per_out, "ola_grains(n_out, win_len, hop)")
-        _int32_sizes(who, n_in=n_in, n_out=n_out, x_stride=x2.stride(0) if n_sig > 1 else 0)
+    b2 = None
     if base is not None:
         if not torch.is_tensor(base) or tuple(base.shape) != want:
             raise ValueError(f"{who}: base must be shaped like the result, {want}")
         b2 = _ola_rows(base, "base", who)
-        if pos is not None:
-            _int32_sizes(who, base_stride=b2.stride(0) if n_sig > 1 else 0)
-        a.base, a.base_stride = b2.data_ptr(), (b2.stride(0) if n_sig > 1 else n_out)
     out = _out(out, want, x.device, who, rows=True)
     o2 = out[None] if out.dim() == 1 else out
     if n_sig > 1 and o2.stride(0) < n_out:
         raise ValueError(f"{who}: rows of out overlap (strides {out.stride()})")
+    # (the stride of a single row is its length)
+    x_stride, y_stride = (x2.stride(0), o2.stride(0)) if n_sig > 1 else (n_in, n_out)
+    base_stride = 0 if b2 is None else b2.stride(0) if n_sig > 1 else n_out
+    if pos is None:
+        name, a = who, _lib.OlaStretchArgs()
+        a.src_per_out = src_per_out
+    else:
+        name, a = "ola_stretch_map", _lib.OlaStretchMapArgs()
+        a.pos = _pos_table(pos, ola_grains(n_out, win_len, hop), who, src_per_out, "ola_grains(n_out, win_len, hop)")
+        _int32_sizes(who, n_in=n_in, n_out=n_out, x_stride=x_stride, base_stride=base_stride, y_stride=y_stride)
     a.n_sig, a.win_len, a.hop, a.n_in, a.n_out = n_sig, win_len, hop, n_in, n_out
-    a.x, a.x_stride = x2.data_ptr(), (x2.stride(0) if n_sig > 1 else n_in)
+    a.x, a.x_stride = x2.data_ptr(), x_stride
+    if b2 is not None:
+        a.base, a.base_stride = b2.data_ptr(), base_stride
+    a.y, a.y_stride = o2.data_ptr(), y_stride
     a.win = _ola_window(win_len, x.device).data_ptr()
-    a.y, a.y_stride = o2.data_ptr(), (o2.stride(0) if n_sig > 1 else n_out)
-    if pos is not None:
-        _int32_sizes(who, y_stride=o2.stride(0) if n_sig > 1 else 0)
-        _lib.check(_lib.load().pg_ola_stretch_map(C.byref(a), _stream()), "ola_stretch_map")
-        return out
-    a.src_per_out = src_per_out
-    _lib.check(_lib.load().pg_ola_stretch(C.byref(a), _stream()), who)
+    _lib.check(getattr(_lib.load(), "pg_" + name)(C.byref(a), _stream()), name)
     return out
 
 
