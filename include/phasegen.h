@@ -878,6 +878,56 @@ typedef struct pg_ola_stretch_map_args {
 } pg_ola_stretch_map_args;                       /* 72 bytes */
 int     pg_ola_stretch_map(const pg_ola_stretch_map_args* a, void* stream);
 
+/* pg_varispeed: a band-limited resampler whose read position and bandwidth vary along the output -- the playback half of a pitch
+ * curve (phasegen/track.py, PitchCurve), where pg_resample takes one (up, down) for the whole row.  Struct of its own, PG_VERSION
+ * unchanged; the reference has no counterpart; the arithmetic below is the contract.
+ *   Filter.  Smith's table-driven band-limited interpolation with pg_resample's Kaiser-windowed sinc
+ *   h(t) = r sinc(r t) I0(beta sqrt(1 - (t/Z)^2)) / I0(beta), |t| <= Z, sampled L = per_zero times per zero crossing and interpolated
+ *   linearly (the scheme resampy uses, with the table built exactly).  pg_varispeed_table_elems(Z, L) = 2 (Z L + 1) (negative = error
+ *   code).  pg_varispeed_table (HOST, in double, as pg_resample_bank) fills pairs (h_i, d_i), i = 0 .. Z L: h_i = float32(h(i / L)),
+ *   d_i = fl32(h_{i+1} - h_i) of the ROUNDED values, d_{ZL} = 0.  The caller passes a DEVICE copy as `table`; the kernel reads no other
+ *   coefficients.  Limits: Z in [1, 64], L a power of two in [1, 512], beta in [0, 15], r in (0, 1].
+ *   Tables.  step is a power of two, 1 <= step <= 4096; nb = ceil(n_out / step) blocks of step outputs.  pos: nb + 1 source positions
+ *   in samples, one per block end; scale: nb bandwidths, one per block.
+ *   Per output t of a row, every operation a separate IEEE operation (nothing contracted):
+ *     j = t div step, q = t - j step
+ *     P_j = pc(pos[j]), the mapped kernels' clamp above: a NaN or a negative position counts as 0, anything above 2^52 as 2^52
+ *     delta = (P_{j+1} - P_j) (1.0 / step);   p = P_j + (double)q delta                        (double)
+ *     s = sc(scale[j]),  sc(v) = !(v >= 0.25f) ? 0.25f : (v > 1.0f ? 1.0f : v): a NaN, zero or tiny scale counts as 0.25
+ *     for every integer n in [0, n_in), ascending:
+ *       u = fabs(p - (double)n) ((double)s L)                                                   (double; the product s L is exact)
+ *       the tap belongs to the sum iff u < Z L;   i = (int)floor(u),  eta = (float)(u - floor(u))
+ *       w = fl(fl(h_i + fl(eta d_i)) s);   acc = fl(acc + fl(w x[n])), from acc = 0.0f           (float)
+ *     y[t] = acc
+ *   Consequences.  A tap outside the support or outside the row is not read and not added: the result depends on the set of taps
+ *   alone, never on the loop bounds the kernel chooses.  A NaN in x reaches exactly the outputs whose support contains it.  Row
+ *   padding and the next row are never read.  Positions need not be monotone (a frozen table repeats a sample, a backward step plays
+ *   backwards).  A row's bits do not depend on n_sig or on its place in the batch.  An output whose support misses the row is +0.0.
+ *   Sizes.  Every size is an int32_t and the row strides are counts of samples; all index arithmetic inside is 64-bit.  There is no
+ *   workspace: the library allocates nothing and keeps nothing.
+ *   Kernel: one workgroup per 1024 consecutive outputs of one row.  It folds the clamped block ends its tile touches into a source
+ *   span; a span that, with the filter's widest reach 4 Z on either side, fits 48 KB of LDS is staged once and summed from there,
+ *   any other (jumps, backward steps, hostile tables) is summed straight from global memory with the same chain: the same bits.
+ *   One 8-byte load of (h_i, d_i) per tap; no atomics; one launch on the caller's stream.
+ *   Errors (host side, before any launch, in this order): NULL args PG_ERR_NULL; non-positive n_sig / n_in / n_out PG_ERR_SHAPE;
+ *   step, zeros or per_zero outside the limits or not a power of two where one is required PG_ERR_UNSUPPORTED; a stride shorter
+ *   than its row PG_ERR_SHAPE; pos, scale, table, x or y NULL PG_ERR_NULL; pos or table not 8-byte aligned PG_ERR_ALIGN.  Messages
+ *   begin "varispeed: ".  pg_varispeed_table: NULL PG_ERR_NULL, zeros / per_zero as above, beta or rolloff outside the limits
+ *   PG_ERR_SHAPE. */
+int64_t pg_varispeed_table_elems(int32_t zeros, int32_t per_zero);   /* 2 (Z L + 1); negative = error code */
+int     pg_varispeed_table(float* table_host, int32_t zeros, int32_t per_zero, double beta, double rolloff);  /* HOST, double arithmetic */
+typedef struct pg_varispeed_args {
+    int32_t n_sig, n_in, n_out, step;            /* step: a power of two, 1 <= step <= 4096                             */
+    int32_t zeros, per_zero;                     /* Z in [1, 64]; L a power of two in [1, 512]                          */
+    int32_t x_stride, y_stride;                  /* rows x_stride >= n_in, y_stride >= n_out samples apart              */
+    const double* pos;                           /* DEVICE: nb + 1 source positions in samples, nb = ceil(n_out / step) */
+    const float*  scale;                         /* DEVICE: nb bandwidths, one per block                                */
+    const float*  table;                         /* DEVICE copy of pg_varispeed_table's output                          */
+    const float*  x;                             /* (n_sig, n_in)                                                       */
+    float*        y;                             /* (n_sig, n_out)                                                      */
+} pg_varispeed_args;                             /* 72 bytes */
+int     pg_varispeed(const pg_varispeed_args* a, void* stream);
+
 /* pg_formant_shift: the spectral envelope of every frame of a log1p-magnitude plane and, optionally, the plane with that envelope
  * re-imposed at `ratio` times each bin's frequency -- formant preservation for a pitch shift (phasegen/track.py, formant_semitones,
  * pitch_shift(formants="keep")): the resampling that moves the partials moves the envelope with them, and this moves it back.

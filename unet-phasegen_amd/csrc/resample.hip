@@ -36,6 +36,7 @@
 #include <stdint.h>
 #include "phasegen.h"
 #include "pg_common.h"
+#include "pg_kaiser.h"
 
 namespace {
 
@@ -44,9 +45,6 @@ constexpr int RS_KB = 8;            // taps whose bank values a lane fetches tog
 constexpr int RS_WIN_MAX = 12288;   // floats of LDS a workgroup's input window may take (48 KB: three workgroups per CU)
 constexpr int RS_S_MAX = 4096;      // same-phase spacing S <= this: per-lane offsets (4 S) * D stay far below 2^31
 constexpr int RS_U_MAX = 1024, RS_TAPS_MAX = 2048;
-
-struct RsFilter { int Z; double beta, rolloff; };
-constexpr RsFilter RS_FILTERS[2] = {{64, 14.769656459379492, 0.9475937167399596}, {16, 8.555504641634386, 0.85}};
 
 // the reduced ratio and everything that follows from it (host; pure function of up, down, quality)
 struct RsPlan {
@@ -87,17 +85,6 @@ int rs_plan(int32_t up, int32_t down, int32_t quality, RsPlan& p) {
     p.tile = p.R * p.S;
     p.win = rs_window(p, p.tile);
     return PG_OK;
-}
-
-double rs_i0(double x) {                                          // modified Bessel function I0 by its power series (x <= 15)
-    const double q = 0.25 * x * x;
-    double term = 1.0, sum = 1.0;
-    for (int k = 1; k < 500; ++k) {
-        term *= q / ((double)k * (double)k);
-        sum += term;
-        if (term < 1e-18 * sum) break;
-    }
-    return sum;
 }
 
 struct RsKernelArgs {
@@ -201,13 +188,7 @@ extern "C" int pg_resample_bank(float* bank_host, int32_t up, int32_t down, int3
     for (int k = 0; k < p.taps; ++k)
         for (int ph = 0; ph < p.U; ++ph) {
             const double t = (double)((long)ph + (long)p.U * (p.H - k)) / den;
-            double h = 0.0;
-            if (fabs(t) <= (double)f.Z) {
-                const double u = t / (double)f.Z, a = M_PI * f.rolloff * t;
-                const double sinc = a == 0.0 ? 1.0 : sin(a) / a;
-                const double c = 1.0 - u * u;
-                h = f.rolloff * sinc * rs_i0(f.beta * sqrt(c > 0.0 ? c : 0.0)) / i0b;
-            }
+            const double h = rs_h(t, (double)f.Z, f.beta, f.rolloff, i0b);
             bank_host[(long)k * p.U + ph] = (float)(s * h);
         }
     return PG_OK;

@@ -276,6 +276,17 @@ class OlaStretchMapArgs(C.Structure):
                 ("pos", C.c_void_p), ("x", C.c_void_p), ("win", C.c_void_p), ("base", C.c_void_p), ("y", C.c_void_p)]
 
 
+VARISPEED_MAX_ZEROS, VARISPEED_MAX_PER_ZERO, VARISPEED_MAX_STEP = 64, 512, 4096     # pg_varispeed's limits
+
+
+class VarispeedArgs(C.Structure):
+    """pg_varispeed_args: band-limited resampling along a table of source positions and bandwidths (include/phasegen.h).  No 64-bit
+    integer field: every size is an int32 and the row strides are counts of samples."""
+    _fields_ = [("n_sig", C.c_int32), ("n_in", C.c_int32), ("n_out", C.c_int32), ("step", C.c_int32),
+                ("zeros", C.c_int32), ("per_zero", C.c_int32), ("x_stride", C.c_int32), ("y_stride", C.c_int32),
+                ("pos", C.c_void_p), ("scale", C.c_void_p), ("table", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p)]
+
+
 class WaveCompareArgs(C.Structure):
     """pg_wave_compare_args: six sums per signal of a reference / estimate pair of waveforms (include/phasegen.h)."""
     _fields_ = [("n_signals", C.c_int32), ("_pad0", C.c_int32), ("n", C.c_int64),
@@ -359,6 +370,9 @@ SYMBOLS = {
     "pg_workspace_bytes_phase_lock_linked_map": (C.c_int64, [C.POINTER(PhaseLockLinkedMapArgs)]),
     "pg_phase_lock_linked_map": (C.c_int, [C.POINTER(PhaseLockLinkedMapArgs), C.c_void_p]),
     "pg_ola_stretch_map": (C.c_int, [C.POINTER(OlaStretchMapArgs), C.c_void_p]),
+    "pg_varispeed_table_elems": (C.c_int64, [C.c_int32, C.c_int32]),
+    "pg_varispeed_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
+    "pg_varispeed": (C.c_int, [C.POINTER(VarispeedArgs), C.c_void_p]),
     "pg_workspace_bytes_wave_compare": (C.c_int64, [C.POINTER(WaveCompareArgs)]),
     "pg_wave_compare": (C.c_int, [C.POINTER(WaveCompareArgs), C.c_void_p]),
     "pg_workspace_bytes_spec_compare": (C.c_int64, [C.POINTER(SpecCompareArgs)]),

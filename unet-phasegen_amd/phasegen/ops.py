@@ -781,6 +781,107 @@ def resample(x, orig_sr, target_sr, res_type="kaiser_best", out=None):
     return out
 
 
+# resampy's published (zeros, beta, rolloff) per quality: the parameters of pg_resample's filter (csrc/pg_kaiser.h)
+VARISPEED_FILTERS = {_lib.RS_KAISER_BEST: (64, 14.769656459379492, 0.9475937167399596), _lib.RS_KAISER_FAST: (16, 8.555504641634386, 0.85)}
+_varispeed_tables = {}   # (device, quality, per_zero) -> device copy of pg_varispeed_table's output (read-only; at most 256 KB each)
+
+
+def varispeed_table_host(zeros, per_zero, beta, rolloff):
+    """pg_varispeed_table: the (zeros * per_zero + 1, 2) float32 table of pairs (h_i, h_{i+1} - h_i) of the Kaiser-windowed sinc,
+    ``per_zero`` samples per zero crossing, built on the host in double (no GPU needed)."""
+    import numpy as np
+    lib = _lib.load()
+    zeros, per_zero = int(zeros), int(per_zero)
+    n = lib.pg_varispeed_table_elems(zeros, per_zero)
+    if n < 0:
+        _lib.check(int(n), "varispeed_table_elems")
+    table = np.empty(n, np.float32)
+    _lib.check(lib.pg_varispeed_table(table.ctypes.data_as(C.c_void_p), zeros, per_zero, float(beta), float(rolloff)), "varispeed_table")
+    return table.reshape(-1, 2)
+
+
+def _varispeed_table(quality, per_zero, device):
+    key = (torch.device(device), quality, per_zero)
+    table = _varispeed_tables.get(key)
+    if table is None:
+        zeros, beta, rolloff = VARISPEED_FILTERS[quality]
+        table = _varispeed_tables[key] = torch.from_numpy(varispeed_table_host(zeros, per_zero, beta, rolloff)).to(device)
+    return table
+
+
+def varispeed_blocks(n_out, step):
+    """nb = ceil(n_out / step): the blocks of ``varispeed``; ``pos`` holds nb + 1 entries and ``scale`` nb."""
+    return -(-int(n_out) // int(step))
+
+
+def varispeed(x, pos, scale, n_out, step=64, res_type="kaiser_best", per_zero=512, table=None, out=None):
+    """Band-limited resampling along a table of source positions (pg_varispeed): x (n,) or (n_signals, n) float32 on the device whose
+    rows are contiguous (the row stride is free) -> (..., n_out).  Output t of block j = t // step reads the source at
+    pos[j] + (t - j step) (pos[j + 1] - pos[j]) / step samples through the Kaiser-windowed sinc of ``resample`` narrowed to
+    scale[j] in [0.25, 1] of the band (1: the filter as it is; below 1 for a block that is read faster than one sample per output).
+    ``pos``: 1-D float64 device tensor of nb + 1 entries, ``scale``: 1-D float32 device tensor of nb entries, nb =
+    ``varispeed_blocks(n_out, step)``; ``step`` a power of two up to 4096.  ``res_type`` picks resampy's (zeros, beta, rolloff), as in
+    ``resample``; the filter is tabulated ``per_zero`` times per zero crossing (a power of two up to 512) and interpolated linearly,
+    the table built once per (device, res_type, per_zero).  ``table``: (device table from ``varispeed_table_host``, zeros, per_zero)
+    in place of the cached one."""
+    who = "varispeed"
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() in (1, 2)):
+        raise ValueError(f"{who}: expected a 1-D or 2-D float32 device tensor")
+    _on_current_device(x, "x")
+    x2 = x[None] if x.dim() == 1 else x
+    n_sig, n_in = x2.shape
+    n_out, step = int(n_out), int(step)
+    if n_sig < 1 or n_in < 1 or n_out < 1:
+        raise ValueError(f"{who}: empty input {tuple(x.shape)} or n_out {n_out}")
+    if n_in > 1 and x2.stride(1) != 1:
+        raise ValueError(f"{who}: samples must be contiguous (strides {x.stride()})")
+    if not (1 <= step <= _lib.VARISPEED_MAX_STEP and step & (step - 1) == 0):
+        raise ValueError(f"{who}: step must be a power of two within [1, {_lib.VARISPEED_MAX_STEP}], got {step}")
+    if table is None:
+        if res_type not in _RES_TYPES:
+            raise ValueError(f"{who}: res_type must be 'kaiser_best' or 'kaiser_fast', got {res_type!r}")
+        quality, per_zero = _RES_TYPES[res_type], int(per_zero)
+        zeros = VARISPEED_FILTERS[quality][0]
+        if not (1 <= per_zero <= _lib.VARISPEED_MAX_PER_ZERO and per_zero & (per_zero - 1) == 0):
+            raise ValueError(f"{who}: per_zero must be a power of two within [1, {_lib.VARISPEED_MAX_PER_ZERO}], got {per_zero}")
+        tab = _varispeed_table(quality, per_zero, x.device)
+    else:
+        try:
+            tab, zeros, per_zero = table
+            zeros, per_zero = int(zeros), int(per_zero)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: table must be (device tensor, zeros, per_zero)")
+        if not (1 <= zeros <= _lib.VARISPEED_MAX_ZEROS and 1 <= per_zero <= _lib.VARISPEED_MAX_PER_ZERO and per_zero & (per_zero - 1) == 0):
+            raise ValueError(f"{who}: table needs zeros within [1, {_lib.VARISPEED_MAX_ZEROS}] and per_zero a power of two within "
+                             f"[1, {_lib.VARISPEED_MAX_PER_ZERO}], got {zeros} and {per_zero}")
+        if not (torch.is_tensor(tab) and tab.is_cuda and tab.dtype == torch.float32 and tab.numel() == 2 * (zeros * per_zero + 1)):
+            raise ValueError(f"{who}: table must be a float32 device tensor of 2 * (zeros * per_zero + 1) = {2 * (zeros * per_zero + 1)} entries")
+    tab_ptr = _dense(tab, "table")
+    nb = varispeed_blocks(n_out, step)
+    if not (torch.is_tensor(pos) and pos.is_cuda and pos.dtype == torch.float64 and pos.dim() == 1):
+        raise ValueError(f"{who}: pos must be a 1-D float64 device tensor")
+    if pos.shape[0] != nb + 1:
+        raise ValueError(f"{who}: pos must hold {nb + 1} entries (ceil(n_out / step) + 1), got {pos.shape[0]}")
+    if not (torch.is_tensor(scale) and scale.is_cuda and scale.dtype == torch.float32 and scale.dim() == 1):
+        raise ValueError(f"{who}: scale must be a 1-D float32 device tensor")
+    if scale.shape[0] != nb:
+        raise ValueError(f"{who}: scale must hold {nb} entries (ceil(n_out / step)), got {scale.shape[0]}")
+    pos_ptr, scale_ptr = _dense_as(pos, torch.float64, "pos"), _dense_as(scale, torch.float32, "scale")
+    want = (n_out,) if x.dim() == 1 else (n_sig, n_out)
+    out = _out(out, want, x.device, who, rows=True)
+    o2 = out[None] if out.dim() == 1 else out
+    x_stride, y_stride = (x2.stride(0) if n_sig > 1 else n_in), (o2.stride(0) if n_sig > 1 else n_out)
+    if x_stride < n_in or y_stride < n_out:
+        raise ValueError(f"{who}: rows overlap in memory (strides {x.stride()} and {out.stride()})")
+    _int32_sizes(who, n_in=n_in, n_out=n_out, x_stride=x_stride, y_stride=y_stride)
+    a = _lib.VarispeedArgs()
+    a.n_sig, a.n_in, a.n_out, a.step, a.zeros, a.per_zero = n_sig, n_in, n_out, step, zeros, per_zero
+    a.x_stride, a.y_stride = x_stride, y_stride
+    a.pos, a.scale, a.table, a.x, a.y = pos_ptr, scale_ptr, tab_ptr, x2.data_ptr(), o2.data_ptr()
+    _lib.check(_lib.load().pg_varispeed(C.byref(a), _stream()), who)
+    return out
+
+
 _stitch_ramps = {}       # (V, device) -> device copy of pg_stitch_ramp's output (read-only)
 _stitch_ws = _StreamCache()
 _caches.append(_stitch_ws)

@@ -49,6 +49,11 @@ window (ops.ola_stretch, ``TRANSIENT_WINDOW`` / ``TRANSIENT_HOP``), which reloca
 output seconds) and piecewise linear between them.  ``TimeMap.plan`` is ``spectral_plan`` for it and holds one source position per
 output frame (and one source centre per overlap-add grain); the tables go to the device once per call and every stretch kernel
 reads them instead of the one rate (``pos=`` of ops.spec_clips, phase_vocoder, phase_lock, phase_lock_linked, ola_stretch).
+
+``pitch_shift`` takes a ``PitchCurve`` wherever it takes a number of semitones: a transposition given by anchors (seconds,
+semitones), piecewise linear between them.  ``PitchCurve.plan`` turns it into a tempo map for the stretch (every 256 samples at the
+stretch 2 ** (semitones / 12) of their midpoint) and into the position and bandwidth tables of the variable-rate resampler that plays
+the stretched track back (ops.varispeed), block by block of 64 samples, so that the result has the input's length and tempo.
 """
 import collections
 import fractions
@@ -764,6 +769,125 @@ def pitch_ratio(semitones, max_denominator=1024):
     return stretch, fractions.Fraction(stretch).limit_denominator(max_denominator)
 
 
+CurvePlan = collections.namedtuple("CurvePlan", "time_map pos scale step")
+PITCH_CURVE_STEP, PITCH_CURVE_SEGMENT = 64, 256                   # ops.varispeed's block and PitchCurve.plan's segment, in samples
+
+
+class PitchCurve:
+    """A pitch curve: a time-varying transposition, piecewise linear in semitones between anchors and constant past the last one
+    (host only, float64).  ``anchors``: a sequence of (seconds, semitones) with at least two entries, finite, the first at 0 s,
+    seconds strictly increasing, |semitones| <= 24 (the domain of a uniform ``pitch_shift``).  ValueError otherwise.
+    ``pitch_shift`` takes one in place of its number of semitones: a glide, a vibrato, a correction, a tape stop."""
+
+    def __init__(self, anchors):
+        try:
+            a = np.array([[float(v) for v in row] for row in anchors], dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"PitchCurve: anchors must be (seconds, semitones) pairs ({e})")
+        if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 2:
+            raise ValueError("PitchCurve: at least two anchors (seconds, semitones)")
+        if not np.isfinite(a).all():
+            raise ValueError("PitchCurve: anchors must be finite")
+        if a[0, 0] != 0.0:
+            raise ValueError(f"PitchCurve: the first anchor must be at 0 s, got {a[0, 0]}")
+        if not (np.diff(a[:, 0]) > 0.0).all():
+            raise ValueError("PitchCurve: seconds must increase strictly")
+        if not (np.abs(a[:, 1]) <= 24.0).all():
+            raise ValueError(f"PitchCurve: semitones must be within [-24, 24], got {a[:, 1].min():g} .. {a[:, 1].max():g}")
+        self.seconds, self.semitones = a[:, 0].copy(), a[:, 1].copy()
+        self.seconds.setflags(write=False)
+        self.semitones.setflags(write=False)
+
+    @property
+    def anchors(self):
+        return [(float(t), float(s)) for t, s in zip(self.seconds, self.semitones)]
+
+    def __repr__(self):
+        return f"PitchCurve({self.anchors!r})"
+
+    def semitones_at(self, t):
+        """the transposition at ``t`` seconds (a number or an array): linear between anchors, the last anchor's from there on"""
+        y = np.interp(np.asarray(t, np.float64), self.seconds, self.semitones)
+        return float(y) if y.ndim == 0 else y
+
+    @classmethod
+    def vibrato(cls, duration_s, depth, rate_hz, per_cycle=16):
+        """``depth`` semitones of vibrato at ``rate_hz`` over ``duration_s`` seconds: depth * sin(2 pi rate_hz t), sampled
+        ``per_cycle`` times per cycle (the last anchor lies at or beyond ``duration_s``)."""
+        duration_s, depth, rate_hz, per_cycle = float(duration_s), float(depth), float(rate_hz), int(per_cycle)
+        if not (0.0 < duration_s < math.inf and 0.0 < rate_hz < math.inf) or per_cycle < 4:
+            raise ValueError(f"PitchCurve.vibrato: duration_s {duration_s} and rate_hz {rate_hz} must be positive and finite and "
+                             f"per_cycle {per_cycle} at least 4")
+        if not abs(depth) <= 24.0:
+            raise ValueError(f"PitchCurve.vibrato: depth must be within [-24, 24], got {depth}")
+        k = np.arange(int(math.ceil(duration_s * rate_hz * per_cycle)) + 1, dtype=np.float64)
+        return cls(list(zip(k / (rate_hz * per_cycle), depth * np.sin(2.0 * np.pi * (k / per_cycle)))))
+
+    @classmethod
+    def load(cls, path):
+        """A text file in ``TimeMap.load``'s format: two columns per line, seconds and semitones."""
+        anchors = []
+        with open(path) as f:
+            for n, line in enumerate(f, 1):
+                cols = line.split("#", 1)[0].replace(",", " ").split()
+                if not cols:
+                    continue
+                if len(cols) != 2:
+                    raise ValueError(f"PitchCurve.load: {path}:{n}: expected two columns, got {len(cols)}")
+                try:
+                    anchors.append((float(cols[0]), float(cols[1])))
+                except ValueError:
+                    raise ValueError(f"PitchCurve.load: {path}:{n}: not two numbers: {line.strip()!r}")
+        return cls(anchors)
+
+    def save(self, path):
+        with open(path, "w") as f:
+            f.write("# seconds semitones\n")
+            for t, s in zip(self.seconds, self.semitones):
+                f.write(f"{float(t)!r} {float(s)!r}\n")
+
+    def plan(self, a_len, sr=16000, step=PITCH_CURVE_STEP, segment=PITCH_CURVE_SEGMENT):
+        """The two halves of a pitch shift along this curve for a track of ``a_len`` samples at ``sr`` (host only): a
+        ``CurvePlan(time_map, pos, scale, step)``.
+          segment i covers the samples [i segment, (i + 1) segment) and is stretched by r_i = 2 ** (semitones_at(its midpoint) / 12)
+          time_map    the ``TimeMap`` through (i segment, sum of segment r_k for k < i) / sr: what ``reconstruct_track`` stretches by
+          pos[j] = time_map.out_of_src(j step, sr), j = 0 .. nb, nb = ceil(a_len / step): where output block j of ``ops.varispeed``
+                      begins in the stretched track
+          scale[j] = float32(min(1, step / (pos[j + 1] - pos[j]))): the band of a block that is read faster than it is written
+        ``segment`` is a multiple of ``step``, so every block lies inside one segment: the resampler undoes the stretch exactly at
+        every block boundary, and the tempo is the input's by construction."""
+        a_len, sr, step, segment = int(a_len), int(sr), int(step), int(segment)
+        if a_len < 1 or sr < 1:
+            raise ValueError(f"PitchCurve.plan: a_len {a_len} and sr {sr} must be positive")
+        if not (1 <= step <= 4096 and step & (step - 1) == 0):
+            raise ValueError(f"PitchCurve.plan: step must be a power of two within [1, 4096], got {step}")
+        if segment < step or segment % step:
+            raise ValueError(f"PitchCurve.plan: segment {segment} must be a multiple of step {step}")
+        n_seg = -(-a_len // segment)
+        src = np.arange(n_seg + 1, dtype=np.float64) * segment
+        r = 2.0 ** (self.semitones_at((src[:-1] + 0.5 * segment) / sr) / 12.0)
+        out = np.concatenate([[0.0], np.cumsum(np.diff(src) * r)])
+        time_map = TimeMap(list(zip(src / sr, out / sr)))
+        nb = -(-a_len // step)
+        pos = np.asarray(time_map.out_of_src(np.arange(nb + 1, dtype=np.float64) * step, sr), np.float64)
+        scale = np.minimum(1.0, step / np.diff(pos)).astype(np.float32)
+        return CurvePlan(time_map, pos, scale, step)
+
+
+def _pitch_curve(model, audio, curve, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phase, normalize,
+                 link_channels, transients):
+    """``pitch_shift`` along a ``PitchCurve``: stretch by the plan's tempo map, play back along its positions."""
+    a = preproc.resample(audio, osr, sr, res_type=res_type) if osr is not None else audio
+    a_len = int(a.shape[-1])
+    pl = curve.plan(a_len, sr)
+    out = reconstruct_track(model, a, n_fft, hop_length, frames, overlap_frames, stats, None, sr, res_type, clip_batch, phase,
+                            normalize=False, join="spectral", stretch=pl.time_map, link_channels=link_channels, transients=transients)
+    with torch.cuda.device(out.device):
+        out = ops.varispeed(out, torch.from_numpy(pl.pos).to(out.device), torch.from_numpy(pl.scale).to(out.device), a_len, step=pl.step,
+                            res_type=res_type)
+    return peak_normalize(out) if normalize else out
+
+
 def pitch_shift(model, audio, semitones, n_fft=2048, hop_length=512, frames=128, overlap_frames=32, stats=None, osr=None, sr=16000,
                 res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True, *, link_channels=False, transients=None, formants=None):
     """Pitch shift by ``semitones`` (within two octaves) without a change of tempo: the track is stretched by 2 ** (semitones / 12)
@@ -774,11 +898,22 @@ def pitch_shift(model, audio, semitones, n_fft=2048, hop_length=512, frames=128,
     lets the spectral envelope move with the partials (a voice shifted up sounds smaller); ``"keep"`` forwards
     ``formant_semitones=-semitones``, so the envelope is moved the other way on the analysed plane and the resampling puts it back
     where it was.
+    ``semitones`` may be a ``PitchCurve``: the transposition then varies along the track.  The track is stretched by the curve's tempo
+    map (``PitchCurve.plan``; ``reconstruct_track(stretch=TimeMap)``) and played back along the plan's position table by the
+    variable-rate resampler (``ops.varispeed``), which undoes the stretch at every block boundary: the result has exactly the
+    input's length, without a trim or a pad.  ``formants="keep"`` is not available with a curve (ValueError).
     -> float32 device tensor shaped like the input at ``sr``."""
     if formants not in FORMANTS:
         raise ValueError(f"pitch_shift: formants must be None or 'keep', got {formants!r}")
     if isinstance(semitones, TimeMap):
-        raise ValueError("pitch_shift: a TimeMap is not a pitch (a pitch curve would need a variable-rate resampler, which is not built)")
+        raise ValueError("pitch_shift: a TimeMap is not a pitch: a time-varying pitch is a PitchCurve of (seconds, semitones) anchors")
+    if isinstance(semitones, PitchCurve):
+        if formants is not None:
+            raise ValueError("pitch_shift: formants='keep' is not available with a PitchCurve (per-frame envelope ratios are not built)")
+        _check_link("pitch_shift", link_channels, "spectral", (phase,))
+        _check_transients("pitch_shift", transients, "spectral")
+        return _pitch_curve(model, audio, semitones, n_fft, hop_length, frames, overlap_frames, stats, osr, sr, res_type, clip_batch, phase,
+                            normalize, link_channels, transients)
     stretch, ratio = pitch_ratio(semitones)
     _check_link("pitch_shift", link_channels, "spectral", (phase,))
     _check_transients("pitch_shift", transients, "spectral")

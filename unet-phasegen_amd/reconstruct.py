@@ -50,6 +50,13 @@ shifted up does not turn into a smaller voice.  ``--formant_shift SEMITONES`` mo
 holds two columns per line, source seconds and output seconds (``#`` begins a comment), the map is piecewise linear between these
 anchors and every segment's stretch must lie within [0.25, 4] (``phasegen.track.TimeMap``).  It implies what ``--stretch`` implies
 and works with ``--phase``, ``--link_channels``, ``--transients``, ``--formant_shift`` and ``--stretch_report``.
+
+``--pitch_curve FILE`` (instead of ``--pitch``) shifts the pitch along a curve at the same tempo: the file holds two columns per
+line, seconds and semitones (``#`` begins a comment), the transposition is piecewise linear between these anchors, constant past the
+last one and within +-24 semitones (``phasegen.track.PitchCurve``): a glide, a vibrato, a correction.  The result has exactly the
+input's length at ``--sr``.  It implies the spectral join, works with ``--phase``, ``--link_channels`` and ``--transients`` as
+``--pitch`` does, and excludes ``--pitch``, ``--stretch``, ``--tempo_map``, ``--formants``, ``--formant_shift``, ``--report`` and
+``--stretch_report``.
 """
 import argparse
 import json
@@ -96,6 +103,9 @@ def main():
                              "linear between them (phasegen.track.TimeMap; instead of --stretch, implies --join spectral)")
     parser.add_argument("--pitch", default=None, type=float, metavar="SEMITONES",
                         help="shift the pitch at the same tempo, within +-24 semitones (implies --join spectral)")
+    parser.add_argument("--pitch_curve", default=None, metavar="FILE",
+                        help="a time-varying pitch shift at the same tempo: a text file of two columns per line, seconds and semitones, "
+                             "piecewise linear between them (phasegen.track.PitchCurve; instead of --pitch, implies --join spectral)")
     parser.add_argument("--phase", choices=["unet", "vocoder", "vocoder_locked", "spsi", "zero"], default="unet",
                         help="where the phase comes from: the model (default), the phase vocoder, plain or with identity phase locking, "
                              "single-pass inversion of the magnitudes alone (all three imply --join spectral), or none")
@@ -113,6 +123,12 @@ def main():
     args = parser.parse_args()
     if args.phase == "unet" and args.weight is None:
         parser.error("the following arguments are required: --weight")
+    if args.pitch_curve is not None:
+        for flag in ("pitch", "stretch", "tempo_map", "formants", "formant_shift", "report", "stretch_report"):
+            if getattr(args, flag) is not None:
+                parser.error(f"--pitch_curve is a pitch shift of its own: it excludes --{flag}")
+        if args.join == "waveform":
+            parser.error("--pitch_curve needs --join spectral")
     if args.stretch is not None and args.pitch is not None:
         parser.error("--stretch and --pitch exclude each other")
     if args.tempo_map is not None and (args.stretch is not None or args.pitch is not None):
@@ -129,7 +145,8 @@ def main():
     if args.formant_shift is not None and args.report is not None:
         parser.error("--report compares against the input: it does not work with --formant_shift")
     formant_shift = 0.0 if args.formant_shift is None else args.formant_shift
-    modified = (args.stretch is not None and args.stretch != 1.0) or args.pitch is not None or args.tempo_map is not None
+    modified = ((args.stretch is not None and args.stretch != 1.0) or args.pitch is not None or args.tempo_map is not None
+                or args.pitch_curve is not None)
     if modified and args.join == "waveform":
         parser.error("--stretch and --pitch need --join spectral")
     if modified and args.report is not None:
@@ -140,7 +157,7 @@ def main():
         parser.error("--report measures the model's phase: it needs --phase unet")
     if args.link_channels and args.phase != "vocoder_locked":
         parser.error("--link_channels needs --phase vocoder_locked")
-    if args.transients is not None and not stretched and args.pitch is None:
+    if args.transients is not None and not stretched and args.pitch is None and args.pitch_curve is None:
         parser.error("--transients needs --stretch or --pitch")
     if args.transients is not None and args.report is not None:
         parser.error("--report compares against the input: it does not work with --transients")
@@ -197,8 +214,9 @@ def main():
     kw = dict(n_fft=n_fft, hop_length=hop, frames=args.frames, overlap_frames=args.overlap_frames, stats=stats, osr=file_sr, sr=args.sr)
     report = None
     stretch_report = None
-    if args.pitch is not None:
-        out = track.pitch_shift(model, audio, args.pitch, phase=args.phase, link_channels=args.link_channels, transients=args.transients,
+    if args.pitch is not None or args.pitch_curve is not None:
+        semitones = args.pitch if args.pitch_curve is None else track.PitchCurve.load(args.pitch_curve)
+        out = track.pitch_shift(model, audio, semitones, phase=args.phase, link_channels=args.link_channels, transients=args.transients,
                                 formants=args.formants, **kw)
     elif args.stretch_report is not None:
         # (the locked vocoder and spsi are reported when they are asked for; the other modes' reports stay as they were)
