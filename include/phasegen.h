@@ -928,6 +928,48 @@ typedef struct pg_varispeed_args {
 } pg_varispeed_args;                             /* 72 bytes */
 int     pg_varispeed(const pg_varispeed_args* a, void* stream);
 
+/* pg_pitch_track: a fundamental-frequency tracker, YIN (de Cheveigne and Kawahara 2002) per frame -- the measuring half of a pitch
+ * correction (phasegen/track.py, detect_pitch, PitchCurve.correcting, autotune).  Struct of its own, PG_VERSION unchanged; the
+ * reference has no counterpart; the arithmetic below is the contract: every operation a separate IEEE float32 operation (nothing
+ * contracted, division correctly rounded), so a numpy restatement reproduces the kernel bit for bit.
+ *   Frame f of a row holds the samples x_j = x[f hop + j], j = 0 .. W + tau_max - 1.  A sample at or beyond n_in counts as +0.0f
+ *   and is not read; the next row and the stride padding are never read.  Index arithmetic is 64-bit inside.
+ *   1. Difference function.  d(0) = 0.  For tau = 1 .. tau_max: acc = 0; for j = 0 .. W - 1 ascending: e = fl(x_j - x_{j+tau}),
+ *      acc = fl(acc + fl(e e)); d(tau) = acc.
+ *   2. Running sum.  S(0) = 0, S(tau) = fl(S(tau - 1) + d(tau)), ascending.
+ *   3. Non-finite gate.  If S(tau_max) is not finite, period[f] = ap[f] = NaN (quiet, positive: 0x7fc00000) and the frame is done.
+ *      This covers a NaN or an Inf anywhere in the frame's W + tau_max samples (every one of them enters some d(tau)) and an
+ *      overflow of the squares.  No other frame is affected.
+ *   4. Normalised difference.  cm(0) = 1; for tau >= 1: cm(tau) = S(tau) > 0 ? fl(fl(d(tau) (float)tau) / S(tau)) : 1.0f.
+ *   5. Pick.  A = [tau_min, tau_max - 1].  If some tau in A has cm(tau) < threshold, take the smallest; then, while tau + 1 is in A
+ *      and cm(tau + 1) < cm(tau), step to tau + 1.  Otherwise take the smallest tau in A that attains min cm over A.  A NaN
+ *      threshold never matches.  Both searches are exact comparisons, so any reduction order gives the same tau^.
+ *   6. Refine.  a = cm(tau^ - 1), b = cm(tau^), c = cm(tau^ + 1) (both neighbours exist: tau_min >= 2, cm is defined up to
+ *      tau_max).  den = fl(fl(a + c) - fl(2 b)); delta = den > 0 ? clamp(fl(fl(0.5f fl(a - c)) / den), -1, 1) : 0, with
+ *      clamp(q) = q < -1 ? -1 : (q > 1 ? 1 : q); period[f] = fl((float)tau^ + delta), ap[f] = b.
+ *   Consequences.  A frame's bits depend on its own W + tau_max samples and on nothing else: not on n_sig, the row's place, frames,
+ *   or how frames share a workgroup.  Silence, a constant row and values whose squares underflow give S = 0, so cm = 1 everywhere,
+ *   period = tau_min and ap = 1.  Scaling a row by a power of two that causes neither overflow nor underflow leaves both outputs
+ *   bit-identical.  Voicing is the caller's decision (ap < threshold): the kernel always writes both values.
+ *   Sizes.  Every size is an int32_t and the strides are counts of elements.  There is no workspace: the library allocates nothing
+ *   and keeps nothing.
+ *   Kernel: one workgroup per up to four consecutive frames of a row, their common span staged in LDS once; a lane owns five
+ *   consecutive lags and a sliding register window; the running sum is one serial chain in one lane; the searches are shuffle
+ *   reductions.  No atomics, no global scratch; one launch on the caller's stream.
+ *   Errors (host side, before any launch, in this order): NULL args PG_ERR_NULL; non-positive n_sig / n_in / frames / hop
+ *   PG_ERR_SHAPE; window, tau_min or tau_max outside the limits PG_ERR_UNSUPPORTED; a stride shorter than its row PG_ERR_SHAPE;
+ *   x, period or ap NULL PG_ERR_NULL.  Messages begin "pitch_track: ". */
+typedef struct pg_pitch_track_args {
+    int32_t n_sig, n_in, frames, hop;            /* frame f of a row begins at sample f * hop                        */
+    int32_t window, tau_min, tau_max;            /* W in [4, 2048]; 2 <= tau_min < tau_max <= 1024                   */
+    int32_t x_stride, out_stride;                /* rows x_stride >= n_in samples, out_stride >= frames values apart */
+    float   threshold;                           /* theta of the absolute threshold; any float                       */
+    const float* x;                              /* (n_sig, n_in)                                                    */
+    float* period;                               /* (n_sig, frames): the period in samples                           */
+    float* ap;                                   /* (n_sig, frames): the aperiodicity d'(tau^)                       */
+} pg_pitch_track_args;                           /* 64 bytes */
+int     pg_pitch_track(const pg_pitch_track_args* a, void* stream);
+
 /* pg_formant_shift: the spectral envelope of every frame of a log1p-magnitude plane and, optionally, the plane with that envelope
  * re-imposed at `ratio` times each bin's frequency -- formant preservation for a pitch shift (phasegen/track.py, formant_semitones,
  * pitch_shift(formants="keep")): the resampling that moves the partials moves the envelope with them, and this moves it back.

@@ -287,6 +287,18 @@ class VarispeedArgs(C.Structure):
                 ("pos", C.c_void_p), ("scale", C.c_void_p), ("table", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p)]
 
 
+PITCH_MIN_WINDOW, PITCH_MAX_WINDOW, PITCH_MIN_TAU, PITCH_MAX_TAU = 4, 2048, 2, 1024     # pg_pitch_track's limits
+
+
+class PitchTrackArgs(C.Structure):
+    """pg_pitch_track_args: YIN per frame -- the period and the aperiodicity of every frame of every row (include/phasegen.h).  No
+    64-bit integer field and no workspace: every size is an int32 and the strides are counts of elements."""
+    _fields_ = [("n_sig", C.c_int32), ("n_in", C.c_int32), ("frames", C.c_int32), ("hop", C.c_int32),
+                ("window", C.c_int32), ("tau_min", C.c_int32), ("tau_max", C.c_int32),
+                ("x_stride", C.c_int32), ("out_stride", C.c_int32), ("threshold", C.c_float),
+                ("x", C.c_void_p), ("period", C.c_void_p), ("ap", C.c_void_p)]
+
+
 class WaveCompareArgs(C.Structure):
     """pg_wave_compare_args: six sums per signal of a reference / estimate pair of waveforms (include/phasegen.h)."""
     _fields_ = [("n_signals", C.c_int32), ("_pad0", C.c_int32), ("n", C.c_int64),
@@ -373,6 +385,7 @@ SYMBOLS = {
     "pg_varispeed_table_elems": (C.c_int64, [C.c_int32, C.c_int32]),
     "pg_varispeed_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     "pg_varispeed": (C.c_int, [C.POINTER(VarispeedArgs), C.c_void_p]),
+    "pg_pitch_track": (C.c_int, [C.POINTER(PitchTrackArgs), C.c_void_p]),
     "pg_workspace_bytes_wave_compare": (C.c_int64, [C.POINTER(WaveCompareArgs)]),
     "pg_wave_compare": (C.c_int, [C.POINTER(WaveCompareArgs), C.c_void_p]),
     "pg_workspace_bytes_spec_compare": (C.c_int64, [C.POINTER(SpecCompareArgs)]),

@@ -882,6 +882,67 @@ def varispeed(x, pos, scale, n_out, step=64, res_type="kaiser_best", per_zero=51
     return out
 
 
+def pitch_frames(n_in, hop=256, window=1024, tau_max=320):
+    """the complete frames of ``pitch_track`` in a row of ``n_in`` samples: max(1, 1 + (n_in - window - tau_max) // hop)"""
+    return max(1, 1 + (int(n_in) - int(window) - int(tau_max)) // int(hop))
+
+
+def pitch_track(x, frames=None, hop=256, window=1024, tau_min=16, tau_max=320, threshold=0.15, out=None):
+    """The fundamental period of every frame of every row, YIN (pg_pitch_track): x (n,) or (n_signals, n) float32 on the device whose
+    rows are contiguous (the row stride is free) -> (period, ap), each (..., frames) float32.  Frame f holds the ``window + tau_max``
+    samples from f * hop on (zeros past the row's end); ``period[f]`` is the lag in [tau_min, tau_max - 1] picked by the absolute
+    ``threshold`` on the cumulative-mean-normalised difference, refined by a parabola (in samples: f0 = sr / period), ``ap[f]`` the
+    normalised difference there: a frame is voiced where ``ap < threshold`` (the caller's decision; both are NaN for a frame that
+    holds a non-finite sample).  ``frames=None``: the complete frames, ``pitch_frames(n, hop, window, tau_max)``.  ``window`` within
+    [4, 2048], 2 <= tau_min < tau_max <= 1024.  ``out=(period, ap)``: views that are written in place.  Runs on the current stream
+    and never synchronises."""
+    who = "pitch_track"
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() in (1, 2)):
+        raise ValueError(f"{who}: expected a 1-D or 2-D float32 device tensor")
+    _on_current_device(x, "x")
+    x2 = x[None] if x.dim() == 1 else x
+    n_sig, n_in = x2.shape
+    hop, window, tau_min, tau_max, threshold = int(hop), int(window), int(tau_min), int(tau_max), float(threshold)
+    if n_sig < 1 or n_in < 1:
+        raise ValueError(f"{who}: empty input {tuple(x.shape)}")
+    if n_in > 1 and x2.stride(1) != 1:
+        raise ValueError(f"{who}: samples must be contiguous (strides {x.stride()})")
+    if hop < 1:
+        raise ValueError(f"{who}: hop must be positive, got {hop}")
+    if not _lib.PITCH_MIN_WINDOW <= window <= _lib.PITCH_MAX_WINDOW:
+        raise ValueError(f"{who}: window must be within [{_lib.PITCH_MIN_WINDOW}, {_lib.PITCH_MAX_WINDOW}], got {window}")
+    if not _lib.PITCH_MIN_TAU <= tau_min < tau_max <= _lib.PITCH_MAX_TAU:
+        raise ValueError(f"{who}: lags must satisfy {_lib.PITCH_MIN_TAU} <= tau_min < tau_max <= {_lib.PITCH_MAX_TAU}, got {tau_min} and {tau_max}")
+    frames = pitch_frames(n_in, hop, window, tau_max) if frames is None else int(frames)
+    if frames < 1:
+        raise ValueError(f"{who}: frames must be positive, got {frames}")
+    want = (frames,) if x.dim() == 1 else (n_sig, frames)
+    if out is None:
+        period, ap = _out(None, want, x.device, who), _out(None, want, x.device, who)
+    else:
+        try:
+            period, ap = out
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: out must be (period, ap)")
+        if not (torch.is_tensor(period) and torch.is_tensor(ap)):
+            raise ValueError(f"{who}: out must be (period, ap)")
+        period, ap = _out(period, want, x.device, who, rows=True), _out(ap, want, x.device, who, rows=True)
+    p2, a2 = (period[None], ap[None]) if x.dim() == 1 else (period, ap)
+    x_stride = x2.stride(0) if n_sig > 1 else n_in
+    o_stride = p2.stride(0) if n_sig > 1 else frames
+    if n_sig > 1 and a2.stride(0) != o_stride:
+        raise ValueError(f"{who}: period and ap must have the same row stride (strides {period.stride()} and {ap.stride()})")
+    if x_stride < n_in or o_stride < frames:
+        raise ValueError(f"{who}: rows overlap in memory (strides {x.stride()} and {period.stride()})")
+    _int32_sizes(who, n_in=n_in, frames=frames, hop=hop, x_stride=x_stride, out_stride=o_stride)
+    a = _lib.PitchTrackArgs()
+    a.n_sig, a.n_in, a.frames, a.hop, a.window, a.tau_min, a.tau_max = n_sig, n_in, frames, hop, window, tau_min, tau_max
+    a.x_stride, a.out_stride, a.threshold = x_stride, o_stride, threshold
+    a.x, a.period, a.ap = x2.data_ptr(), p2.data_ptr(), a2.data_ptr()
+    _lib.check(_lib.load().pg_pitch_track(C.byref(a), _stream()), who)
+    return period, ap
+
+
 _stitch_ramps = {}       # (V, device) -> device copy of pg_stitch_ramp's output (read-only)
 _stitch_ws = _StreamCache()
 _caches.append(_stitch_ws)

@@ -54,6 +54,10 @@ reads them instead of the one rate (``pos=`` of ops.spec_clips, phase_vocoder, p
 semitones), piecewise linear between them.  ``PitchCurve.plan`` turns it into a tempo map for the stretch (every 256 samples at the
 stretch 2 ** (semitones / 12) of their midpoint) and into the position and bandwidth tables of the variable-rate resampler that plays
 the stretched track back (ops.varispeed), block by block of 64 samples, so that the result has the input's length and tempo.
+
+``detect_pitch`` measures what a curve is drawn against: the fundamental frequency of a monophonic take, frame by frame (YIN on the
+device, ops.pitch_track), as a ``PitchTrack`` of host arrays.  ``PitchCurve.correcting`` turns a track into the curve that pulls
+every voiced frame to the nearest degree of a scale, and ``autotune`` is the three in a row: detect, correct, ``pitch_shift``.
 """
 import collections
 import fractions
@@ -773,6 +777,22 @@ CurvePlan = collections.namedtuple("CurvePlan", "time_map pos scale step")
 PITCH_CURVE_STEP, PITCH_CURVE_SEGMENT = 64, 256                   # ops.varispeed's block and PitchCurve.plan's segment, in samples
 
 
+PitchTrack = collections.namedtuple("PitchTrack", "times f0 voiced ap")
+TONICS = {"C": 0, "C#": 1, "Db": 1, "D": 2, "D#": 3, "Eb": 3, "E": 4, "F": 5, "F#": 6, "Gb": 6, "G": 7, "G#": 8, "Ab": 8, "A": 9, "A#": 10,
+          "Bb": 10, "B": 11}
+SCALE_DEGREES = {"maj": (0, 2, 4, 5, 7, 9, 11), "min": (0, 2, 3, 5, 7, 8, 10)}
+
+
+def scale_classes(scale):
+    """the pitch classes (0 = C) of "chromatic", "<tonic>:maj" or "<tonic>:min" (natural minor), as a frozenset"""
+    if scale == "chromatic":
+        return frozenset(range(12))
+    tonic, _, mode = scale.partition(":") if isinstance(scale, str) else ("", "", "")
+    if tonic not in TONICS or mode not in SCALE_DEGREES:
+        raise ValueError(f"scale must be 'chromatic', '<tonic>:maj' or '<tonic>:min' with a tonic among {', '.join(TONICS)}, got {scale!r}")
+    return frozenset((TONICS[tonic] + d) % 12 for d in SCALE_DEGREES[mode])
+
+
 class PitchCurve:
     """A pitch curve: a time-varying transposition, piecewise linear in semitones between anchors and constant past the last one
     (host only, float64).  ``anchors``: a sequence of (seconds, semitones) with at least two entries, finite, the first at 0 s,
@@ -781,7 +801,10 @@ class PitchCurve:
 
     def __init__(self, anchors):
         try:
-            a = np.array([[float(v) for v in row] for row in anchors], dtype=np.float64)
+            if isinstance(anchors, np.ndarray) and anchors.dtype == np.float64:
+                a = anchors.copy()                                # (thousands of anchors, as ``correcting`` makes them: no Python lists)
+            else:
+                a = np.array([[float(v) for v in row] for row in anchors], dtype=np.float64)
         except (TypeError, ValueError) as e:
             raise ValueError(f"PitchCurve: anchors must be (seconds, semitones) pairs ({e})")
         if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 2:
@@ -845,6 +868,64 @@ class PitchCurve:
             f.write("# seconds semitones\n")
             for t, s in zip(self.seconds, self.semitones):
                 f.write(f"{float(t)!r} {float(s)!r}\n")
+
+    @classmethod
+    def correcting(cls, pitch_track, strength=1.0, scale="chromatic", a4=440.0, retune_ms=0.0):
+        """The curve that corrects a detected ``PitchTrack`` (``detect_pitch``) towards the nearest note of ``scale`` (host, float64).
+          m_k = 69 + 12 log2(f0_k / a4) at a voiced frame; its target is the nearest note whose pitch class is in the scale, the
+          lower one on a tie.  ``scale``: "chromatic", "<tonic>:maj" or "<tonic>:min" (natural minor), tonic C, C#, Db, ... B.
+          c_k = strength (target - m_k) at voiced frames; an unvoiced frame holds the previous voiced value, the frames before the
+          first voiced one take its value, a track without a voiced frame gives the zero curve.
+          y_k = y_{k-1} + alpha (c_k - y_{k-1}), y_{-1} = c_0, alpha = 1 - exp(-dt / (retune_ms / 1000)) with dt the spacing of the
+          track's frames (hop / sr); alpha = 1 for retune_ms = 0: how fast a note is pulled in.
+        Anchors: (0, y_0) and then (times[k], y_k).  ``strength`` within [0, 1], ``a4`` and ``retune_ms`` finite, a4 > 0,
+        retune_ms >= 0, else ValueError."""
+        who = "PitchCurve.correcting"
+        try:
+            times, f0, voiced = (np.asarray(v) for v in (pitch_track.times, pitch_track.f0, pitch_track.voiced))
+        except AttributeError:
+            raise ValueError(f"{who}: expected a PitchTrack (times, f0, voiced, ap)")
+        times, f0, voiced = times.astype(np.float64), f0.astype(np.float64), voiced.astype(bool)
+        if times.ndim != 1 or times.shape[0] < 1 or f0.shape != times.shape or voiced.shape != times.shape:
+            raise ValueError(f"{who}: times, f0 and voiced must be 1-D arrays of one length, at least 1")
+        if not (np.isfinite(times).all() and times[0] > 0.0 and (np.diff(times) > 0.0).all()):
+            raise ValueError(f"{who}: times must be finite, positive and strictly increasing")
+        strength, a4, retune_ms = float(strength), float(a4), float(retune_ms)
+        if not 0.0 <= strength <= 1.0:
+            raise ValueError(f"{who}: strength must be within [0, 1], got {strength}")
+        if not (0.0 < a4 < math.inf):
+            raise ValueError(f"{who}: a4 must be positive and finite, got {a4}")
+        if not (0.0 <= retune_ms < math.inf):
+            raise ValueError(f"{who}: retune_ms must be non-negative and finite, got {retune_ms}")
+        classes = scale_classes(scale)
+        if voiced.any() and not (np.isfinite(f0[voiced]).all() and (f0[voiced] > 0.0).all()):
+            raise ValueError(f"{who}: f0 must be positive and finite at voiced frames")
+        c = np.zeros(times.shape[0], np.float64)
+        if voiced.any():
+            m = 69.0 + 12.0 * np.log2(f0[voiced] / a4)
+            notes = np.array([n for n in range(-60, 200) if n % 12 in classes], dtype=np.float64)
+            if m.min() < notes[0] or m.max() > notes[-1]:
+                raise ValueError(f"{who}: f0 outside the notes {notes[0]:.0f} .. {notes[-1]:.0f} of a4 = {a4}")
+            hi = np.searchsorted(notes, m, side="left")                              # notes[hi - 1] < m <= notes[hi]
+            hi = np.clip(hi, 1, len(notes) - 1)
+            below, above = notes[hi - 1], notes[hi]
+            target = np.where(above - m < m - below, above, below)                   # a tie goes to the lower note
+            idx = np.flatnonzero(voiced)
+            held = np.maximum.accumulate(np.where(voiced, np.arange(times.shape[0]), -1))   # the last voiced frame at or before k
+            held = np.where(held < 0, idx[0], held)
+            full = np.zeros(times.shape[0], np.float64)
+            full[idx] = strength * (target - m)
+            c = full[held]
+        if retune_ms > 0.0 and times.shape[0] > 1:
+            alpha = 1.0 - math.exp(-float(times[1] - times[0]) / (retune_ms / 1000.0))
+            y = np.empty_like(c)
+            prev = c[0]
+            for k in range(c.shape[0]):
+                prev = prev + alpha * (c[k] - prev)
+                y[k] = prev
+        else:
+            y = c
+        return cls(np.column_stack([np.concatenate([[0.0], times]), np.concatenate([y[:1], y])]))
 
     def plan(self, a_len, sr=16000, step=PITCH_CURVE_STEP, segment=PITCH_CURVE_SEGMENT):
         """The two halves of a pitch shift along this curve for a track of ``a_len`` samples at ``sr`` (host only): a
@@ -929,3 +1010,81 @@ def pitch_shift(model, audio, semitones, n_fft=2048, hop_length=512, frames=128,
     else:
         out = torch.nn.functional.pad(out, (0, a_len - out.shape[-1]))
     return peak_normalize(out) if normalize else out.contiguous()
+
+
+def pitch_lags(sr, fmin, fmax):
+    """(tau_min, tau_max) of ``detect_pitch``: max(2, floor(sr / fmax)) and min(1024, ceil(sr / fmin))"""
+    sr, fmin, fmax = int(sr), float(fmin), float(fmax)
+    if sr < 1 or not (0.0 < fmin < fmax < math.inf):
+        raise ValueError(f"detect_pitch: sr {sr} must be positive and 0 < fmin < fmax, got {fmin} and {fmax}")
+    tau_min, tau_max = max(2, int(math.floor(sr / fmax))), min(1024, int(math.ceil(sr / fmin)))
+    if tau_min >= tau_max:
+        raise ValueError(f"detect_pitch: fmin {fmin} .. fmax {fmax} leaves no lags at sr {sr} (tau_min {tau_min}, tau_max {tau_max})")
+    return tau_min, tau_max
+
+
+def _median_log(f0, voiced, median):
+    """f0 at voiced frames replaced by the median, in log frequency, of the voiced frames within k +- median // 2 (the mean of the
+    two middle ones when their count is even)"""
+    half = int(median) // 2
+    out = f0.copy()
+    if half < 1 or not voiced.any():
+        return out
+    n = f0.shape[0]
+    logf = np.full(n + 2 * half, np.inf)
+    logf[half:half + n] = np.where(voiced, np.log(np.where(voiced, f0, 1.0)), np.inf)
+    win = np.sort(np.stack([logf[k:k + n] for k in range(2 * half + 1)], axis=1), axis=1)      # the voiced ones first, ascending
+    count = np.isfinite(win).sum(axis=1)
+    rows = np.flatnonzero(voiced)
+    c = count[rows]
+    mid = (win[rows, (c - 1) // 2] + win[rows, c // 2]) / 2.0
+    out[rows] = np.exp(mid)
+    return out
+
+
+def detect_pitch(audio, sr=16000, osr=None, fmin=50.0, fmax=1000.0, hop_length=256, window=1024, threshold=0.15, median=5,
+                 res_type="kaiser_best"):
+    """The fundamental frequency of a monophonic take, frame by frame: YIN on the device (ops.pitch_track) -> a ``PitchTrack(times,
+    f0, voiced, ap)`` of host arrays (float64, bool).  ``audio``: (samples,) or (channels, samples), numpy or tensor, at ``osr``
+    (resampled to ``sr`` on the device, as ``reconstruct_track``) or at ``sr``; stereo is tracked on the channel mean, formed on the
+    device.  Lags: ``pitch_lags(sr, fmin, fmax)``; the complete frames of ``window + tau_max`` samples, ``hop_length`` apart.
+      times[k] = (k hop_length + window / 2) / sr        the middle of frame k's window, in seconds
+      voiced   = isfinite(ap) & (ap < threshold)
+      f0       = sr / period at voiced frames, then replaced by the median, in log frequency, of the voiced frames within
+                 k +- median // 2 (isolated octave slips go); 0 at unvoiced frames."""
+    tau_min, tau_max = pitch_lags(sr, fmin, fmax)
+    hop_length, window, median = int(hop_length), int(window), int(median)
+    if median < 1:
+        raise ValueError(f"detect_pitch: median must be at least 1, got {median}")
+    an = _load(audio, osr, sr, res_type)
+    with torch.cuda.device(an.a2.device), torch.no_grad():
+        mono = an.a2[0] if an.n_ch == 1 else an.a2.mean(dim=0)
+        period, ap = ops.pitch_track(mono, None, hop_length, window, tau_min, tau_max, threshold)
+        both = torch.stack([period, ap]).cpu().numpy().astype(np.float64)          # the one copy to the host
+    period, ap = both[0], both[1]
+    times = (np.arange(period.shape[0], dtype=np.float64) * hop_length + window / 2.0) / sr
+    with np.errstate(invalid="ignore", divide="ignore"):
+        voiced = np.isfinite(ap) & (ap < float(threshold))
+        f0 = np.where(voiced, sr / np.where(voiced, period, 1.0), 0.0)
+    return PitchTrack(times, _median_log(f0, voiced, median), voiced, ap)
+
+
+def autotune(model, audio, strength=1.0, scale="chromatic", a4=440.0, retune_ms=50.0, n_fft=2048, hop_length=512, frames=128,
+             overlap_frames=32, stats=None, osr=None, sr=16000, res_type="kaiser_best", clip_batch=64, phase="unet", normalize=True, *,
+             link_channels=False, transients=None, formants=None, fmin=50.0, fmax=1000.0, threshold=0.15, median=5, return_curve=False):
+    """Pitch correction of a monophonic take: ``detect_pitch`` (``fmin``, ``fmax``, ``threshold``, ``median``), then
+    ``PitchCurve.correcting`` (``strength``, ``scale``, ``a4``, ``retune_ms``), then ``pitch_shift`` along that curve with the other
+    arguments -> float32 device tensor shaped like the input at ``sr``; with ``return_curve=True`` -> (tensor, PitchTrack,
+    PitchCurve).  ``strength=0`` is ``pitch_shift`` along the zero curve.  The refusals are the curve path's (``formants="keep"``)."""
+    if formants not in FORMANTS:
+        raise ValueError(f"autotune: formants must be None or 'keep', got {formants!r}")
+    if formants is not None:
+        raise ValueError("autotune: formants='keep' is not available with a PitchCurve (per-frame envelope ratios are not built)")
+    _check_link("autotune", link_channels, "spectral", (phase,))
+    _check_transients("autotune", transients, "spectral")
+    a = preproc.resample(audio, osr, sr, res_type=res_type) if osr is not None else audio
+    pt = detect_pitch(a, sr, None, fmin, fmax, threshold=threshold, median=median)
+    curve = PitchCurve.correcting(pt, strength, scale, a4, retune_ms)
+    out = pitch_shift(model, a, curve, n_fft, hop_length, frames, overlap_frames, stats, None, sr, res_type, clip_batch, phase, normalize,
+                      link_channels=link_channels, transients=transients)
+    return (out, pt, curve) if return_curve else out

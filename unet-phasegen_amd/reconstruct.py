@@ -57,6 +57,13 @@ last one and within +-24 semitones (``phasegen.track.PitchCurve``): a glide, a v
 input's length at ``--sr``.  It implies the spectral join, works with ``--phase``, ``--link_channels`` and ``--transients`` as
 ``--pitch`` does, and excludes ``--pitch``, ``--stretch``, ``--tempo_map``, ``--formants``, ``--formant_shift``, ``--report`` and
 ``--stretch_report``.
+
+``--autotune [STRENGTH]`` corrects the pitch of a monophonic take: the fundamental is tracked frame by frame on the device
+(``phasegen.track.detect_pitch``, YIN between ``--fmin`` and ``--fmax`` Hz), every voiced frame is pulled by STRENGTH (0 .. 1,
+default 1) of its distance to the nearest note of ``--scale`` (``chromatic``, ``<tonic>:maj`` or ``<tonic>:min``; ``--a4`` tunes the
+reference, ``--retune_ms`` sets how fast a note is pulled in) and the take is shifted along that curve as by ``--pitch_curve``, whose
+exclusions it shares; it excludes ``--pitch_curve`` itself.  ``--pitch_report FILE`` writes the detected track as JSON (``times``,
+``f0``, ``voiced``, ``ap`` and, with ``--autotune``, the ``curve``'s anchors); it also works alone, beside whatever else is written.
 """
 import argparse
 import json
@@ -106,6 +113,16 @@ def main():
     parser.add_argument("--pitch_curve", default=None, metavar="FILE",
                         help="a time-varying pitch shift at the same tempo: a text file of two columns per line, seconds and semitones, "
                              "piecewise linear between them (phasegen.track.PitchCurve; instead of --pitch, implies --join spectral)")
+    parser.add_argument("--autotune", default=None, type=float, nargs="?", const=1.0, metavar="STRENGTH",
+                        help="correct the pitch of a monophonic take towards the nearest note of --scale, by STRENGTH of the distance "
+                             "(0 .. 1, default 1; phasegen.track.autotune; implies --join spectral)")
+    parser.add_argument("--scale", default="chromatic", help="with --autotune: chromatic (default), <tonic>:maj or <tonic>:min, e.g. A:min")
+    parser.add_argument("--a4", default=440.0, type=float, help="with --autotune: the frequency of A4 in Hz")
+    parser.add_argument("--retune_ms", default=50.0, type=float, help="with --autotune: the time constant with which a note is pulled in (0: at once)")
+    parser.add_argument("--fmin", default=50.0, type=float, help="with --autotune or --pitch_report: the lowest fundamental looked for, Hz")
+    parser.add_argument("--fmax", default=1000.0, type=float, help="with --autotune or --pitch_report: the highest fundamental looked for, Hz")
+    parser.add_argument("--pitch_report", default=None, metavar="FILE",
+                        help="write the detected pitch track as JSON: times, f0, voiced, ap and, with --autotune, the curve's anchors")
     parser.add_argument("--phase", choices=["unet", "vocoder", "vocoder_locked", "spsi", "zero"], default="unet",
                         help="where the phase comes from: the model (default), the phase vocoder, plain or with identity phase locking, "
                              "single-pass inversion of the magnitudes alone (all three imply --join spectral), or none")
@@ -123,6 +140,14 @@ def main():
     args = parser.parse_args()
     if args.phase == "unet" and args.weight is None:
         parser.error("the following arguments are required: --weight")
+    if args.autotune is not None:
+        for flag in ("pitch", "stretch", "tempo_map", "pitch_curve", "formants", "formant_shift", "report", "stretch_report"):
+            if getattr(args, flag) is not None:
+                parser.error(f"--autotune is a pitch shift of its own: it excludes --{flag}")
+        if args.join == "waveform":
+            parser.error("--autotune needs --join spectral")
+        if not 0.0 <= args.autotune <= 1.0:
+            parser.error("--autotune STRENGTH must be within [0, 1]")
     if args.pitch_curve is not None:
         for flag in ("pitch", "stretch", "tempo_map", "formants", "formant_shift", "report", "stretch_report"):
             if getattr(args, flag) is not None:
@@ -146,7 +171,7 @@ def main():
         parser.error("--report compares against the input: it does not work with --formant_shift")
     formant_shift = 0.0 if args.formant_shift is None else args.formant_shift
     modified = ((args.stretch is not None and args.stretch != 1.0) or args.pitch is not None or args.tempo_map is not None
-                or args.pitch_curve is not None)
+                or args.pitch_curve is not None or args.autotune is not None)
     if modified and args.join == "waveform":
         parser.error("--stretch and --pitch need --join spectral")
     if modified and args.report is not None:
@@ -157,7 +182,7 @@ def main():
         parser.error("--report measures the model's phase: it needs --phase unet")
     if args.link_channels and args.phase != "vocoder_locked":
         parser.error("--link_channels needs --phase vocoder_locked")
-    if args.transients is not None and not stretched and args.pitch is None and args.pitch_curve is None:
+    if args.transients is not None and not stretched and args.pitch is None and args.pitch_curve is None and args.autotune is None:
         parser.error("--transients needs --stretch or --pitch")
     if args.transients is not None and args.report is not None:
         parser.error("--report compares against the input: it does not work with --transients")
@@ -214,7 +239,15 @@ def main():
     kw = dict(n_fft=n_fft, hop_length=hop, frames=args.frames, overlap_frames=args.overlap_frames, stats=stats, osr=file_sr, sr=args.sr)
     report = None
     stretch_report = None
-    if args.pitch is not None or args.pitch_curve is not None:
+    pitch_track = pitch_curve = None
+    if args.autotune is not None:
+        try:
+            out, pitch_track, pitch_curve = track.autotune(model, audio, args.autotune, args.scale, args.a4, args.retune_ms, phase=args.phase,
+                                                           link_channels=args.link_channels, transients=args.transients, fmin=args.fmin,
+                                                           fmax=args.fmax, return_curve=True, **kw)
+        except ValueError as e:
+            parser.error(f"--autotune: {e}")
+    elif args.pitch is not None or args.pitch_curve is not None:
         semitones = args.pitch if args.pitch_curve is None else track.PitchCurve.load(args.pitch_curve)
         out = track.pitch_shift(model, audio, semitones, phase=args.phase, link_channels=args.link_channels, transients=args.transients,
                                 formants=args.formants, **kw)
@@ -231,12 +264,24 @@ def main():
     else:
         report = track.evaluate_track(model, audio, phases=phases, gl_iters=args.gl_iters, return_audio=True, join=join, gl_init=args.gl_init, **kw)
         out = track.peak_normalize(report.pop("audio")["unet"])
+    if args.pitch_report is not None and pitch_track is None:
+        pitch_track = track.detect_pitch(audio, args.sr, file_sr, args.fmin, args.fmax)
     out = out.cpu().numpy()
     took = time.time() - start
     n = out.shape[-1]
     _, _, n_clips = track.track_plan(n, args.frames, hop, args.overlap_frames)
     wavfile.write(args.output, args.sr, np.ascontiguousarray(out.T if out.ndim == 2 else out, dtype=np.float32))
     print("Reconstructed {:.2f} s of audio in {:.3f} s ({} clips).".format(n / args.sr, took, n_clips))
+    if pitch_track is not None and args.pitch_report is not None:
+        doc = dict(input=os.path.abspath(args.input), sr=args.sr, times=pitch_track.times.tolist(), f0=pitch_track.f0.tolist(),
+                   voiced=pitch_track.voiced.tolist(), ap=[None if v != v else v for v in pitch_track.ap.tolist()])
+        if pitch_curve is not None:
+            doc["curve"] = [list(a) for a in pitch_curve.anchors]
+        with open(args.pitch_report, "w") as f:
+            json.dump(doc, f, indent=1)
+        voiced = pitch_track.voiced
+        print("Pitch report: {} of {} frames voiced{}.".format(int(voiced.sum()), voiced.shape[0], "" if not voiced.any() else
+              ", f0 {:.1f} .. {:.1f} Hz".format(float(pitch_track.f0[voiced].min()), float(pitch_track.f0[voiced].max()))))
     if report is not None:
         report.update(input=os.path.abspath(args.input), seconds=n / args.sr, flags=vars(args))
         with open(args.report, "w") as f:
